@@ -1,7 +1,13 @@
 #!/usr/bin/env python3
 """bench.py -- sweeps/s of the 3D-Dual-Fusion hot path on MI355X (BASELINE.json metric).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, runs the W warm-up steps, times the K steps and prints the headline line (metric, value, unit,
+higher_is_better, dtype, ms_per_step, config, reduced_losses).  --dump-outputs DIR then writes what the last timed step
+returned to its caller as DIR/<name>.npy (float32, or float64 for float64 / integer arrays; a fixed, seeded sample of
+each array when all of them together exceed 64 MB).  The inputs are synthetic and seeded: the same arguments give the
+same inputs in every run.  --full adds everything else this script measures (listed below) to the same line.
 
 With N > 1 and no WORLD_SIZE in the environment the script starts its own N ranks (one process per GPU,
 torch.distributed.run, 127.0.0.1 rendezvous, backend nccl = RCCL over xGMI); launched BY torch.distributed.run it
@@ -16,11 +22,14 @@ Frames are independent: ranks process different sweeps (weak scaling); the loss 
 collective.  Every step takes the NEXT of >= 8 distinct frames (sweep, camera feature maps, calibration, targets) and
 fresh batch_dict / example objects, as a data loader would hand them over.
 
-Besides the driver contract the JSON line carries
+With --full the JSON line also carries
   hot_path      the same K steps ending at the dense BEV tensor (round-1's step), timed in a second pass
   fp32          both of the above with every sparse conv on the exact-fp32 MFMA kernels (--conv-precision fp32)
+  split3        the same with three bf16 operand parts, and `in_flight` (--inflight frames in flight in one process)
   roofline      dominant sparse-conv kernel: SURVEY 8(d) algorithmic bytes / HIP-event time, measured in the timed region
   cpu_baseline  the reference's own compiled CPU ops (oracle/_ref) on this box's host cores (rank 0, N = 1 only)
+  precision_evidence, configs (the side workloads, each in a process of its own)
+The --no-* options below leave single parts of --full out.
 """
 import argparse
 import json
@@ -57,6 +66,11 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the extra passes (hot_path, in_flight, split3, fp32), the roofline / kernel timing, "
+                         "the precision probe, the CPU baseline and the side configs.  Off: the headline steps alone")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="write what the last timed step returned as DIR/<name>.npy (rank 0; float32 / float64, <= 64 MB)")
     ap.add_argument("--workload", default=os.environ.get("DF3D_WORKLOAD", "cp_fusion"),
                     choices=["cp_fusion", "cp_lidar", "tf_fusion", "vr_fusion", "protocol"],
                     help="cp_fusion = BASELINE configs[1] (default, the headline); cp_lidar = configs[0] shape; tf_fusion = "
@@ -96,7 +110,10 @@ def parse():
                     help="skip the ~10-step passes over BASELINE configs[0] / [2] / [4] after the headline (N = 1 only)")
     ap.add_argument("--cpu-sweeps", type=int, default=20,
                     help="timed sweeps of the CPU baseline at the fastest thread setting (SURVEY 8(d): 20 after 3 untimed ones)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 # ------------------------------------------------------------------------------------------------ workloads
@@ -746,8 +763,59 @@ def note(msg):
         print("bench.py: " + msg, file=sys.stderr, flush=True)
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def output_arrays(out, name=""):
+    """(name, numpy array) for every tensor / array / number in a step's return value: dicts, lists and tuples are walked
+    (names joined with '.'), other objects through their attributes (the sparse tensors of the Voxel-RCNN tree)."""
+    sub = (lambda k: "%s.%s" % (name, k) if name else str(k))
+    if isinstance(out, torch.Tensor):
+        yield name or "out", (out.detach().float() if out.dtype == torch.bfloat16 else out.detach()).cpu().numpy()
+    elif isinstance(out, np.ndarray):
+        yield name or "out", out
+    elif isinstance(out, (bool, int, float, np.number)):
+        yield name or "out", np.asarray(out)
+    elif isinstance(out, dict):
+        for k in sorted(out, key=str):
+            yield from output_arrays(out[k], sub(k))
+    elif isinstance(out, (list, tuple)):
+        for k, v in enumerate(out):
+            yield from output_arrays(v, sub(k))
+    elif hasattr(out, "__dict__"):
+        for k, v in sorted(vars(out).items()):
+            if isinstance(v, (torch.Tensor, np.ndarray)):
+                yield from output_arrays(v, sub(k))
+
+
+def dump_outputs(out, path):
+    """What the last timed step returned, as path/<name>.npy: floating arrays in float32 (float64 stays float64), integer
+    and boolean arrays in float64.  Above DUMP_LIMIT_BYTES in all, every array over 1 MB is cut to the same share of its
+    elements, taken (flattened, in index order) at positions drawn by a RandomState seeded from its name: the same sample
+    in every run with the same arguments."""
+    import zlib
+    arrays = []
+    for name, a in output_arrays(out):
+        a = np.asarray(a)
+        a = a.astype(np.float64 if a.dtype == np.float64 or not np.issubdtype(a.dtype, np.floating) else np.float32)
+        arrays.append((name, a))
+    big = sum(a.nbytes for _, a in arrays if a.nbytes > 1 << 20)
+    small = sum(a.nbytes for _, a in arrays) - big
+    share = min(1.0, (DUMP_LIMIT_BYTES * 0.95 - small) / max(big, 1))
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays:
+        if share < 1.0 and a.nbytes > 1 << 20:
+            rs = np.random.RandomState(zlib.crc32(name.encode()))
+            a = a.reshape(-1)[np.unique(rs.randint(0, a.size, max(1, int(a.size * share))))]
+        np.save(os.path.join(path, "".join(c if c.isalnum() or c in "._-" else "_" for c in name) + ".npy"), a)
+
+
 def main():
     args = parse()
+    if not args.full:
+        # a plain run is the headline alone: the extra passes, kernel timing / roofline, precision probe, CPU baseline and
+        # side configs all belong to --full
+        args.no_cpu_baseline = args.no_kernel_timing = args.no_extra_passes = True
     from dualfusion import dist as D
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(D.launch_ranks(args.gpus, os.path.abspath(__file__), sys.argv[1:]))
@@ -811,16 +879,18 @@ def main():
     # Roofline: HIP events around EVERY conv launch cost the timed region ~6 % (30 launches per frame).  The roofline
     # needs the dominant kernel only: one untimed probe step with all events finds it (and yields the per-kernel
     # table), the timed region then records events around its launches alone.
+    # Step W runs untimed in every mode (with kernel timing it is that probe step): the timed steps are W+1 .. W+K, the same
+    # frames with and without --full.
     timer = probe = meta_timer = None
-    first_timed = args.warmup
+    first_timed = args.warmup + 1
     kernel_timing = not (args.no_kernel_timing or protocol)
     if kernel_timing:
         probe = ops.KernelTimer()
         probe.start()
-        wl.step(args.warmup, stage)            # the next step of the sequence (its head was prefetched by the last warm-up step)
+    wl.step(args.warmup, stage)                # the next step of the sequence (its head was prefetched by the last warm-up step)
+    if kernel_timing:
         torch.cuda.synchronize()
         probe.stop()
-        first_timed = args.warmup + 1
         tot = {}
         for r in probe.records:
             if r["kvol"] == 27:                  # the 3-D sparse convolutions (the neck / head reuse the kernel with K = 9)
@@ -836,6 +906,9 @@ def main():
         timer.stop()
     elapsed = D.max_over_ranks(elapsed, dev)
     wl.check(out, stage)
+    if args.dump_outputs and rank == 0:
+        # before any other pass: later steps may reuse the buffers the last timed step returned
+        dump_outputs(out, args.dump_outputs)
     extra = {}
     if stage == "train":
         assert args.workload in ("cp_lidar", "cp_fusion", "tf_fusion"), "--stage train: the CenterPoint / TransFusion detectors"

@@ -15,12 +15,32 @@ def pytest_configure(config):
     config.addinivalue_line("markers", "gpu: needs a real MI355X (run with -m gpu on the GPU box)")
 
 
+class _Joined(dict):
+    """The arrays of a fixture stored in parts (name.npz, name.1.npz, ...: tests/golden/make_golden.py `save`)."""
+
+    @property
+    def files(self):
+        return list(self)
+
+
 @pytest.fixture(scope="session")
 def golden():
     import numpy as np
 
     def load(name):
-        return np.load(os.path.join(GOLDEN, name), allow_pickle=False)
+        path = os.path.join(GOLDEN, name)
+        parts, i = [path], 1
+        while os.path.exists("%s.%d.npz" % (path[:-len(".npz")], i)):
+            parts.append("%s.%d.npz" % (path[:-len(".npz")], i))
+            i += 1
+        if len(parts) == 1:
+            return np.load(path, allow_pickle=False)
+        blocks = {}
+        for p in parts:
+            with np.load(p, allow_pickle=False) as z:
+                for k in z.files:
+                    blocks.setdefault(k, []).append(z[k])
+        return _Joined((k, v[0] if len(v) == 1 else np.concatenate(v)) for k, v in blocks.items())
 
     return load
 

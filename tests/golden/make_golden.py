@@ -35,10 +35,35 @@ from oracle import ref  # noqa: E402
 from dualfusion import synth  # noqa: E402
 
 
+PART_BYTES = 1000 * 1000         # a committed file stays under 1 MiB
+
+
 def save(name, **arrs):
-    path = os.path.join(HERE, name)
-    np.savez_compressed(path, **arrs)
-    print("wrote %s (%.1f KB)" % (name, os.path.getsize(path) / 1024))
+    """name.npz; a fixture that does not fit in PART_BYTES is written as name.npz, name.1.npz, ... instead: every array over
+    64 KB split along its first axis into that many row blocks, the others whole in name.npz (tests/conftest.py `golden`
+    joins the parts)."""
+    import glob
+    stem = os.path.join(HERE, name[:-len(".npz")])
+    for stale in glob.glob(stem + ".[0-9]*.npz"):
+        os.remove(stale)
+    n = 1
+    while True:
+        parts = [{} for _ in range(n)]
+        for k, a in arrs.items():
+            a = np.asarray(a)
+            blocks = np.array_split(a, n) if n > 1 and a.nbytes > 64 * 1024 and len(a) >= n else [a]
+            for part, block in zip(parts, blocks):
+                part[k] = block
+        paths = [stem + ".npz"] + ["%s.%d.npz" % (stem, i) for i in range(1, n)]
+        for path, part in zip(paths, parts):
+            np.savez_compressed(path, **part)
+        if max(os.path.getsize(p) for p in paths) <= PART_BYTES:
+            break
+        if n == 16:
+            raise ValueError("%s: the arrays under 64 KB alone exceed %d bytes" % (name, PART_BYTES))
+        n += 1
+    for path in paths:
+        print("wrote %s (%.1f KB)" % (os.path.basename(path), os.path.getsize(path) / 1024))
 
 
 # ------------------------------------------------------------------ voxelize
@@ -243,8 +268,10 @@ def gen_actr(actr):
 
 
 # ------------------------------------------------------------------ CenterPoint fusion adapter (a7-a9)
+# the rig is turned off the axes: with axis-aligned cameras the voxel lattice projects exactly onto pixel boundaries, and the
+# reference's truncations there follow the last bit of the host BLAS's float32 products (synth.nusc_cameras)
 FUS = dict(batch=2, pc_range=[-9.6, -9.6, -5.0, 9.6, 9.6, 3.0], voxel_size=[0.075, 0.075, 0.2],
-           raw_hw=(240, 320), image_scale=2.0 / 3.0, img_hw=(160, 213), feat_hw=(40, 54), focal=250.0,
+           raw_hw=(240, 320), image_scale=2.0 / 3.0, img_hw=(160, 213), feat_hw=(40, 54), focal=250.0, yaw_offset_deg=7.3,
            depth_thres={'CAM_FRONT': 1, 'CAM_FRONT_LEFT': 0, 'CAM_FRONT_RIGHT': 0, 'CAM_BACK': 0.5,
                         'CAM_BACK_LEFT': 0, 'CAM_BACK_RIGHT': 0})
 FUS_IFAT = dict(fusion_method='Basicgate_patch_iv_multivoxel', img_num_channel=256, pts_num_channel=128,
@@ -276,7 +303,7 @@ def fusion_voxel_sets():
 def fusion_inputs():
     sets = fusion_voxel_sets()
     feats = [detgen.randn("fus_feat%d" % i, (len(s), c)) for i, (s, c) in enumerate(zip(sets, [32, 64, 128]))]
-    cams = synth.nusc_cameras(image_hw=FUS["raw_hw"], focal=FUS["focal"])
+    cams = synth.nusc_cameras(image_hw=FUS["raw_hw"], focal=FUS["focal"], yaw_offset_deg=FUS["yaw_offset_deg"])
     B = FUS["batch"]
     img = {name.lower(): detgen.randn("fus_img_" + name, (B, 256) + FUS["feat_hw"]) for name in synth.NUSC_CAMS}
     return sets, feats, cams, img

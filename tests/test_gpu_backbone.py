@@ -120,7 +120,7 @@ def test_centerpoint_fusion_adapter_vs_reference_golden(golden):
     mod.load_state_dict({k: torch.from_numpy(v) for k, v in sd.items()})
     mod = mod.to(dev)
     B = FUS["batch"]
-    cams = synth.nusc_cameras(image_hw=FUS["raw_hw"], focal=FUS["focal"])
+    cams = synth.nusc_cameras(image_hw=FUS["raw_hw"], focal=FUS["focal"], yaw_offset_deg=FUS["yaw_offset_deg"])
     H, W = FUS["img_hw"]
     batch_dict = {'image_shape': {}, 'img_feat': {'layer1_ori_feat2d': {}}, 'calib': {}}
     for n in synth.NUSC_CAMS:
@@ -186,7 +186,7 @@ def test_centerpoint_fusion_adapter_training_path(golden):
         if isinstance(m, torch.nn.Dropout):
             m.p = 0.0
     B = FUS["batch"]
-    cams = synth.nusc_cameras(image_hw=FUS["raw_hw"], focal=FUS["focal"])
+    cams = synth.nusc_cameras(image_hw=FUS["raw_hw"], focal=FUS["focal"], yaw_offset_deg=FUS["yaw_offset_deg"])
     H, W = FUS["img_hw"]
     batch_dict = {'image_shape': {}, 'img_feat': {'layer1_ori_feat2d': {}}, 'calib': {}}
     for n in synth.NUSC_CAMS:

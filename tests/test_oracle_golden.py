@@ -184,7 +184,7 @@ def test_centerpoint_fusion_oracle_vs_reference_golden(golden):
     sd = detgen.det_state_dict(shapes)
     sets = [g["coords2"].astype(np.int32), g["coords3"].astype(np.int32), g["coords4"].astype(np.int32)]
     feats = [detgen.randn("fus_feat%d" % i, (len(s), c)) for i, (s, c) in enumerate(zip(sets, [32, 64, 128]))]
-    cams = synth.nusc_cameras(image_hw=FUS["raw_hw"], focal=FUS["focal"])
+    cams = synth.nusc_cameras(image_hw=FUS["raw_hw"], focal=FUS["focal"], yaw_offset_deg=FUS["yaw_offset_deg"])
     B = FUS["batch"]
     img = {n: detgen.randn("fus_img_" + n, (B, 256) + tuple(FUS["feat_hw"])) for n in synth.NUSC_CAMS}
     calib = {n: (np.stack([cams[n][0]] * B), np.stack([cams[n][1]] * B)) for n in synth.NUSC_CAMS}

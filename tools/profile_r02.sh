@@ -14,5 +14,5 @@ rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $OUT/calib_fetc
 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $OUT/calib_write -o write -- python $R/tools/ubench/pmc_calib.py > $OUT/calib_write.log 2>&1
 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_VALU_MFMA_MOPS_BF16 GRBM_GUI_ACTIVE --kernel-trace --output-format csv -d $OUT/sq -o sq -- $BENCH --no-kernel-timing > $OUT/bench_sq.log 2>&1 || true
 cd $R
-python bench.py --no-cpu-baseline > $OUT/bench.json 2> $OUT/bench.err || true
+python bench.py --full --no-cpu-baseline > $OUT/bench.json 2> $OUT/bench.err || true
 find $OUT -name "*.csv" | head -30

@@ -16,7 +16,7 @@ rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $OUT/calib_writ
 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_VALU_MFMA_MOPS_BF16 GRBM_GUI_ACTIVE --kernel-trace --output-format csv -d $OUT/sq -o sq -- $BENCH --no-kernel-timing > $OUT/bench_sq.log 2>&1 || true
 rocprofv3 --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_VMEM_RD SQ_INSTS_LDS SQ_INSTS_SALU SQ_WAIT_INST_LDS SQ_INST_CYCLES_VMEM --kernel-trace --output-format csv -d $OUT/sq2 -o sq2 -- $BENCH --no-kernel-timing > $OUT/bench_sq2.log 2>&1 || true
 cd $R
-python bench.py --no-cpu-baseline --no-side-configs > $OUT/bench.json 2> $OUT/bench.err || true
+python bench.py --full --no-cpu-baseline --no-side-configs > $OUT/bench.json 2> $OUT/bench.err || true
 # keep what is merged back small: the counter CSVs of the conv / rulebook / fusion kernels only
 for d in fetch write sq sq2 calib_fetch calib_write; do
   f=$(find $OUT/$d -name "*counter_collection.csv" | head -1)

@@ -5,13 +5,13 @@ python __graft_entry__.py build
 python -m pytest tests -q -m "not gpu"
 python -m pytest tests -q -m gpu
 python __graft_entry__.py smoke
-python bench.py                                   # configs[1]: detector step + hot_path / fp32 passes + roofline + cpu_baseline
-python bench.py --gpus 2 --no-cpu-baseline        # spawns its own ranks (one per GPU, RCCL)
-python bench.py --inflight 2 --no-cpu-baseline    # + the two-frames-in-flight pass
-python bench.py --workload cp_lidar --stage train --no-cpu-baseline      # training step of the LiDAR detector
-python bench.py --workload cp_fusion --stage train --no-cpu-baseline     # ... with the camera fusion in the graph
-python bench.py --workload tf_fusion --no-cpu-baseline                   # configs[2]: TransFusion-L + 3D-DF, bs = 4, bf16
-python bench.py --workload vr_fusion --no-cpu-baseline                   # configs[4]: Voxel-RCNN + 3D-DF, KITTI, bs = 8
+python bench.py --full                            # configs[1]: detector step + hot_path / fp32 passes + roofline + cpu_baseline
+python bench.py --full --gpus 2 --no-cpu-baseline        # spawns its own ranks (one per GPU, RCCL)
+python bench.py --full --inflight 2 --no-cpu-baseline    # + the two-frames-in-flight pass
+python bench.py --full --workload cp_lidar --stage train --no-cpu-baseline      # training step of the LiDAR detector
+python bench.py --full --workload cp_fusion --stage train --no-cpu-baseline     # ... with the camera fusion in the graph
+python bench.py --full --workload tf_fusion --no-cpu-baseline                   # configs[2]: TransFusion-L + 3D-DF, bs = 4, bf16
+python bench.py --full --workload vr_fusion --no-cpu-baseline                   # configs[4]: Voxel-RCNN + 3D-DF, KITTI, bs = 8
 bash tools/profile_r02.sh && python tools/make_profiles.py gpurun_out/prof_r02 r02   # profiles/r02_* (trace, PMC, calibration)
 python tools/bench_trees.py neck 20               # BEV neck (RPN) on the row kernels vs torch/MIOpen
 python tools/bench_trees.py head 20               # CenterHead forward + predict; sweep -> boxes
