@@ -49,7 +49,9 @@ class _LinearBf16Function(torch.autograd.Function):
     result stays bfloat16 for the next layer of the feed-forward branch), fp32 accumulation in the library's products.  The
     weight gradient grad^T x contracts over the ROWS (131 k at the TransFusion shape): as ONE product the library runs it at a
     few per cent of its rate (442 us for 128 x 1024 outputs), so it is taken per sample -- a batched product over the leading
-    dimension (or over 16 row chunks) -- and the partial results are summed in fp32."""
+    dimension (or over 16 row chunks) -- and the partial results are summed in fp32.  The batched product writes its partials
+    in fp32 (`out_dtype`): a bfloat16 result would round every partial -- and, as one product, the whole weight gradient -- to
+    8 significant bits before the sum (2e-3 of scale at [6, 3001] rows: tests/test_gpu_bf16train.py)."""
 
     @staticmethod
     def forward(ctx, x, weight, bias):
@@ -71,14 +73,15 @@ class _LinearBf16Function(torch.autograd.Function):
                 g2, x2 = g3.reshape(-1, g3.shape[-1]), x3.reshape(-1, x3.shape[-1])
                 parts = 16 if g2.shape[0] % 16 == 0 and g2.shape[0] >= 16 * 1024 else 1
                 g3, x3 = g2.view(parts, -1, g2.shape[1]), x2.view(parts, -1, x2.shape[1])
-            gw = torch.bmm(g3.transpose(1, 2), x3).sum(0, dtype=torch.float32)
+            gw = torch.bmm(g3.transpose(1, 2), x3, out_dtype=torch.float32).sum(0)
         if ctx.has_bias and ctx.needs_input_grad[2]:
             gb = g16.reshape(-1, g16.shape[-1]).sum(0, dtype=torch.float32)
         return gx, gw, gb
 
 
 def linear_bf16(x, weight, bias=None):
-    """x W^T + b with bfloat16 operands and a bfloat16 result, differentiable (fp32 parameter gradients)."""
+    """x W^T + b with bfloat16 operands and a bfloat16 result, differentiable (fp32 parameter gradients).  CUDA tensors only: the
+    weight gradient's fp32-output batched product (`torch.bmm(..., out_dtype=)`) has no CPU kernel."""
     return _LinearBf16Function.apply(x, weight, bias)
 
 

@@ -2048,6 +2048,11 @@ def add_layernorm(x, y, weight, bias, eps, want_split=False):
     return out
 
 
+def _dropout_threshold(p):
+    """The dropout kernels' threshold on the 24-bit hash (dropout_threshold, csrc/actr.hip) for p as the fp32 they receive."""
+    return int(ctypes.c_float(p).value * 16777216.0)
+
+
 def _dropout_seed(device):
     """A 63-bit seed per call from the device generator's (seed, Philox offset), which the call advances like a dropout kernel
     would: the masks of a run repeat under torch.manual_seed, host side only (no launch)."""
@@ -2113,7 +2118,8 @@ class _DropoutAddLayerNorm(torch.autograd.Function):
         grad = grad.contiguous()
         C = xhat.shape[-1]
         dx = torch.empty_like(xhat)
-        dy = torch.empty_like(xhat) if ctx.p > 0 else None
+        # the kernel drops nothing -- and writes no d y -- where its threshold rounds to 0 (0 < p < 2^-24): d y = d x there
+        dy = torch.empty_like(xhat) if _dropout_threshold(ctx.p) else None
         dwb = torch.zeros((2, C), dtype=torch.float32, device=xhat.device)
         rc = _lib.load().df3d_dropout_add_layernorm_backward(_ptr(grad), _ptr(xhat), _ptr(rstd), _ptr(weight), ctx.p, ctx.seed,
                                                              xhat.numel() // C, C, _ptr(dx), _ptr(dy), _ptr(dwb[0]),

@@ -1921,7 +1921,7 @@ def test_relu_dropout_in_place_forward_and_maskless_backward():
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("rows,C", [(5003, 128), (777, 64), (300, 256), (1030, 32)])
+@pytest.mark.parametrize("rows,C", [(5003, 128), (777, 64), (300, 256), (1030, 32), (333, 4), (97, 1024), (1, 128)])
 def test_dropout_add_layernorm_forward_and_backward(rows, C):
     """df3d_dropout_add_layernorm: norm(x + dropout(y)) of the encoder layers' residual steps (actr_transformer.py:311-312,
     389-396, 416-417) as one kernel each way.  p = 0 against nn.LayerNorm in float64 (output, d x = d y, d gamma, d beta);
