@@ -608,7 +608,7 @@ __global__ __launch_bounds__(256) void dropout_add_layernorm_kernel(const float 
     v[k] = (f32x4){0.f, 0.f, 0.f, 0.f};
     if (live && c4 < nv) {
       f32x4 a = ((const f32x4 *)(x + row * C))[c4];
-      f32x4 b = ((const f32x4 *)(y + row * C))[c4];
+      f32x4 b = y ? ((const f32x4 *)(y + row * C))[c4] : (f32x4){0.f, 0.f, 0.f, 0.f};   // (y == NULL: LayerNorm(x) alone)
       if (thr) {
         const unsigned long long i0 = (unsigned long long)row * C + c4 * 4;
 #pragma unroll
@@ -722,7 +722,7 @@ extern "C" int df3d_dropout_add_layernorm(const float *x, const float *y, const 
   DF3D_CHECK_ARG(rows >= 0 && C > 0 && C % 4 == 0 && C <= 1024, "dropout_add_layernorm: C must be a multiple of 4 and <= 1024 (got %d)", C);
   DF3D_CHECK_ARG(p >= 0.f && p < 1.f, "dropout_add_layernorm: p must be in [0, 1) (got %g)", (double)p);
   if (rows == 0) return DF3D_OK;
-  DF3D_CHECK_ARG(x && y && gamma && beta && out && xhat && rstd, "dropout_add_layernorm: null argument");
+  DF3D_CHECK_ARG(x && gamma && beta && out && xhat && rstd, "dropout_add_layernorm: null argument");   // (y may be NULL)
   const unsigned thr = dropout_threshold(p), s0 = (unsigned)seed, s1 = (unsigned)(seed >> 32);
   const float sc = dropout_scale(thr);
 #define DF3D_DAL(LPR, RPWV)                                                                                                   \

@@ -515,6 +515,169 @@ extern "C" int df3d_group_attention_split(const float *qkv, int tokens, int grou
   return group_attention_impl(qkv, tokens, groups, heads, head_dim, out, (unsigned *)out_split, stream_);
 }
 
+// Backward of group_attention_kernel (training of the LocalTransformer): grad_out [L * G][C] -> grad_qkv [L * G][3 * C], the
+// probabilities recomputed from qkv (the forward stores none).  A workgroup owns a group, thread = (token, head) as in the
+// forward, two phases over two LDS tiles of L rows:
+//   A  thread = query i: K | V of the group in LDS, q_i (scaled) and dO_i in registers.  First walk over the keys: online
+//      softmax -> m_i, 1 / l_i and Delta_i = dO_i . O_i; second walk: p_ij, dS_ij = p_ij (dO_i . v_j - Delta_i),
+//      dq_i += dS_ij k_j (a reduction over keys: stays in the thread).
+//   B  thread = key j: it takes k_j, v_j into registers, then the tiles are overwritten with the scaled Q | dO rows and the three
+//      row statistics; walk over the queries: the same p_ij, dS_ij, dv_j += p_ij dO_i, dk_j += dS_ij q_i (the reductions over
+//      queries: stay in the thread too).  No atomics: the result does not depend on the schedule.
+// Every LDS read inside the walks is one row slice per head: the lanes of a head broadcast, heads sit 64 B apart.  The reads and
+// writes of a thread's OWN row (lane stride = one row) would be 16-way conflicts on 256-byte rows (C = 64): rows are padded by
+// one 16-byte access (stride C + 4 floats), which spreads 16 lanes over the 64 banks.
+template <int D>
+__global__ void group_attention_backward_kernel(const float *__restrict__ qkv, const float *__restrict__ grad_out, int L, int G,
+                                                int H, float scale, float *__restrict__ grad_qkv) {
+  extern __shared__ __align__(16) float gab_smem[];
+  typedef float f4 __attribute__((ext_vector_type(4)));
+  const int C = H * D, CP = C + 4, g = blockIdx.x, tid = threadIdx.x;
+  float *sa = gab_smem, *sb = gab_smem + (size_t)L * CP;          // K then Q (scaled) | V then dO
+  float *sm = sb + (size_t)L * CP, *sil = sm + L * H, *sdl = sil + L * H;   // m, 1 / l, Delta per (head, token)
+  const int c4n = C / 4;
+  for (int it = tid; it < L * c4n * 2; it += blockDim.x) {
+    const int kv = it / (L * c4n), r = it - kv * (L * c4n);
+    const int t = r / c4n, c4 = r - t * c4n;
+    const f4 v = *(const f4 *)(qkv + ((size_t)t * G + g) * 3 * C + (1 + kv) * C + c4 * 4);
+    *(f4 *)((kv ? sb : sa) + t * CP + c4 * 4) = v;
+  }
+  __syncthreads();
+  const bool live = tid < L * H;                 // (the padding lanes of the last wave only keep the barriers)
+  const int h = live ? tid / L : 0, t = live ? tid - h * L : 0;
+  const size_t row = (size_t)t * G + g;
+  float q[D], go[D], acc[D];
+  float m = -INFINITY, l = 0.f, inv = 0.f, delta = 0.f;
+  if (live) {
+    const float *qp = qkv + row * 3 * C + h * D, *gp = grad_out + row * C + h * D;
+#pragma unroll
+    for (int e = 0; e < D; e += 4) {
+      const f4 v = *(const f4 *)(qp + e), w = *(const f4 *)(gp + e);
+      q[e] = v[0] * scale, q[e + 1] = v[1] * scale, q[e + 2] = v[2] * scale, q[e + 3] = v[3] * scale;
+      go[e] = w[0], go[e + 1] = w[1], go[e + 2] = w[2], go[e + 3] = w[3];
+    }
+#pragma unroll
+    for (int e = 0; e < D; ++e) acc[e] = 0.f;
+    for (int j = 0; j < L; ++j) {                // the forward's walk: m, l and the unnormalised output row
+      const float *kp = sa + j * CP + h * D, *vp = sb + j * CP + h * D;
+      float s = 0.f;
+#pragma unroll
+      for (int e = 0; e < D; e += 4) {
+        const f4 k4 = *(const f4 *)(kp + e);
+        s = fmaf(q[e], k4[0], s), s = fmaf(q[e + 1], k4[1], s), s = fmaf(q[e + 2], k4[2], s), s = fmaf(q[e + 3], k4[3], s);
+      }
+      const float mn = fmaxf(m, s);
+      const float a = __expf(m - mn), p = __expf(s - mn);
+      l = l * a + p;
+#pragma unroll
+      for (int e = 0; e < D; e += 4) {
+        const f4 v4 = *(const f4 *)(vp + e);
+        acc[e] = fmaf(p, v4[0], acc[e] * a), acc[e + 1] = fmaf(p, v4[1], acc[e + 1] * a);
+        acc[e + 2] = fmaf(p, v4[2], acc[e + 2] * a), acc[e + 3] = fmaf(p, v4[3], acc[e + 3] * a);
+      }
+      m = mn;
+    }
+    inv = 1.f / l;
+#pragma unroll
+    for (int e = 0; e < D; ++e) delta = fmaf(go[e], acc[e], delta);
+    delta *= inv;
+#pragma unroll
+    for (int e = 0; e < D; ++e) acc[e] = 0.f;    // now d q_i (of the scaled scores)
+    for (int j = 0; j < L; ++j) {
+      const float *kp = sa + j * CP + h * D, *vp = sb + j * CP + h * D;
+      f4 k4[D / 4];
+      float s = 0.f, dp = 0.f;
+#pragma unroll
+      for (int e = 0; e < D; e += 4) {
+        k4[e / 4] = *(const f4 *)(kp + e);
+        const f4 k = k4[e / 4], v4 = *(const f4 *)(vp + e);
+        s = fmaf(q[e], k[0], s), s = fmaf(q[e + 1], k[1], s), s = fmaf(q[e + 2], k[2], s), s = fmaf(q[e + 3], k[3], s);
+        dp = fmaf(go[e], v4[0], dp), dp = fmaf(go[e + 1], v4[1], dp), dp = fmaf(go[e + 2], v4[2], dp), dp = fmaf(go[e + 3], v4[3], dp);
+      }
+      const float ds = __expf(s - m) * inv * (dp - delta);
+#pragma unroll
+      for (int e = 0; e < D; e += 4) {
+        const f4 k = k4[e / 4];
+        acc[e] = fmaf(ds, k[0], acc[e]), acc[e + 1] = fmaf(ds, k[1], acc[e + 1]);
+        acc[e + 2] = fmaf(ds, k[2], acc[e + 2]), acc[e + 3] = fmaf(ds, k[3], acc[e + 3]);
+      }
+    }
+    float *dq = grad_qkv + row * 3 * C + h * D;
+#pragma unroll
+    for (int e = 0; e < D; e += 4)
+      *(f4 *)(dq + e) = (f4){acc[e] * scale, acc[e + 1] * scale, acc[e + 2] * scale, acc[e + 3] * scale};
+  }
+  // phase B: this thread's key / value row into registers, then Q (scaled) | dO and the row statistics take the tiles' place
+  float kr[D], vr[D], dk[D], dv[D];
+  if (live) {
+#pragma unroll
+    for (int e = 0; e < D; e += 4) {
+      const f4 k4 = *(const f4 *)(sa + t * CP + h * D + e), v4 = *(const f4 *)(sb + t * CP + h * D + e);
+      kr[e] = k4[0], kr[e + 1] = k4[1], kr[e + 2] = k4[2], kr[e + 3] = k4[3];
+      vr[e] = v4[0], vr[e + 1] = v4[1], vr[e + 2] = v4[2], vr[e + 3] = v4[3];
+    }
+  }
+  __syncthreads();
+  if (live) {
+#pragma unroll
+    for (int e = 0; e < D; e += 4) {
+      *(f4 *)(sa + t * CP + h * D + e) = (f4){q[e], q[e + 1], q[e + 2], q[e + 3]};
+      *(f4 *)(sb + t * CP + h * D + e) = (f4){go[e], go[e + 1], go[e + 2], go[e + 3]};
+    }
+    sm[tid] = m, sil[tid] = inv, sdl[tid] = delta;
+  }
+  __syncthreads();
+  if (!live) return;
+#pragma unroll
+  for (int e = 0; e < D; ++e) dk[e] = 0.f, dv[e] = 0.f;
+  for (int i = 0; i < L; ++i) {
+    const float *qp = sa + i * CP + h * D, *gp = sb + i * CP + h * D;
+    f4 q4[D / 4], g4[D / 4];
+    float s = 0.f, dp = 0.f;
+#pragma unroll
+    for (int e = 0; e < D; e += 4) {
+      q4[e / 4] = *(const f4 *)(qp + e), g4[e / 4] = *(const f4 *)(gp + e);
+      const f4 a = q4[e / 4], b = g4[e / 4];
+      s = fmaf(a[0], kr[e], s), s = fmaf(a[1], kr[e + 1], s), s = fmaf(a[2], kr[e + 2], s), s = fmaf(a[3], kr[e + 3], s);
+      dp = fmaf(b[0], vr[e], dp), dp = fmaf(b[1], vr[e + 1], dp), dp = fmaf(b[2], vr[e + 2], dp), dp = fmaf(b[3], vr[e + 3], dp);
+    }
+    const float p = __expf(s - sm[h * L + i]) * sil[h * L + i];
+    const float ds = p * (dp - sdl[h * L + i]);
+#pragma unroll
+    for (int e = 0; e < D; e += 4) {
+      const f4 a = q4[e / 4], b = g4[e / 4];
+      dk[e] = fmaf(ds, a[0], dk[e]), dk[e + 1] = fmaf(ds, a[1], dk[e + 1]);
+      dk[e + 2] = fmaf(ds, a[2], dk[e + 2]), dk[e + 3] = fmaf(ds, a[3], dk[e + 3]);
+      dv[e] = fmaf(p, b[0], dv[e]), dv[e + 1] = fmaf(p, b[1], dv[e + 1]);
+      dv[e + 2] = fmaf(p, b[2], dv[e + 2]), dv[e + 3] = fmaf(p, b[3], dv[e + 3]);
+    }
+  }
+  float *dkp = grad_qkv + row * 3 * C + C + h * D, *dvp = dkp + C;
+#pragma unroll
+  for (int e = 0; e < D; e += 4) {
+    *(f4 *)(dkp + e) = (f4){dk[e], dk[e + 1], dk[e + 2], dk[e + 3]};
+    *(f4 *)(dvp + e) = (f4){dv[e], dv[e + 1], dv[e + 2], dv[e + 3]};
+  }
+}
+
+extern "C" int df3d_group_attention_backward(const float *qkv, const float *grad_out, int tokens, int groups, int heads,
+                                             int head_dim, float *grad_qkv, void *stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  DF3D_CHECK_ARG(tokens >= 1 && groups >= 0 && heads >= 1 && head_dim == 16,
+                 "group_attention_backward: heads of 16 channels only (got %d)", head_dim);
+  const int C = heads * head_dim;
+  const size_t lds = ((size_t)2 * tokens * (C + 4) + (size_t)3 * tokens * heads) * sizeof(float);
+  DF3D_CHECK_ARG(tokens * heads <= 1024 && lds <= 64 * 1024,
+                 "group_attention_backward: %d tokens x %d heads does not fit a workgroup", tokens, heads);
+  if (groups == 0) return DF3D_OK;               // (empty tensors carry null pointers)
+  DF3D_CHECK_ARG(qkv && grad_out && grad_qkv, "group_attention_backward: null argument");
+  const int threads = cdiv(tokens * heads, 64) * 64;
+  hipLaunchKernelGGL(group_attention_backward_kernel<16>, dim3(groups), dim3(threads), lds, stream, qkv, grad_out, tokens, groups,
+                     heads, 1.f / sqrtf((float)head_dim), grad_qkv);
+  DF3D_LAUNCH_CHECK();
+  return DF3D_OK;
+}
+
 // Grouped features + positional MLP of the LocalTransformer in one pass (pointformer.py:232-262: x = group(features) +
 // pe(grouped xyz), pe = Conv1x1(3 -> C/2) + BN + ReLU + Conv1x1(C/2 -> C); BN folded by the caller):
 //   out[r][:] = feat[sel[r]][:] + W1 relu(W0 xyz[r] + b0) + b1

@@ -2110,6 +2110,7 @@ class _DropoutAddLayerNorm(torch.autograd.Function):
         _lib.check(rc, "df3d_dropout_add_layernorm")
         ctx.save_for_backward(xhat, rstd, weight)
         ctx.p, ctx.seed = float(p), int(seed)
+        ctx.has_y = y is not None                      # (None: LayerNorm(x) alone, `layernorm_rows`)
         return out
 
     @staticmethod
@@ -2119,13 +2120,13 @@ class _DropoutAddLayerNorm(torch.autograd.Function):
         C = xhat.shape[-1]
         dx = torch.empty_like(xhat)
         # the kernel drops nothing -- and writes no d y -- where its threshold rounds to 0 (0 < p < 2^-24): d y = d x there
-        dy = torch.empty_like(xhat) if _dropout_threshold(ctx.p) else None
+        dy = torch.empty_like(xhat) if _dropout_threshold(ctx.p) and ctx.has_y else None
         dwb = torch.zeros((2, C), dtype=torch.float32, device=xhat.device)
         rc = _lib.load().df3d_dropout_add_layernorm_backward(_ptr(grad), _ptr(xhat), _ptr(rstd), _ptr(weight), ctx.p, ctx.seed,
                                                              xhat.numel() // C, C, _ptr(dx), _ptr(dy), _ptr(dwb[0]),
                                                              _ptr(dwb[1]), _stream())
         _lib.check(rc, "df3d_dropout_add_layernorm_backward")
-        return dx, (dy if dy is not None else dx), dwb[0], dwb[1], None, None, None
+        return dx, ((dy if dy is not None else dx) if ctx.has_y else None), dwb[0], dwb[1], None, None, None
 
 
 def dropout_add_layernorm(x, y, norm, drop):
@@ -2180,7 +2181,7 @@ def ball_query(min_radius, max_radius, nsample, xyz, new_xyz):
     return idx
 
 
-def group_points(features, idx):
+def _group_points(features, idx):
     lib = _lib.load()
     _chk(features, torch.float32, "features")
     _chk(idx, torch.int32, "idx")
@@ -2192,7 +2193,7 @@ def group_points(features, idx):
     return out
 
 
-def gather_points(features, idx):
+def _gather_points(features, idx):
     lib = _lib.load()
     _chk(features, torch.float32, "features")
     _chk(idx, torch.int32, "idx")
@@ -2202,6 +2203,43 @@ def gather_points(features, idx):
     rc = lib.df3d_gather_points(_ptr(features), _ptr(idx), B, C, N, npoint, _ptr(out), _stream())
     _lib.check(rc, "df3d_gather_points")
     return out
+
+
+class _GroupPoints(torch.autograd.Function):
+    """GroupingOperation (CP/det3d/ops/group_points/group_points.py:176-206) / GatherPoints (gather_points.py:29-49): the
+    gradient is scatter-added onto the source points (df3d_group_points_grad: fp32 atomics); the indices get none."""
+
+    @staticmethod
+    def forward(ctx, features, idx):
+        ctx.save_for_backward(idx)
+        ctx.n = features.shape[2]
+        return _group_points(features, idx) if idx.dim() == 3 else _gather_points(features, idx)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad):
+        (idx,) = ctx.saved_tensors
+        grad = _chk(grad.contiguous(), torch.float32, "grad")
+        B, C = grad.shape[:2]
+        out = torch.zeros((B, C, ctx.n), dtype=torch.float32, device=grad.device)
+        nsample = idx.shape[2] if idx.dim() == 3 else 1
+        rc = _lib.load().df3d_group_points_grad(_ptr(grad), _ptr(idx), B, C, ctx.n, idx.shape[1], nsample, _ptr(out), _stream())
+        _lib.check(rc, "df3d_group_points_grad")
+        return out, None
+
+
+def group_points(features, idx):
+    """features [B, C, N], idx int32 [B, npoint, nsample] -> [B, C, npoint, nsample]; differentiable in `features`."""
+    if torch.is_grad_enabled() and features.requires_grad:
+        return _GroupPoints.apply(_chk(features, torch.float32, "features"), _chk(idx, torch.int32, "idx"))
+    return _group_points(features, idx)
+
+
+def gather_points(features, idx):
+    """features [B, C, N], idx int32 [B, npoint] -> [B, C, npoint]; differentiable in `features`."""
+    if torch.is_grad_enabled() and features.requires_grad:
+        return _GroupPoints.apply(_chk(features, torch.float32, "features"), _chk(idx, torch.int32, "idx"))
+    return _gather_points(features, idx)
 
 
 def head_final_conv_backward(acts, grad_out, batch, H, W, groups, weights, out_cols, want_acts=True, want_weights=True):
@@ -2298,7 +2336,11 @@ def group_attention(qkv, tokens, groups, heads, split_only=False):
     C = heads * 16
     if qkv.shape != (tokens * groups, 3 * C):
         raise ValueError("qkv must be [tokens * groups, 3 * heads * 16]")
-    if split_only:                                   # split rows for the out-projection, no fp32 copy
+    if torch.is_grad_enabled() and qkv.requires_grad:
+        if split_only:
+            raise _lib.Df3dError("group_attention: the split rows feed the inference kernels and carry no gradient")
+        return _GroupAttention.apply(qkv, int(tokens), int(groups), int(heads))
+    if split_only:                                 # split rows for the out-projection, no fp32 copy
         sp = torch.empty((tokens * groups, 4 * C), dtype=torch.uint8, device=qkv.device)
         rc = lib.df3d_group_attention_split(_ptr(qkv), int(tokens), int(groups), int(heads), 16, None, _ptr(sp), _stream())
         _lib.check(rc, "df3d_group_attention_split")
@@ -2307,6 +2349,41 @@ def group_attention(qkv, tokens, groups, heads, split_only=False):
     rc = lib.df3d_group_attention(_ptr(qkv), int(tokens), int(groups), int(heads), 16, _ptr(out), _stream())
     _lib.check(rc, "df3d_group_attention")
     return out
+
+
+class _GroupAttention(torch.autograd.Function):
+    """`group_attention` under grad: the forward kernel, and df3d_group_attention_backward, which recomputes the probabilities
+    from the saved qkv rows (nothing else is kept: [rows, heads, tokens] probabilities would be 268 MB per layer at the
+    Voxel-RCNN size)."""
+
+    @staticmethod
+    def forward(ctx, qkv, tokens, groups, heads):
+        ctx.save_for_backward(qkv)
+        ctx.shape = (tokens, groups, heads)
+        return group_attention(qkv, tokens, groups, heads)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad):
+        (qkv,) = ctx.saved_tensors
+        tokens, groups, heads = ctx.shape
+        grad = _chk(grad.contiguous(), torch.float32, "grad")
+        out = torch.empty_like(qkv)
+        rc = _lib.load().df3d_group_attention_backward(_ptr(qkv), _ptr(grad), tokens, groups, heads, 16, _ptr(out), _stream())
+        _lib.check(rc, "df3d_group_attention_backward")
+        return out, None, None, None
+
+
+def group_attention_backward_supported(tokens, heads):
+    """The argument contract of df3d_group_attention_backward for heads of 16 channels (include/df3d_hip.h): one thread per
+    (token, head), two padded [tokens, C + 4] tiles and three statistics per thread within 64 KB of LDS."""
+    return 1 <= tokens and 1 <= heads and tokens * heads <= 1024 and (2 * tokens * (heads * 16 + 4) + 3 * tokens * heads) * 4 <= 65536
+
+
+def layernorm_rows(x, norm):
+    """norm(x) for an nn.LayerNorm over the last dimension of fp32 CUDA rows under grad: the row kernels of
+    `dropout_add_layernorm` without a second operand (one pass each way)."""
+    return _DropoutAddLayerNorm.apply(x.contiguous(), None, norm.weight, norm.bias, norm.eps, 0.0, 0)
 
 
 def voxel_image_sample(indices, batch, voxel_stride, voxel_size_zyx, range_min_zyx, aug, lidar2img, fmap, hw, add=None,

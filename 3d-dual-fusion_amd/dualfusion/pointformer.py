@@ -6,8 +6,11 @@ CP/det3d/ops/group_points/group_points.py:11-131).
 Pipeline: D-FPS of npoint centres -> ball query (radius, nsample) -> group features and ABSOLUTE
 xyz -> position-encoding MLP (1x1 conv + BN2d + ReLU, 1x1 conv) -> `num_layers` pre-norm MHA
 encoder layers over each group (sequence = nsample, batch = B*npoint) -> scatter the transformed
-group features back to the points.  Index ops are the HIP kernels of csrc/pointops.hip; the dense
-layers are plain library GEMMs.  Parameter names follow the reference (`pe.0.conv`, `pe.0.bn`,
+group features back to the points.  Index ops are the HIP kernels of csrc/pointops.hip.  Inference runs
+the fused layer kernels (csrc/ltlayer.hip) or the row kernels; under grad the module takes the same row
+layout from differentiable pieces (`_forward_train_rows`: row kernels with their own backward, the
+attention inside a group through df3d_group_attention / _backward); configurations those do not serve
+keep the torch composition of the layer.  Parameter names follow the reference (`pe.0.conv`, `pe.0.bn`,
 `pe.1.conv`, `chunk.layers.j.{self_attn,linear1,linear2,norm1,norm2}`), SURVEY.md Appendix B.
 """
 import copy
@@ -144,6 +147,44 @@ class TransformerEncoderLayerPreNorm(nn.Module):
             src = _ops.add_layernorm(src, src2.contiguous(), self.norm2.weight, self.norm2.bias, self.norm2.eps)
             src2 = self.linear2(self.activation(self.linear1(src)))
             return src + src2
+        if self._train_rows_fit(src, src_mask, src_key_padding_mask):
+            return self._forward_train_rows(src)
+        return self._forward_torch(src, src_mask, src_key_padding_mask)
+
+    def _train_rows_fit(self, src, src_mask, src_key_padding_mask):
+        """Under grad, the layer on the row kernels with backward kernels: fp32 GPU rows, heads of 16 channels, no masks, no
+        active dropout (LocalTransformer builds drop = 0.0).  Follows from the module and the tensor alone."""
+        a = self.self_attn
+        drops = a.dropout + self.dropout.p + self.dropout1.p + self.dropout2.p
+        return (torch.is_grad_enabled() and src.is_cuda and src.dtype == torch.float32 and src.dim() == 3
+                and not torch.is_autocast_enabled() and src_mask is None and src_key_padding_mask is None
+                and (drops == 0 or not self.training) and a.head_dim == 16 and a._qkv_same_embed_dim and not a.batch_first
+                and a.in_proj_bias is not None and a.bias_k is None and not a.add_zero_attn and src.shape[-1] == a.embed_dim
+                and src.shape[-1] <= 1024 and src.shape[1] > 0
+                and _ops.group_attention_backward_supported(src.shape[0], a.num_heads))
+
+    def _forward_train_rows(self, src):
+        """The layer under grad on [tokens * groups, C] rows, every step a kernel pair with its own backward: LN1
+        (`layernorm_rows`) -> in-projection (`linear_rows_autograd`: chunked weight gradient) -> `group_attention` (backward
+        recomputes the probabilities) -> out-projection -> LN2(x + .) (`dropout_add_layernorm`) -> linear1 -> ReLU in place
+        (`relu_dropout_`) -> linear2 -> + residual.  Both residuals start from the NORMALISED tensor (the reference's pre-norm
+        form, pointformer.py:34-43)."""
+        L, G, C = src.shape
+        a = self.self_attn
+        x1 = _ops.layernorm_rows(src.reshape(L * G, C), self.norm1)
+        qkv = _ops.linear_rows_autograd(x1, a.in_proj_weight, a.in_proj_bias)
+        att = _ops.group_attention(qkv, L, G, a.num_heads)
+        att = _ops.linear_rows_autograd(att, a.out_proj.weight, a.out_proj.bias)
+        x3 = _ops.dropout_add_layernorm(x1, att, self.norm2, self.dropout1)
+        h = _ops.linear_rows_autograd(x3, self.linear1.weight, self.linear1.bias)
+        if h.requires_grad and h._base is None and _ops.relu_dropout_supported(h):
+            h = _ops.relu_dropout_(h, 0.0)
+        else:
+            h = torch.relu(h)
+        return (x3 + _ops.linear_rows_autograd(h, self.linear2.weight, self.linear2.bias)).view(L, G, C)
+
+    def _forward_torch(self, src, src_mask=None, src_key_padding_mask=None):
+        """The layer as the torch composition of its modules (any configuration: masks, dropout, heads of any size, CPU)."""
         src = self.norm1(src)
         src2, _ = self.self_attn(src, src, src, attn_mask=src_mask, key_padding_mask=src_key_padding_mask,
                                  need_weights=False)
@@ -356,14 +397,53 @@ class LocalTransformer(nn.Module):
         flat.copy_(torch.where(has, y.index_select(0, src), flat))
         return rows
 
+    def _pe_rows_train(self, gx):
+        """self.pe on coordinate rows [R, 3] -> [R, C] under grad: the two 1x1 convolutions as row linears with the chunked
+        weight gradient, BatchNorm2d over the rows (its statistics over [B, ., np, ns] are the statistics over the R rows) on
+        batch statistics in train() mode (`ops.batch_norm_rows`: running statistics move as nn.BatchNorm2d moves them)."""
+        c0, c1 = self.pe[0], self.pe[1]
+        h = _ops.linear_rows_autograd(gx, c0.conv.weight[:, :, 0, 0], c0.conv.bias)
+        if c0.with_norm:
+            h = _ops.batch_norm_rows(c0.bn, h, relu=c0.with_activation)
+        elif c0.with_activation:
+            h = torch.relu(h)
+        return _ops.linear_rows_autograd(h, c1.conv.weight[:, :, 0, 0], c1.conv.bias)
+
+    def _forward_train_rows(self, xyz, features):
+        """The row layout of `_forward_rows` from differentiable pieces: the gradient reaches `features` through the grouped
+        rows (index_select by `sel`: every group a point is in) as well as through the kept rows of the points in no group
+        (the `where`).  Geometry and row plan carry no gradient and are shared between the layers as at inference."""
+        B, C, N = features.shape
+        with torch.no_grad():
+            group_idx, group_xyz = self._geometry(xyz)
+            sel, gx, src, has, _ = self._row_plan(xyz, group_idx, group_xyz)
+        ns, np_ = group_idx.shape[2], group_idx.shape[1]
+        flat = features.permute(0, 2, 1).reshape(B * N, C)         # (a view when the caller holds [B,N,C] rows)
+        x = flat.index_select(0, sel) + self._pe_rows_train(gx)
+        y = self.chunk(x.view(ns, B * np_, C)).reshape(ns * B * np_, C)
+        out = torch.where(has, y.index_select(0, src), flat).view(B, N, C)
+        features.copy_(out.permute(0, 2, 1))             # the reference mutates its input in place (:371-372)
+        return out
+
     def forward(self, xyz, features):
         """xyz [B,N,3], features [B,C,N] (may be a permuted view: 'replace' writes through it, as the
-        reference does) -> [B,N,C]."""
+        reference does) -> [B,N,C].
+
+        Under grad the result is differentiable in `features` and in every parameter, through the grouped rows and through
+        the kept rows.  With feat_agg_method 'replace' the result is ALSO written into the caller's `features` in place, under
+        grad as without: autograd refuses that write for a view of a leaf that requires grad and -- at backward -- for a
+        tensor an earlier node saved, so a training caller hands in a non-leaf nobody saved (the ACTRv2 encoder's query
+        tensor is one)."""
         if (features.is_cuda and not torch.is_grad_enabled() and not self.training and features.dtype == torch.float32
                 and self.attn_feat_agg_method == "unique" and self.feat_agg_method == "replace"
                 and features.permute(0, 2, 1).is_contiguous() and not (self.pe[0].with_norm and self.pe[0].bn.training)
                 and self.pe[1].with_norm is False and self.pe[1].with_activation is False):
             return self._forward_rows(xyz, features.permute(0, 2, 1))
+        if (features.is_cuda and torch.is_grad_enabled() and features.dtype == torch.float32
+                and not torch.is_autocast_enabled() and self.attn_feat_agg_method == "unique"
+                and self.feat_agg_method == "replace" and self.pe[1].with_norm is False
+                and self.pe[1].with_activation is False):
+            return self._forward_train_rows(xyz, features)
         feats_c = features.contiguous()
         group_idx, group_xyz = self._geometry(xyz)
         group_features = _ops.group_points(feats_c, group_idx)                          # [B,C,np,ns]

@@ -610,6 +610,15 @@ int df3d_group_attention(const float *qkv, int tokens, int groups, int heads, in
  * bf16 lo), what the out-projection on the split-precision kernels reads. */
 int df3d_group_attention_split(const float *qkv, int tokens, int groups, int heads, int head_dim, float *out, void *out_split,
                                void *stream);
+/* Backward of df3d_group_attention (training of the LocalTransformer): qkv as above, grad_out [tokens*groups][heads*16] ->
+ * grad_qkv [tokens*groups][3*heads*16], every element written (no pre-zeroing).  The probabilities are recomputed from qkv
+ * (the forward stores none); one workgroup owns a group and both reductions (d q over keys, d k / d v over queries) stay
+ * inside it: no atomics, two runs give the same bits.  fp32 arithmetic.
+ * Served: head_dim == 16, tokens * heads <= 1024 and (2 * tokens * (heads*16 + 4) + 3 * tokens * heads) * 4 bytes of LDS
+ * <= 64 KB (110 tokens at 4 heads: a little under the forward's 128, whose two tiles carry no padding and no statistics);
+ * groups == 0 is a no-op; null pointers with groups > 0 are refused (-1, df3d_last_error). */
+int df3d_group_attention_backward(const float *qkv, const float *grad_out, int tokens, int groups, int heads, int head_dim,
+                                  float *grad_qkv, void *stream);
 
 /* Grouped features + positional MLP of the LocalTransformer (pointformer.py:232-262) in one pass:
  * out[r] = feat[sel[r]] + W1 relu(W0 xyz[r] + b0) + b1 with feat [*, channels], sel [rows] int64, xyz [rows][3], W0 [hidden][3]
@@ -828,7 +837,8 @@ int df3d_relu_dropout_backward_bf16(const void *h, const void *grad, long long n
 /* training (round 6): out = LayerNorm(x + dropout(y, p)) over [rows, C] fp32 rows -- the residual steps of the encoder layers
  * (CP/det3d/models/model_utils/actr_transformer.py:311-312, 330-331, 389-390, 395-396, 416-417) -- in one kernel; also writes the
  * normalised rows `xhat` [rows, C] and `rstd` [rows] for the backward.  keep(i) = the hash of df3d_relu_dropout over the element
- * index row * C + c (p = 0: no dropout).  ..._backward: dx = d out / d x [rows, C]; dy = dx . keep / (1 - p) (may be NULL when
+ * index row * C + c (p = 0: no dropout).  y may be NULL: LayerNorm(x) alone (the first norm of the LocalTransformer's pre-norm
+ * layer in training; the backward then takes p = 0 and dy = NULL).  ..._backward: dx = d out / d x [rows, C]; dy = dx . keep / (1 - p) (may be NULL when
  * p = 0: dy = dx); dgamma / dbeta [C] are ADDED to (zero them first).  C % 4 == 0, C <= 1024. */
 int df3d_dropout_add_layernorm(const float *x, const float *y, const float *gamma, const float *beta, float eps, float p,
                                unsigned long long seed, long long rows, int C, float *out, float *xhat, float *rstd, void *stream);
