@@ -240,6 +240,16 @@ __device__ __forceinline__ int grid_rank(const GridView &g, long long flat) {
   return (int)(g.prefix[flat >> 6] + __popcll(w & ((1ull << b) - 1ull)));
 }
 
+// spconv_split.hip: the operand formats of the matrix-core convolutions by their 16-bit parts per value (1 = bf16 rows and
+// filters, 2 = "split", 3 = "split3"; rows and packed filters hold 2 * parts bytes per channel).  packed_bytes = 0: the format
+// has no kernel for the shape; rows: fp32 rows -> operand rows; run: the fused sparse convolution, `residual` as bf16 rows for
+// parts = 1 and fp32 rows otherwise, `out` and `out_rows` (operand rows of the result) each optional.
+size_t conv_operand_packed_bytes(int parts, int kvol, int cin, int cout);
+int conv_operand_rows(int parts, const float *x, long long n, int c, void *rows, hipStream_t stream);
+int conv_operand_run(int parts, const void *in, int n_in, int cin, const void *packed, int kvol, int cout, const int32_t *nbr,
+                     int n_out, const float *bias, const float *scale, const float *shift, const void *residual, int relu,
+                     float *out, void *out_rows, hipStream_t stream);
+
 // topk.hip: the K smallest 64-bit keys of each of S equally long segments, ascending (K <= 4096); out_count[s] (optional)
 // = how many of them are not the all-ones key
 size_t topk_keys_workspace(int S, long long n, int K);

@@ -133,6 +133,16 @@ int fail_arena(RunState &S, Bump *m, size_t *arena_used, size_t arena_bytes) {
   return DF3D_ENOMEM;
 }
 
+
+// The operand format layer L runs in, as 16-bit parts per value (common.h: 1 = bf16, 2 = split, 3 = split3), or 0 = the
+// exact-fp32 kernel.  Bits 1 (value 2: bf16) and 3 (value 8: three parts) of `reserved` are ABI.
+int layer_parts(const df3d_layer &L) {
+  if (!L.packed) return 0;
+  if (L.reserved & 2) return 1;
+  if (L.reserved & 8) return 3;
+  return conv_operand_packed_bytes(2, kvol_of(L.ksize), L.cin, L.cout) != 0 ? 2 : 0;
+}
+
 int state_init(RunState &S, const df3d_layer *layers, int nlayers, const int32_t *indices, int n, int in_channels, int batch,
                const int *shape) {
   S.layers = layers, S.nlayers = nlayers, S.indices = indices, S.n = n, S.in_channels = in_channels, S.batch = batch;
@@ -159,9 +169,9 @@ int state_init(RunState &S, const df3d_layer *layers, int nlayers, const int32_t
     const df3d_layer &L = layers[li];
     if (!flagged || (L.reserved & 4) || li == nlayers - 1) S.need_f32[li] = 1;
     if (L.residual >= 0 && L.residual < nlayers) S.need_f32[L.residual] = 1;
-    const bool split_consumer = L.packed && !(L.reserved & 2) && !(L.reserved & 1) &&
-                                ((L.reserved & 8) ? df3d_conv_packed_weight_bytes3(kvol_of(L.ksize), L.cin, L.cout) != 0
-                                                  : df3d_conv_packed_weight_bytes(kvol_of(L.ksize), L.cin, L.cout) != 0);
+    const int parts = layer_parts(L);
+    const bool split_consumer = parts >= 2 && !(L.reserved & 1) &&
+                                conv_operand_packed_bytes(parts, kvol_of(L.ksize), L.cin, L.cout) != 0;
     if (L.input >= 0 && L.input < nlayers && !split_consumer) S.need_f32[L.input] = 1;
     if (L.input >= 0 && L.input < nlayers && split_consumer && !(L.reserved & 8)) S.want_split[L.input] = 1;
   }
@@ -269,8 +279,7 @@ int geo_layer(RunState &S, int li, hipStream_t gstream, bool *new_table) {
     // are ~90 % empty, and the kernel then reads the present pairs instead of all K entries of every row.  Built here, in the
     // geometry phase (the frame head's stream, a frame ahead); layers that share the rulebook share the lists.
     static const bool lists_on = !(getenv("DF3D_ROW_LISTS") && getenv("DF3D_ROW_LISTS")[0] == '0');
-    const bool fp32_small = !(L.reserved & 1) && !(L.packed && (L.reserved & (2 | 8))) &&
-                            !(L.packed && df3d_conv_packed_weight_bytes(K, L.cin, L.cout) != 0);   // conv_layer's last branch
+    const bool fp32_small = !(L.reserved & 1) && layer_parts(L) == 0;   // conv_layer's last branch
     const int n_rows = S.sets[out_set].n;
     if (lists_on && fp32_small && L.cin <= 16 && (L.cout == 16 || L.cout == 32) && n_rows >= 2048 &&
         S.sets[in_set].n < (1 << 26)) {
@@ -331,10 +340,11 @@ int conv_layer(RunState &S, int li, const float *features, df3d_layer_view *view
   }
   DF3D_CHECK_ARG(L.input < 0 || S.outs[L.input].ran, "backbone_run: layer %d reads a geometry-only layer", li);
   o.ran = true;
-  const bool split_layer = L.packed && !(L.reserved & 2) &&
-                           ((L.reserved & 8) ? df3d_conv_packed_weight_bytes3(K, L.cin, L.cout) != 0
-                                             : df3d_conv_packed_weight_bytes(K, L.cin, L.cout) != 0);
-  if (S.need_f32[li] || !split_layer) {
+  const int parts = layer_parts(L);
+  if (parts)
+    DF3D_CHECK_ARG(conv_operand_packed_bytes(parts, K, L.cin, L.cout) != 0,
+                   "backbone_run: layer %d has no kernel on %d-part operands (K=%d cin=%d cout=%d)", li, parts, K, L.cin, L.cout);
+  if (S.need_f32[li] || parts < 2) {
     o.features = (float *)mem.take((size_t)n_out * L.cout * 4);
     if (!o.features) return DF3D_ENOMEM;
   }
@@ -342,59 +352,37 @@ int conv_layer(RunState &S, int li, const float *features, df3d_layer_view *view
   if (L.residual >= 0)
     DF3D_CHECK_ARG(S.outs[L.residual].set == out_set && S.outs[L.residual].channels == L.cout,
                    "backbone_run: residual of layer %d lives on another index set", li);
-  if (L.packed && (L.reserved & 2)) {          // bf16 rows / bf16 weights (DF3D_CONV_PRECISION=bf16)
-    DF3D_CHECK_ARG(df3d_conv_packed_weight_bytes_bf16(K, L.cin, L.cout) != 0,
-                   "backbone_run: layer %d has no bf16 kernel (K=%d cin=%d cout=%d)", li, K, L.cin, L.cout);
-    void **in16 = L.input < 0 ? &S.rows16_0 : &S.outs[L.input].rows16;
-    if (!*in16) {
-      *in16 = mem.take((size_t)n_in * L.cin * 2);
-      if (!*in16) return DF3D_ENOMEM;
-      int rc = df3d_rows_to_bf16(in_feat, n_in, L.cin, *in16, stream_);
-      if (rc) return rc;
-    }
-    const void *res16 = nullptr;
-    if (L.residual >= 0) {
-      LayerOut &R = S.outs[L.residual];
-      if (!R.rows16) {
-        R.rows16 = mem.take((size_t)n_out * L.cout * 2);
-        if (!R.rows16) return DF3D_ENOMEM;
-        int rc = df3d_rows_to_bf16(R.features, n_out, L.cout, R.rows16, stream_);
+  if (parts) {
+    // A matrix-core format: operand rows in (converted once per producer, on demand), fp32 rows and / or operand rows out.
+    // bf16 rows have their own slot; two- and three-part rows share one (a table runs in one of the two modes).
+    const size_t bpc = 2 * (size_t)parts;
+    auto slot = [&](int layer) -> void *& {
+      if (parts == 1) return layer < 0 ? S.rows16_0 : S.outs[layer].rows16;
+      return layer < 0 ? S.split0 : S.outs[layer].split;
+    };
+    auto operand = [&](int layer, const float *rows, int n, int c, const void **out) {
+      void *&r = slot(layer);
+      if (!r) {
+        r = mem.take((size_t)n * c * bpc);
+        if (!r) return (int)DF3D_ENOMEM;
+        int rc = conv_operand_rows(parts, rows, n, c, r, stream);
         if (rc) return rc;
       }
-      res16 = R.rows16;
-    }
-    o.rows16 = mem.take((size_t)n_out * L.cout * 2);
-    if (!o.rows16) return DF3D_ENOMEM;
-    int rc = df3d_sparse_conv_bf16(*in16, n_in, L.cin, L.packed, K, L.cout, nbr, n_out, L.bias, L.scale, L.shift, res16,
-                                   L.relu, o.features, o.rows16, stream_);
+      *out = r;
+      return (int)DF3D_OK;
+    };
+    const void *in_rows = nullptr, *res_rows = res;
+    int rc = operand(L.input, in_feat, n_in, L.cin, &in_rows);
     if (rc) return rc;
-  } else if (L.packed && (L.reserved & 8)) {     // three-part operands ("split3" precision)
-    DF3D_CHECK_ARG(df3d_conv_packed_weight_bytes3(K, L.cin, L.cout) != 0,
-                   "backbone_run: layer %d has no three-part kernel (K=%d cin=%d cout=%d)", li, K, L.cin, L.cout);
-    void **in3 = L.input < 0 ? &S.split0 : &S.outs[L.input].split;
-    if (!*in3) {
-      *in3 = mem.take((size_t)n_in * L.cin * 6);
-      if (!*in3) return DF3D_ENOMEM;
-      int rc = df3d_split_rows3(in_feat, n_in, L.cin, *in3, stream_);
+    if (parts == 1 && L.residual >= 0) {         // the bf16 kernel reads its residual as bf16 rows
+      rc = operand(L.residual, res, n_out, L.cout, &res_rows);
       if (rc) return rc;
     }
-    o.split = mem.take((size_t)n_out * L.cout * 6);
-    if (!o.split) return DF3D_ENOMEM;
-    int rc = df3d_conv_rows_split3(*in3, n_in, L.cin, L.cin, 0, L.packed, K, L.cout, 1, nbr, n_out, L.bias, L.scale, L.shift,
-                                   res, L.relu, o.features, L.cout, nullptr, o.split, stream_);
-    if (rc) return rc;
-  } else if (L.packed && df3d_conv_packed_weight_bytes(K, L.cin, L.cout) != 0) {
-    void **in_split = L.input < 0 ? &S.split0 : &S.outs[L.input].split;
-    if (!*in_split) {
-      *in_split = mem.take((size_t)n_in * L.cin * 4);
-      if (!*in_split) return DF3D_ENOMEM;
-      int rc = df3d_split_rows(in_feat, n_in, L.cin, *in_split, stream_);
-      if (rc) return rc;
-    }
-    o.split = mem.take((size_t)n_out * L.cout * 4);
-    if (!o.split) return DF3D_ENOMEM;
-    int rc = df3d_sparse_conv_split(*in_split, n_in, L.cin, L.packed, K, L.cout, nbr, n_out, L.bias, L.scale, L.shift,
-                                    res, L.relu, o.features, o.split, nullptr, 0, stream_);
+    void *&out_rows = slot(li);
+    out_rows = mem.take((size_t)n_out * L.cout * bpc);
+    if (!out_rows) return DF3D_ENOMEM;
+    rc = conv_operand_run(parts, in_rows, n_in, L.cin, L.packed, K, L.cout, nbr, n_out, L.bias, L.scale, L.shift, res_rows,
+                          L.relu, o.features, out_rows, stream);
     if (rc) return rc;
   } else {
     // a matrix-core layer reads this one (the stride-2 16 -> 32 layer feeds conv2's blocks): the operand split of the rows

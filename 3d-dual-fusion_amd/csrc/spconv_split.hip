@@ -13,16 +13,13 @@
 //
 // Data formats (both produced by kernels in this file or by the conv epilogue):
 //   split rows   [n][C/8][ hi 8 x fp16 | lo 8 x fp16 ]   32 B per 8 channels, same bytes as fp32
-//   packed W     [K][wave 4][kb][ct][hi|lo][lane 64][8 x fp16]: exactly the B operand of every lane, so the
+//   packed W     [K][kb][ct][hi|lo][lane 64][8 x fp16]: exactly the B operand of every lane, so the
 //                per-offset weight fetch is 16 B per lane, coalesced
 // (NP = 3: three bf16 parts per value, six products, fp32's exponent range; NP = 1: plain bf16 rows and filters)
 //
-// Kernel structure = spconv_pair_kernel (spconv.hip): one workgroup per CU, rulebook pairs of a row tile
-// compacted per kernel offset, 16-pair MFMA chunks, per-wave column slice of W in registers, LDS
-// accumulators, fused epilogue.  Differences: 16x16x32 bf16 MFMAs (3 per fp32 product block), gathers run
-// 3 items ahead (items are ~5x shorter than in the fp32 kernel), weights rotate between two register sets by
-// name, the item list is built by 32 lanes instead of one, and the epilogue can emit the split rows of its
-// output for the next convolution.
+// Kernel structure: output-stationary (spconv_os_split_kernel below; the loader / consumer kernel for 128-column blocks
+// of large maps).  The first kernel of this file compacted the rulebook pairs of a row tile per offset, like
+// spconv_pair_kernel of spconv.hip; it was slower at every measured size (158 against 86 us at conv4) and is gone.
 #include <stdlib.h>
 #include <algorithm>
 #include <string.h>
@@ -85,7 +82,7 @@ __global__ __launch_bounds__(256) void bf16_rows_to_f32_kernel(const u32x4 *__re
 }
 
 // W[K][CIN][COUT] fp32 -> bf16 B operands of the output-stationary kernel (NP = 1): [k][kb][ct][lane], same lane ->
-// (column, channel) map as layout 1 of pack_weights_kernel, hi parts only
+// (column, channel) map as pack_weights_kernel, hi parts only
 __global__ __launch_bounds__(256) void pack_weights_bf16_kernel(const float *__restrict__ w, int K, int cin, int cout,
                                                                 u32x4 *__restrict__ out) {
   const int KB = cin / 32;
@@ -212,7 +209,7 @@ __global__ __launch_bounds__(256) void split3_rows_kernel(const float *__restric
   out[3 * i + 2] = lo;
 }
 
-// W -> packed B operands of the output-stationary kernel with THREE parts: [half][k][kb][ct][hi|mid|lo][lane] (layout 1)
+// W -> packed B operands of the output-stationary kernel with THREE parts: [half][k][kb][ct][hi|mid|lo][lane]
 __global__ __launch_bounds__(256) void pack_weights3_kernel(const float *__restrict__ w, int K, int cin, int cout,
                                                             u32x4 *__restrict__ out) {
   const int KB = cin / 32;
@@ -239,14 +236,11 @@ __global__ __launch_bounds__(256) void pack_weights3_kernel(const float *__restr
   out[i] = (u32x4){v[0], v[1], v[2], v[3]};
 }
 
-// ---- W[K][CIN][COUT] fp32 -> packed B operands -----------------------------------------------------------
-// layout 0 (spconv_split_kernel, pair-compacted):   [k][wave 4][kb][ct][hi|lo][lane], lane (n,g) -> column
-//          wave*COUT/4 + CT*n + ct, channels g*CIN/4 + kb*8 + e
-// layout 1 (spconv_os_split_kernel, output-stationary): [k][kb][ct][hi|lo][lane], lane (n,g) -> column n*CT + ct,
-//          channels kb*32 + g*8 + e.  256-column filters are two such 128-column halves back to back
-//          ([half][k][kb][ct 8][hi|lo][lane], column half*128 + n*8 + ct): a workgroup computes one half.
+// ---- W[K][CIN][COUT] fp32 -> packed B operands (two parts) ------------------------------------------------
+// [k][kb][ct][hi|lo][lane], lane (n,g) -> column n*CT + ct, channels kb*32 + g*8 + e.  256-column filters are two such
+// 128-column halves back to back ([half][k][kb][ct 8][hi|lo][lane], column half*128 + n*8 + ct): a workgroup computes one half.
 __global__ __launch_bounds__(256) void pack_weights_kernel(const float *__restrict__ w, int K, int cin, int cout,
-                                                           int layout, u32x4 *__restrict__ out) {
+                                                           u32x4 *__restrict__ out) {
   const int KB = cin / 32;
   size_t total = (size_t)K * cin * cout / 4;
   size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -255,23 +249,12 @@ __global__ __launch_bounds__(256) void pack_weights_kernel(const float *__restri
   size_t r = i >> 6;
   int part = (int)(r & 1); r >>= 1;
   int n = lane & 15, g = lane >> 4;
-  int k, kb, col, ch0;
-  if (layout == 0) {
-    const int CS = cout / 4, CT = CS / 16;
-    int ct = (int)(r % CT); r /= CT;
-    kb = (int)(r % KB); r /= KB;
-    int wave = (int)(r & 3);
-    k = (int)(r >> 2);
-    col = wave * CS + CT * n + ct;
-    ch0 = g * (cin / 4) + kb * 8;
-  } else {
-    const int CW = cout > 128 ? 128 : cout, CT = CW / 16;
-    int ct = (int)(r % CT); r /= CT;
-    kb = (int)(r % KB); r /= KB;
-    k = (int)(r % K);
-    col = (int)(r / K) * CW + n * CT + ct;     // lane n owns CT consecutive output columns -> vector epilogue
-    ch0 = kb * 32 + g * 8;
-  }
+  const int CW = cout > 128 ? 128 : cout, CT = CW / 16;
+  int ct = (int)(r % CT); r /= CT;
+  int kb = (int)(r % KB); r /= KB;
+  int k = (int)(r % K);
+  int col = (int)(r / K) * CW + n * CT + ct;     // lane n owns CT consecutive output columns -> vector epilogue
+  int ch0 = kb * 32 + g * 8;
   u32x4 o;
 #pragma unroll
   for (int e = 0; e < 4; ++e) {
@@ -344,278 +327,6 @@ __device__ __forceinline__ f32x4 mfma_parts(const u32x4 &A, const u32x4 &B, cons
 // accumulator -> fp32 value
 template <int NP>
 __device__ __forceinline__ constexpr float acc_unscale() { return NP == 2 ? DF3D_ACC_UNSCALE : 1.0f; }
-
-template <int CIN, int COUT>
-__global__ __launch_bounds__(256, 1) void spconv_split_kernel(SplitConvArgs a, int TM,
-                                                               const int32_t *__restrict__ tile_rows) {
-  constexpr int KB = CIN / 32;       // 32-deep MFMA k-blocks; lane group g owns channels [g*CIN/4, (g+1)*CIN/4)
-  constexpr int CS = COUT / 4;       // output columns per wave
-  constexpr int CT = CS / 16;        // 16-wide column tiles per wave (1 or 2)
-  constexpr int NCH = 2 / CT;        // chunks per item -> always 2 independent accumulators
-  constexpr int RQ = CIN / 4;        // u32x4 per split row
-  static_assert(CT == 1 || CT == 2, "COUT must be 64 or 128");
-  static_assert(CIN % 32 == 0, "CIN must be a multiple of 32");
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  float *accL = (float *)smem;                                  // [4][TM+1][CS]; row TM = trash row
-  int *idxL = (int *)(smem + (size_t)4 * (TM + 1) * CS * 4);    // [K][TM]: nbr tile, compacted in place to input rows
-  unsigned short *listL = (unsigned short *)(idxL + a.K * TM);  // [K][TM]: matching output rows (tile-local)
-  __shared__ int cntL[DF3D_MAX_KVOL];
-  __shared__ int segL[DF3D_MAX_KVOL + 1];                       // first item of each ACTIVE offset; [nact] = T
-  __shared__ int actL[DF3D_MAX_KVOL + 1];                       // active offsets in order
-  __shared__ int nactL;
-
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int g = lane >> 4, n = lane & 15;
-  const int cs0 = wave * CS;
-  const int K = a.K;
-  const int range0 = tile_rows ? tile_rows[blockIdx.x] : blockIdx.x * TM;
-  const int range1 = tile_rows ? tile_rows[blockIdx.x + 1] : min(range0 + TM, a.n_out);
-  for (int row0 = range0; row0 < range1; row0 += TM) {
-    const int row_end = min(row0 + TM, range1);
-    __syncthreads();
-
-    for (int e = tid; e < K * TM; e += 256) {
-      int k = e / TM, r = e - k * TM;
-      int row = row0 + r;
-      idxL[e] = (row < row_end) ? a.nbr[(size_t)k * a.n_out + row] : -1;
-    }
-    float *myacc = accL + (size_t)wave * (TM + 1) * CS;
-    for (int e = lane; e < TM * CS / 4; e += 64) ((f32x4 *)myacc)[e] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    __syncthreads();
-    // ---- compact the valid pairs of every offset (offsets striped over the waves) ----
-    for (int k = wave; k < K; k += 4) {
-      int cnt = 0;
-      for (int r0 = 0; r0 < TM; r0 += 64) {
-        int r = r0 + lane;
-        int v = r < TM ? idxL[k * TM + r] : -1;
-        bool valid = v >= 0;
-        unsigned long long m = __ballot(valid);
-        int pos = cnt + __popcll(m & ((1ull << lane) - 1ull));
-        __builtin_amdgcn_wave_barrier();
-        if (valid) {
-          idxL[k * TM + pos] = v;
-          listL[k * TM + pos] = (unsigned short)r;
-        }
-        cnt += __popcll(m);
-      }
-      if (lane == 0) cntL[k] = cnt;
-    }
-    __syncthreads();
-
-    // ---- item list: one entry per (offset, chunk group): k | grp << 8 | cnt << 16, built by one lane per offset ----
-    int *itemL = (int *)(listL + (size_t)K * TM + (((size_t)K * TM) & 1));     // 4-byte aligned, [T+3]
-    auto ngroups = [&](int cnt) { return (((cnt + 15) >> 4) + NCH - 1) / NCH; };
-    if (tid < 32) {
-      int cnt = tid < K ? cntL[tid] : 0;
-      int ng = ngroups(cnt);
-      int start = 0, rank = 0, tot = 0, nact = 0;
-      for (int j = 0; j < K; ++j) {                // K <= 32: every lane scans the counts once
-        int c = cntL[j];
-        int gj = ngroups(c);
-        if (j < tid) { start += gj; rank += gj > 0; }
-        tot += gj;
-        nact += gj > 0;
-      }
-      if (tid < K && ng > 0) {
-        segL[rank] = start;
-        actL[rank] = tid;
-        for (int gq = 0; gq < ng; ++gq) itemL[start + gq] = tid | (gq << 8) | (cnt << 16);
-      }
-      if (tid == 0) {
-        segL[nact] = tot;
-        actL[nact] = 0;
-        nactL = nact;
-      }
-    }
-    __syncthreads();
-    const int nact = nactL;
-    const int T = segL[nact];
-    if (tid < 3 && T > 0) itemL[T + tid] = itemL[T - 1];   // sentinels: the look-ahead re-reads the last item
-    __syncthreads();
-
-    u32x4 bc[KB][CT][2], bn[KB][CT][2];
-    auto load_b = [&](int k, u32x4 (&dst)[KB][CT][2]) {
-      const u32x4 *wk = a.w + ((size_t)(k * 4 + wave) * (KB * CT * 2)) * 64 + lane;
-#pragma unroll
-      for (int kb = 0; kb < KB; ++kb)
-#pragma unroll
-        for (int ct = 0; ct < CT; ++ct)
-#pragma unroll
-          for (int p = 0; p < 2; ++p) dst[kb][ct][p] = wk[((kb * CT + ct) * 2 + p) * 64];
-    };
-    auto read_idx = [&](int item, int (&idx)[NCH]) {
-      int k = item & 0xff, grp = (item >> 8) & 0xff, cnt = item >> 16;
-#pragma unroll
-      for (int h = 0; h < NCH; ++h) {
-        int p = (grp * NCH + h) * 16 + n;
-        p = p < cnt ? p : cnt - 1;
-        idx[h] = idxL[k * TM + p];
-      }
-    };
-    auto read_rows = [&](int item, int (&rl)[NCH][4]) {
-      int k = item & 0xff, grp = (item >> 8) & 0xff, cnt = item >> 16;
-#pragma unroll
-      for (int h = 0; h < NCH; ++h)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          int p = (grp * NCH + h) * 16 + 4 * g + r;
-          int pp = p < cnt ? p : cnt - 1;
-          int t = listL[k * TM + pp];
-          rl[h][r] = p < cnt ? t : TM;              // invalid slots -> trash row
-        }
-    };
-    // A fragments of items t .. t+3 (the gathers run 3 items ahead): [slot][chunk][k-block][hi|lo]
-    u32x4 s0[NCH][KB][2], s1[NCH][KB][2], s2[NCH][KB][2], s3[NCH][KB][2];
-    auto load_a = [&](const int (&idx)[NCH], u32x4 (&dst)[NCH][KB][2]) {
-#pragma unroll
-      for (int h = 0; h < NCH; ++h) {
-        const u32x4 *src = a.feat + (size_t)idx[h] * RQ + (size_t)g * KB * 2;
-#pragma unroll
-        for (int kb = 0; kb < KB; ++kb) {
-          dst[h][kb][0] = src[kb * 2];
-          dst[h][kb][1] = src[kb * 2 + 1];
-        }
-      }
-    };
-    f32x4 acc[NCH][CT], aprev[NCH][CT];
-    float2 fo2[NCH][4];
-    float fo1[NCH][4];
-    auto flush_read = [&](const int (&rl)[NCH][4]) {
-#pragma unroll
-      for (int h = 0; h < NCH; ++h)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          if (CT == 2) fo2[h][r] = *(const float2 *)(myacc + (size_t)rl[h][r] * CS + 2 * n);
-          else fo1[h][r] = myacc[(size_t)rl[h][r] * CS + n];
-        }
-    };
-    auto flush_write = [&](const int (&rl)[NCH][4], f32x4 (&v)[NCH][CT]) {
-#pragma unroll
-      for (int h = 0; h < NCH; ++h)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          if (CT == 2) {
-            float2 o = fo2[h][r];
-            o.x += v[h][0][r];
-            o.y += v[h][CT - 1][r];
-            *(float2 *)(myacc + (size_t)rl[h][r] * CS + 2 * n) = o;
-          } else {
-            myacc[(size_t)rl[h][r] * CS + n] = fo1[h][r] + v[h][0][r];
-          }
-        }
-    };
-
-    int idxn[NCH], rl_cur[NCH][4], rl_prev[NCH][4];
-#pragma unroll
-    for (int h = 0; h < NCH; ++h) {
-#pragma unroll
-      for (int ct = 0; ct < CT; ++ct) aprev[h][ct] = (f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int r = 0; r < 4; ++r) rl_prev[h][r] = TM;       // first flush goes to the trash row
-    }
-    if (T > 0) {
-      load_b(actL[0], bn);
-      read_idx(itemL[0], idxn);
-      load_a(idxn, s0);
-      read_idx(itemL[1], idxn);
-      load_a(idxn, s1);
-      read_idx(itemL[2], idxn);
-      load_a(idxn, s2);
-    }
-    // One item = NCH chunks of 16 pairs = 3*KB*NCH*CT MFMAs.  The items of the whole tile form ONE software
-    // pipeline (no bubble at offset boundaries), unrolled four times so that the A ring slots are fixed
-    // registers.  When the offset changes, the prefetched weights move bn -> bc (once per ~T/K items) and the
-    // fetch of the following offset's weights starts.
-    int kcur = -1, ai = -1;
-    auto step = [&](int t, u32x4 (&cur)[NCH][KB][2], u32x4 (&tgt)[NCH][KB][2]) {
-      const int it0 = __builtin_amdgcn_readfirstlane(itemL[t]);
-      const int it3 = __builtin_amdgcn_readfirstlane(itemL[t + 3]);
-      if ((it0 & 0xff) != kcur) {
-        kcur = it0 & 0xff;
-        ++ai;
-#pragma unroll
-        for (int kb = 0; kb < KB; ++kb)
-#pragma unroll
-          for (int ct = 0; ct < CT; ++ct)
-#pragma unroll
-            for (int p = 0; p < 2; ++p) bc[kb][ct][p] = bn[kb][ct][p];
-        if (ai + 1 < nact) load_b(actL[ai + 1], bn);
-      }
-      read_idx(it3, idxn);
-      read_rows(it0, rl_cur);
-      flush_read(rl_prev);
-#pragma unroll
-      for (int h = 0; h < NCH; ++h)
-#pragma unroll
-        for (int ct = 0; ct < CT; ++ct) acc[h][ct] = (f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int kb = 0; kb < KB; ++kb)
-#pragma unroll
-        for (int term = 0; term < 3; ++term)          // lo*hi, hi*lo first (small), hi*hi last
-#pragma unroll
-          for (int h = 0; h < NCH; ++h)
-#pragma unroll
-            for (int ct = 0; ct < CT; ++ct) {
-              const int pa = term == 0 ? 1 : 0, pb = term == 1 ? 1 : 0;
-              acc[h][ct] = DF3D_MFMA_F16(cur[h][kb][pa], bc[kb][ct][pb], acc[h][ct]);
-            }
-      load_a(idxn, tgt);                                  // gathers of item t+3 (into the slot item t-1 freed)
-      flush_write(rl_prev, aprev);                        // item t-1's LDS update
-#pragma unroll
-      for (int h = 0; h < NCH; ++h) {
-#pragma unroll
-        for (int ct = 0; ct < CT; ++ct) aprev[h][ct] = acc[h][ct];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) rl_prev[h][r] = rl_cur[h][r];
-      }
-    };
-    for (int t = 0; t < T; t += 4) {
-      step(t, s0, s3);
-      if (t + 1 < T) step(t + 1, s1, s0);
-      if (t + 2 < T) step(t + 2, s2, s1);
-      if (t + 3 < T) step(t + 3, s3, s2);
-    }
-    flush_read(rl_prev);
-    flush_write(rl_prev, aprev);
-    __builtin_amdgcn_wave_barrier();
-
-    // ---- epilogue: this wave's CS columns of every row of the tile.  LDS column c of the wave's slice holds
-    //      output column cs0 + c (the packed weights put tile ct of lane n at column CT*n + ct) ----
-    constexpr int LPR = CS / 4;          // lanes per row (float4 each)
-    constexpr int RPI = 64 / LPR;        // rows per iteration
-    const int lr = lane / LPR, lc = (lane % LPR) * 4;
-    f32x4 bi = (f32x4){0.f, 0.f, 0.f, 0.f}, sc = (f32x4){1.f, 1.f, 1.f, 1.f}, sh = bi;
-    if (a.bias) bi = *(const f32x4 *)(a.bias + cs0 + lc);
-    if (a.scale) sc = *(const f32x4 *)(a.scale + cs0 + lc);
-    if (a.shift) sh = *(const f32x4 *)(a.shift + cs0 + lc);
-    for (int r0 = 0; r0 < TM; r0 += RPI) {
-      int rl = r0 + lr;
-      int row = row0 + rl;
-      if (rl < TM && row < row_end) {
-        f32x4 v = *(const f32x4 *)(myacc + (size_t)rl * CS + lc);
-        v = (v * DF3D_ACC_UNSCALE + bi) * sc + sh;
-        size_t o = (size_t)row * COUT + cs0 + lc;
-        if (a.residual) v += *(const f32x4 *)(a.residual + o);
-        if (a.relu) {
-          v[0] = fmaxf(v[0], 0.f);
-          v[1] = fmaxf(v[1], 0.f);
-          v[2] = fmaxf(v[2], 0.f);
-          v[3] = fmaxf(v[3], 0.f);
-        }
-        *(f32x4 *)(a.out + o) = v;
-        if (a.out_split) {
-          unsigned h[2], l[2];
-          split_pair(v[0], v[1], h[0], l[0]);
-          split_pair(v[2], v[3], h[1], l[1]);
-          // 8-channel block = [hi 16 B | lo 16 B]; this lane owns 4 of the 8 channels
-          char *blk = (char *)a.out_split + (o >> 3) * 32 + ((o >> 2) & 1) * 8;
-          *(u32x2 *)blk = (u32x2){h[0], h[1]};
-          *(u32x2 *)(blk + 16) = (u32x2){l[0], l[1]};
-        }
-      }
-    }
-  }  // passes over the row range
-}
 
 // (offset, channel block) of a step of the output-stationary kernels, advanced one step at a time from the set of the
 // tile's active offsets.  Everything lives in scalar registers: looking the offset of a step up in LDS put one (and with
@@ -1097,7 +808,7 @@ __global__ __launch_bounds__(NW * KS * 64) void spconv_os_split_kernel(SplitConv
         for (int ct = 0; ct < CT; ++ct) acc[rt][ct] += red[((((q - 1) * NW + wave) * RT + rt) * CT + ct) * 64 + lane];
   }
   // ---- epilogue: bias, folded BN, residual, ReLU; optional split rows of the result.  Lane n owns the CT
-  //      consecutive columns n*CT .. n*CT+CT-1 of its rows (packed-weight layout 1): 16-byte stores ----
+  //      consecutive columns n*CT .. n*CT+CT-1 of its rows (the packed filters' column order): 16-byte stores ----
   static_assert(CT == 2 || CT == 4 || CT == 8, "COUT must be 32, 64, 128 or 256");
   if constexpr (CT == 2) {
     // 32 columns per block: lane n owns columns 2n, 2n+1 (8-byte stores; four lanes share a split block)
@@ -1494,7 +1205,7 @@ __global__ __launch_bounds__(768) void spconv_os_lc_kernel(SplitConvArgs a) {
   } while (0)
 
   // ---- epilogue of one column block: bias, folded BN, residual, ReLU; optional split rows of the result.  Lane n owns the
-  //      CT consecutive columns n * CT .. n * CT + CT - 1 (packed-weight layout 1).  Leaves the accumulators at zero.
+  //      CT consecutive columns n * CT .. n * CT + CT - 1 (the packed filters' column order).  Leaves the accumulators at zero.
   //      Round 3: the arguments live in locals (the step loop's asm memory clobbers made every row re-load them from the
   //      kernel arguments) and the per-column vectors pass through an asm after their one wait -- the compiler could not
   //      prove those loads complete at the loop joins and put an s_waitcnt vmcnt(0) in front of EVERY row, i.e. it also
@@ -1748,66 +1459,6 @@ static int launch_os_split_wide(const SplitConvArgs &a, hipStream_t stream) {
   return DF3D_OK;
 }
 
-
-template <int CIN, int COUT>
-static int launch_split(const SplitConvArgs &a, const int32_t *tile_rows, int ntiles, hipStream_t stream) {
-  const size_t per_row = (size_t)COUT * 4 + (size_t)a.K * 4 + (size_t)a.K * 2;
-  int tm_max = (int)((144 * 1024) / per_row) & ~3;
-  if (tm_max > 4095) tm_max = 4092;                    // chunk-group index has 8 bits: (TM/16) < 256
-  int slots = num_cu();
-  int m = cdiv(a.n_out, (long long)slots * tm_max);
-  int TM = (cdiv(a.n_out, (long long)slots * m) + 3) & ~3;
-  if (TM < 16) TM = 16;
-  static bool configured = false;
-  if (!configured) {
-    hipError_t e = hipFuncSetAttribute((const void *)spconv_split_kernel<CIN, COUT>,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024);
-    if (e != hipSuccess) {
-      set_error("hipFuncSetAttribute(max dynamic LDS) failed: %s", hipGetErrorString(e));
-      return DF3D_EHIP;
-    }
-    configured = true;
-  }
-  int nt = cdiv(a.n_out, TM);
-  if (tile_rows && ntiles > 0) {
-    TM = tm_max;
-    nt = ntiles;
-  } else {
-    tile_rows = nullptr;
-  }
-  size_t lds = (size_t)(TM + 1) * COUT * 4 + (size_t)TM * a.K * 6 + ((size_t)a.K * (TM / 16 + 2) + 8) * 4 + 64;
-  hipLaunchKernelGGL((spconv_split_kernel<CIN, COUT>), dim3(nt), dim3(256), lds, stream, a, TM, tile_rows);
-  return DF3D_OK;
-}
-
-// which kernel serves a shape: 1 = output-stationary (layout 1), 0 = pair-compacted (layout 0)
-static int split_layout(int cin, int cout) {
-  static const char *force = getenv("DF3D_SPLIT_KERNEL");
-  if (force && force[0] == 'p') return 0;
-  if (force && force[0] == 'o') return 1;
-  (void)cin;
-  (void)cout;
-  return 1;
-}
-
-static bool split_shape_wide(int cin, int cout) {      // served by the output-stationary kernel only
-  return (cin == 256 && (cout == 128 || cout == 256)) || (cin == 128 && cout == 256);
-}
-
-static bool split_shape_head(int cin, int cout) {      // detection heads: shared conv 512 -> 64 | 128, final convs -> <= 32
-  return (cin == 512 && (cout == 64 || cout == 128)) || ((cin == 64 || cin == 128) && cout == 32) ||
-         (cin == 128 && cout == 64);                       // + the second linear of a 64-channel transformer FFN
-}
-
-// output-stationary launch of any served (cin, cout per column block) pair
-static int launch_os_any(int cin, int cout, const SplitConvArgs &a, hipStream_t stream);
-
-static bool split_shape_ok(int cin, int cout) {
-  return (cout == 128 && (cin == 128 || cin == 64)) || (cout == 64 && (cin == 64 || cin == 32)) ||
-         ((split_shape_wide(cin, cout) || split_shape_head(cin, cout) || (cout == 32 && cin == 32)) &&
-          split_layout(cin, cout) == 1);
-}
-
 // bf16 rows / bf16 weights (NP = 1): one configuration per shape (8 waves, or 2 for small row counts)
 template <int CIN, int COUT>
 static int launch_os_bf16(const SplitConvArgs &a, hipStream_t stream) {
@@ -1816,46 +1467,6 @@ static int launch_os_bf16(const SplitConvArgs &a, hipStream_t stream) {
   else
     hipLaunchKernelGGL((spconv_os_split_kernel<CIN, COUT, 1, 2, 1, 1>), dim3(cdiv(a.n_out, 32), a.gy), dim3(128), 0, stream, a);
   return DF3D_OK;
-}
-
-static bool bf16_shape_ok(int cin, int cout) {
-  // (128 -> 64 and 64 -> 32: the input gradients of the strided 64 -> 128 / 32 -> 64 layers -- round 6: they fell back to the
-  // exact-fp32 kernel, 649 us of the TransFusion training step)
-  return (cin == 32 && (cout == 32 || cout == 64)) || (cin == 64 && (cout == 32 || cout == 64 || cout == 128)) ||
-         (cin == 128 && (cout == 64 || cout == 128 || cout == 256)) || (cin == 256 && (cout == 128 || cout == 256));
-}
-
-static int launch_os_bf16_any(int cin, int cout, const SplitConvArgs &a, hipStream_t stream) {
-  if (cin == 32 && cout == 32) return launch_os_bf16<32, 32>(a, stream);
-  if (cin == 32 && cout == 64) return launch_os_bf16<32, 64>(a, stream);
-  if (cin == 64 && cout == 32) return launch_os_bf16<64, 32>(a, stream);
-  if (cin == 64 && cout == 64) return launch_os_bf16<64, 64>(a, stream);
-  if (cin == 64 && cout == 128) return launch_os_bf16<64, 128>(a, stream);
-  if (cin == 128 && cout == 64) return launch_os_bf16<128, 64>(a, stream);
-  if (cin == 128 && cout == 128) return launch_os_bf16<128, 128>(a, stream);
-  if (cin == 128 && cout == 256) return launch_os_bf16<128, 256>(a, stream);
-  if (cin == 256 && cout == 128) return launch_os_bf16<256, 128>(a, stream);
-  if (cin == 256 && cout == 256) return launch_os_bf16<256, 256>(a, stream);
-  set_error("no bf16 kernel for cin=%d cout=%d", cin, cout);
-  return DF3D_EINVAL;
-}
-
-static int launch_os_any(int cin, int cout, const SplitConvArgs &a, hipStream_t stream) {
-  if (cin == 256 && cout == 256) return launch_os_split_wide<256, 256>(a, stream);
-  if (cin == 256 && cout == 128) return launch_os_split_wide<256, 128>(a, stream);
-  if (cin == 128 && cout == 256) return launch_os_split_wide<128, 256>(a, stream);
-  if (cin == 512 && cout == 64) return launch_os_split_wide<512, 64>(a, stream);
-  if (cin == 512 && cout == 128) return launch_os_split_wide<512, 128>(a, stream);
-  if (cin == 128 && cout == 32) return launch_os_split<128, 32>(a, stream);
-  if (cin == 128 && cout == 64) return launch_os_split<128, 64>(a, stream);
-  if (cin == 128 && cout == 128) return launch_os_split<128, 128>(a, stream);
-  if (cin == 64 && cout == 128) return launch_os_split<64, 128>(a, stream);
-  if (cin == 64 && cout == 64) return launch_os_split<64, 64>(a, stream);
-  if (cin == 32 && cout == 64) return launch_os_split<32, 64>(a, stream);
-  if (cin == 64 && cout == 32) return launch_os_split<64, 32>(a, stream);
-  if (cin == 32 && cout == 32) return launch_os_split<32, 32>(a, stream);
-  set_error("no output-stationary split kernel for cin=%d cout=%d", cin, cout);
-  return DF3D_EINVAL;
 }
 
 // three-part operands (NP = 3, six products): one configuration per shape -- 8 waves per workgroup on the large maps, 4 / 2 on
@@ -1872,22 +1483,168 @@ static int launch_os_p3(const SplitConvArgs &a, hipStream_t stream) {
   return DF3D_OK;
 }
 
-static int launch_os_p3_any(int cin, int cout, const SplitConvArgs &a, hipStream_t stream) {
-  if (cin == 256 && cout == 256) return launch_os_p3<256, 256>(a, stream);
-  if (cin == 256 && cout == 128) return launch_os_p3<256, 128>(a, stream);
-  if (cin == 128 && cout == 256) return launch_os_p3<128, 256>(a, stream);
-  if (cin == 512 && cout == 64) return launch_os_p3<512, 64>(a, stream);
-  if (cin == 512 && cout == 128) return launch_os_p3<512, 128>(a, stream);
-  if (cin == 128 && cout == 32) return launch_os_p3<128, 32>(a, stream);
-  if (cin == 128 && cout == 64) return launch_os_p3<128, 64>(a, stream);
-  if (cin == 128 && cout == 128) return launch_os_p3<128, 128>(a, stream);
-  if (cin == 64 && cout == 128) return launch_os_p3<64, 128>(a, stream);
-  if (cin == 64 && cout == 64) return launch_os_p3<64, 64>(a, stream);
-  if (cin == 32 && cout == 64) return launch_os_p3<32, 64>(a, stream);
-  if (cin == 64 && cout == 32) return launch_os_p3<64, 32>(a, stream);
-  if (cin == 32 && cout == 32) return launch_os_p3<32, 32>(a, stream);
-  set_error("no three-part split kernel for cin=%d cout=%d", cin, cout);
+// ---- the shapes and the operand formats --------------------------------------------------------------------------------------
+// THE list of served (CIN, COUT per column block) pairs; the support predicate and the launch dispatch of every format are
+// generated from it, so a new shape is one line here.  FAM = launch family of the two-part format: `os` (launch_os_split) or
+// `wide` (launch_os_split_wide: the 256-channel maps of the BEV neck, the 512-channel shared convolutions of the heads).
+// B16 = 1 where the bf16 format has a kernel too; the two- and three-part formats serve every line.
+// (128 -> 32, 64 -> 32, 128 -> 64: final convolutions of the heads, the second linear of a 64-channel transformer FFN, and
+// the input gradients of the strided 64 -> 128 / 32 -> 64 layers -- round 6: the latter fell back to the exact-fp32 kernel in
+// the bf16 mode, 649 us of the TransFusion training step)
+#define DF3D_CONV_SHAPES(X) \
+  X(256, 256, wide, 1)      \
+  X(256, 128, wide, 1)      \
+  X(128, 256, wide, 1)      \
+  X(512, 64, wide, 0)       \
+  X(512, 128, wide, 0)      \
+  X(128, 32, os, 0)         \
+  X(128, 64, os, 1)         \
+  X(128, 128, os, 1)        \
+  X(64, 128, os, 1)         \
+  X(64, 64, os, 1)          \
+  X(32, 64, os, 1)          \
+  X(64, 32, os, 1)          \
+  X(32, 32, os, 1)
+
+enum { FAM_os, FAM_wide };
+
+// the launch of one (format, shape); only the kernels of served combinations are instantiated
+template <int NP, int CIN, int COUT, int FAM, bool B16>
+static int launch_shape(const SplitConvArgs &a, hipStream_t stream) {
+  if constexpr (NP == 3) return launch_os_p3<CIN, COUT>(a, stream);
+  else if constexpr (NP == 1 && B16) return launch_os_bf16<CIN, COUT>(a, stream);
+  else if constexpr (NP == 1) return DF3D_EINVAL;             // (not reached: conv_launch asks shape_ok first)
+  else if constexpr (FAM == FAM_wide) return launch_os_split_wide<CIN, COUT>(a, stream);
+  else return launch_os_split<CIN, COUT>(a, stream);
+}
+
+static bool shape_ok(int parts, int cin, int cout) {
+#define X(CIN, COUT, FAM, B16) \
+  if (cin == CIN && cout == COUT) return parts != 1 || B16;
+  DF3D_CONV_SHAPES(X)
+#undef X
+  return false;
+}
+
+template <int NP>
+static int launch_any(int cin, int cout, const SplitConvArgs &a, hipStream_t stream) {
+#define X(CIN, COUT, FAM, B16) \
+  if (cin == CIN && cout == COUT) return launch_shape<NP, CIN, COUT, FAM_##FAM, B16>(a, stream);
+  DF3D_CONV_SHAPES(X)
+#undef X
   return DF3D_EINVAL;
+}
+
+// An operand format of the matrix-core kernels: how many 16-bit parts stand for one fp32 value.  Operand rows and packed
+// filters hold 2 * parts bytes per channel.  A new format is one entry of g_formats (plus its NP case in the kernel).
+struct ConvFormat {
+  int parts;                 // 1 = bf16, 2 = "split" (fp16 hi + lo, three products), 3 = "split3" (three bf16 parts, six products)
+  const char *what;          // the format in error texts
+  int timing;                // tag of its timing records (df3d_timing_get2: `split`)
+  int both_bit;              // added to the tag of a whole sparse layer that writes fp32 and operand rows (two-part format only)
+  bool tuning;               // the launches read DF3D_OS_DBG and the trace buffer of the tuning builds (two-part format only)
+  int (*rows)(const float *, long long, int, void *, void *);                    // fp32 rows -> operand rows (the exported entry)
+  void (*pack_kernel)(const float *, int, int, int, u32x4 *);                     // fp32 filters -> packed B operands
+  int (*launch)(int cin, int cout, const SplitConvArgs &, hipStream_t);           // the convolution of a served shape
+  int bytes_per_channel() const { return 2 * parts; }
+  size_t packed_bytes(int kvol, int cin, int cout) const {                        // 0: no kernel for the shape
+    if (!shape_ok(parts, cin, cout) || kvol <= 0 || kvol > DF3D_MAX_KVOL) return 0;
+    return (size_t)kvol * cin * cout * bytes_per_channel();
+  }
+};
+
+static const ConvFormat g_formats[3] = {
+    {1, "bf16", 2, 0, false, df3d_rows_to_bf16, pack_weights_bf16_kernel, launch_any<1>},
+    {2, "split-precision", 1, 8, true, df3d_split_rows, pack_weights_kernel, launch_any<2>},
+    {3, "three-part", 3, 0, false, df3d_split_rows3, pack_weights3_kernel, launch_any<3>},
+};
+static const ConvFormat &conv_format(int parts) { return g_formats[parts - 1]; }
+
+// `groups` filter banks [K][cin][cout] back to back -> their packed image (offset-major, so G banks are one bank of G * K offsets)
+static int pack_filters(const ConvFormat &f, const char *entry, const float *filters, int groups, int kvol, int cin, int cout,
+                        void *packed, hipStream_t stream) {
+  DF3D_CHECK_ARG(filters && packed && groups >= 1, "%s: bad argument", entry);
+  DF3D_CHECK_ARG(f.packed_bytes(kvol, cin, cout) != 0 && (groups == 1 || cout <= 128),
+                 "%s: shape K=%d cin=%d cout=%d (%d groups) has no %s kernel", entry, kvol, cin, cout, groups, f.what);
+  const size_t total = (size_t)groups * kvol * cin * cout / 8 * f.parts;           // 16-byte groups
+  hipLaunchKernelGGL(f.pack_kernel, dim3(cdiv((long long)total, 256)), dim3(256), 0, stream, filters, groups * kvol, cin, cout,
+                     (u32x4 *)packed);
+  DF3D_LAUNCH_CHECK();
+  return DF3D_OK;
+}
+
+// What the exported convolution entries hand to conv_launch: `groups` convolutions over one neighbour table; group g reads
+// input columns g * in_group_stride .. + cin of the in_channels-wide operand rows and writes output columns g * cout .. of the
+// out_channels-wide rows (or the compact columns `out_cols`).  The plain sparse convolution is groups = 1, in_channels = cin,
+// out_channels = cout.
+struct ConvCall {
+  const void *in;
+  int n_in, in_channels, cin, in_group_stride;
+  const void *packed;
+  int kvol, cout, groups;
+  const int32_t *nbr;
+  int n_out;
+  const float *bias, *scale, *shift;
+  const void *residual;      // bf16 rows for the bf16 format, fp32 rows otherwise
+  int relu;
+  float *out;
+  int out_channels;
+  const int32_t *out_cols;
+  void *out_rows;            // operand rows of the output (optional)
+  const int32_t *order;      // optional tiling order
+  bool tag_both;             // a whole sparse layer: its timing record says when both row formats are written (bit 3)
+};
+
+// the one launcher: argument checks, kernel arguments, timing record, launch.  `entry` = the exported name in error texts
+static int conv_launch(const ConvFormat &f, const char *entry, const ConvCall &c, hipStream_t stream) {
+  DF3D_CHECK_ARG(c.in && c.packed && c.nbr && (c.out || c.out_rows), "%s: null argument", entry);
+  DF3D_CHECK_ARG(c.kvol > 0 && c.kvol <= DF3D_MAX_KVOL, "%s: kernel volume %d unsupported", entry, c.kvol);
+  DF3D_CHECK_ARG(shape_ok(f.parts, c.cin, c.cout), "%s: cin=%d cout=%d has no %s kernel", entry, c.cin, c.cout, f.what);
+  DF3D_CHECK_ARG(c.groups >= 1 && c.groups <= 65535, "%s: groups", entry);
+  DF3D_CHECK_ARG(c.in_channels % 8 == 0 && c.in_group_stride % 8 == 0 && c.in_group_stride >= 0 &&
+                     (long long)(c.groups - 1) * c.in_group_stride + c.cin <= c.in_channels,
+                 "%s: input columns [g*%d, g*%d+%d) must lie inside the %d-channel rows", entry, c.in_group_stride,
+                 c.in_group_stride, c.cin, c.in_channels);
+  DF3D_CHECK_ARG(!c.residual || (c.groups == 1 && c.out_channels == c.cout), "%s: a residual needs one group and dense output rows",
+                 entry);
+  if (c.out_cols) {
+    DF3D_CHECK_ARG(c.cout == 32 && !c.out_rows, "%s: compact output columns need cout = 32 and no operand rows out", entry);
+  } else {
+    DF3D_CHECK_ARG(c.out_channels % 8 == 0 && (long long)c.groups * c.cout <= c.out_channels,
+                   "%s: %d x %d output columns do not fit %d-channel rows", entry, c.groups, c.cout, c.out_channels);
+  }
+  if (c.n_out == 0) return DF3D_OK;
+  const char *dbg = f.tuning ? getenv("DF3D_OS_DBG") : nullptr;
+  SplitConvArgs a = {(const u32x4 *)c.in, (const u32x4 *)c.packed, c.nbr, c.bias, c.scale, c.shift, (const float *)c.residual,
+                     c.out, (u32x4 *)c.out_rows, c.n_in, c.n_out, c.kvol, c.relu, dbg ? atoi(dbg) : 0,
+                     c.in_channels / 8 * f.parts, c.in_group_stride / 8 * f.parts, c.out_channels,
+                     c.groups * (c.cout > 128 ? c.cout / 128 : 1), c.out_cols, c.order};
+#ifdef DF3D_OS_TRACE
+  if (f.tuning) a.trace = g_os_trace;
+#endif
+  int rec = timing_rec_begin(c.cin, c.cout * c.groups, c.kvol, c.n_out, c.nbr,
+                             f.timing | (c.tag_both && c.out && c.out_rows ? f.both_bit : 0), stream);
+  int rc = f.launch(c.cin, c.cout, a, stream);
+  if (rc) return rc;
+  timing_rec_end(rec, stream);
+  DF3D_LAUNCH_CHECK();
+  return DF3D_OK;
+}
+
+// ---- what csrc/executor.hip needs of a format (common.h) ----
+size_t conv_operand_packed_bytes(int parts, int kvol, int cin, int cout) { return conv_format(parts).packed_bytes(kvol, cin, cout); }
+
+int conv_operand_rows(int parts, const float *x, long long n, int c, void *rows, hipStream_t stream) {
+  return conv_format(parts).rows(x, n, c, rows, (void *)stream);
+}
+
+int conv_operand_run(int parts, const void *in, int n_in, int cin, const void *packed, int kvol, int cout, const int32_t *nbr,
+                     int n_out, const float *bias, const float *scale, const float *shift, const void *residual, int relu,
+                     float *out, void *out_rows, hipStream_t stream) {
+  const ConvFormat &f = conv_format(parts);
+  return conv_launch(f, "backbone_run", ConvCall{in, n_in, cin, cin, 0, packed, kvol, cout, 1, nbr, n_out, bias, scale, shift,
+                                                 residual, relu, out, cout, nullptr, out_rows, nullptr, true},
+                     stream);
 }
 
 }  // namespace df3d
@@ -1896,23 +1653,11 @@ using namespace df3d;
 
 // ---- "split3" precision (round 4): operands as THREE bf16 parts (hi + mid + lo = the fp32 value exactly), six MFMA products
 //      per operand pair, fp32 accumulate: fp32-grade results (dropped terms <= 2^-24 of a product) at 1/6 of the bf16 rate --
-//      2.6x the fp32 matrix rate.  Same shapes as the output-stationary split kernels. ----
-extern "C" size_t df3d_conv_packed_weight_bytes3(int kvol, int cin, int cout) {
-  if (!split_shape_ok(cin, cout) || split_layout(cin, cout) != 1 || kvol <= 0 || kvol > DF3D_MAX_KVOL) return 0;
-  return (size_t)kvol * cin * cout * 6;
-}
+//      2.6x the fp32 matrix rate.  Same shapes as the two-part kernels. ----
+extern "C" size_t df3d_conv_packed_weight_bytes3(int kvol, int cin, int cout) { return conv_format(3).packed_bytes(kvol, cin, cout); }
 
 extern "C" int df3d_conv_pack_weights3(const float *filters, int groups, int kvol, int cin, int cout, void *packed, void *stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  DF3D_CHECK_ARG(filters && packed && groups >= 1, "conv_pack_weights3: bad argument");
-  DF3D_CHECK_ARG(df3d_conv_packed_weight_bytes3(kvol, cin, cout) != 0 && (groups == 1 || cout <= 128),
-                 "conv_pack_weights3: shape K=%d cin=%d cout=%d has no three-part kernel", kvol, cin, cout);
-  // (G filter banks back to back are one bank of G * K offsets, as in df3d_conv_pack_weights_groups)
-  size_t total = (size_t)groups * kvol * cin * cout / 8 * 3;
-  hipLaunchKernelGGL(pack_weights3_kernel, dim3(cdiv((long long)total, 256)), dim3(256), 0, stream, filters, groups * kvol, cin,
-                     cout, (u32x4 *)packed);
-  DF3D_LAUNCH_CHECK();
-  return DF3D_OK;
+  return pack_filters(conv_format(3), "conv_pack_weights3", filters, groups, kvol, cin, cout, packed, (hipStream_t)stream_);
 }
 
 extern "C" int df3d_split_rows3(const float *features, long long n, int c, void *split3, void *stream_) {
@@ -1933,63 +1678,24 @@ extern "C" int df3d_conv_rows_split3(const void *in_split3, int n_in, int in_cha
                                      const float *bias, const float *scale, const float *shift, const float *residual,
                                      int relu, float *out, int out_channels, const int32_t *out_cols, void *out_split3,
                                      void *stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  DF3D_CHECK_ARG(in_split3 && packed3 && nbr && (out || out_split3), "conv_rows_split3: null argument");
-  DF3D_CHECK_ARG(df3d_conv_packed_weight_bytes3(kvol, cin, cout) != 0, "conv_rows_split3: K=%d cin=%d cout=%d has no three-part kernel",
-                 kvol, cin, cout);
-  DF3D_CHECK_ARG(groups >= 1 && groups <= 65535, "conv_rows_split3: groups");
-  DF3D_CHECK_ARG(in_channels % 8 == 0 && in_group_stride % 8 == 0 && in_group_stride >= 0 &&
-                     (long long)(groups - 1) * in_group_stride + cin <= in_channels,
-                 "conv_rows_split3: input columns of the groups must lie inside the %d-channel rows", in_channels);
-  DF3D_CHECK_ARG(!residual || (groups == 1 && out_channels == cout), "conv_rows_split3: a residual needs one group and dense output rows");
-  const int blocks = groups * (cout > 128 ? cout / 128 : 1);
-  if (out_cols) {
-    DF3D_CHECK_ARG(cout == 32 && !out_split3, "conv_rows_split3: compact output columns need cout = 32 and no split output");
-  } else {
-    DF3D_CHECK_ARG(out_channels % 8 == 0 && (long long)groups * cout <= out_channels,
-                   "conv_rows_split3: %d x %d output columns do not fit %d-channel rows", groups, cout, out_channels);
-  }
-  if (n_out == 0) return DF3D_OK;
-  SplitConvArgs a = {(const u32x4 *)in_split3, (const u32x4 *)packed3, nbr, bias, scale, shift, residual,
-                     out, (u32x4 *)out_split3, n_in, n_out, kvol, relu, 0,
-                     in_channels / 8 * 3, in_group_stride / 8 * 3, out_channels, blocks, out_cols};
-  int rec = timing_rec_begin(cin, cout * groups, kvol, n_out, nbr, 3, stream);
-  int rc = launch_os_p3_any(cin, cout, a, stream);
-  if (rc) return rc;
-  timing_rec_end(rec, stream);
-  DF3D_LAUNCH_CHECK();
-  return DF3D_OK;
+  return conv_launch(conv_format(3), "conv_rows_split3",
+                     ConvCall{in_split3, n_in, in_channels, cin, in_group_stride, packed3, kvol, cout, groups, nbr, n_out, bias,
+                              scale, shift, residual, relu, out, out_channels, out_cols, out_split3, nullptr, false},
+                     (hipStream_t)stream_);
 }
 
-extern "C" size_t df3d_conv_packed_weight_bytes(int kvol, int cin, int cout) {
-  if (!split_shape_ok(cin, cout) || kvol <= 0 || kvol > DF3D_MAX_KVOL) return 0;
-  return (size_t)kvol * cin * cout * 4;
-}
+extern "C" size_t df3d_conv_packed_weight_bytes(int kvol, int cin, int cout) { return conv_format(2).packed_bytes(kvol, cin, cout); }
 
 extern "C" int df3d_conv_pack_weights(const float *filters, int kvol, int cin, int cout, void *packed, void *stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  DF3D_CHECK_ARG(filters && packed, "conv_pack_weights: null argument");
-  DF3D_CHECK_ARG(df3d_conv_packed_weight_bytes(kvol, cin, cout) != 0,
-                 "conv_pack_weights: shape K=%d cin=%d cout=%d has no split-precision kernel", kvol, cin, cout);
-  size_t total = (size_t)kvol * cin * cout / 4;     // 16-byte groups
-  hipLaunchKernelGGL(pack_weights_kernel, dim3(cdiv((long long)total, 256)), dim3(256), 0, stream, filters, kvol, cin,
-                     cout, split_layout(cin, cout), (u32x4 *)packed);
-  DF3D_LAUNCH_CHECK();
-  return DF3D_OK;
+  return pack_filters(conv_format(2), "conv_pack_weights", filters, 1, kvol, cin, cout, packed, (hipStream_t)stream_);
 }
 
 extern "C" int df3d_conv_pack_weights_groups(const float *filters, int groups, int kvol, int cin, int cout, void *packed,
                                              void *stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  DF3D_CHECK_ARG(filters && packed && groups >= 1, "conv_pack_weights_groups: bad argument");
-  DF3D_CHECK_ARG(df3d_conv_packed_weight_bytes(kvol, cin, cout) != 0 && cout <= 128,
-                 "conv_pack_weights_groups: shape K=%d cin=%d cout=%d has no grouped split-precision kernel", kvol, cin, cout);
-  // one column block per filter bank: the packed image is offset-major, so G banks back to back are one bank of G * K offsets
-  size_t total = (size_t)groups * kvol * cin * cout / 4;
-  hipLaunchKernelGGL(pack_weights_kernel, dim3(cdiv((long long)total, 256)), dim3(256), 0, stream, filters, groups * kvol,
-                     cin, cout, split_layout(cin, cout), (u32x4 *)packed);
-  DF3D_LAUNCH_CHECK();
-  return DF3D_OK;
+  // one column block per filter bank, also for a single bank
+  DF3D_CHECK_ARG(cout <= 128, "conv_pack_weights_groups: shape K=%d cin=%d cout=%d has no grouped split-precision kernel", kvol, cin,
+                 cout);
+  return pack_filters(conv_format(2), "conv_pack_weights_groups", filters, groups, kvol, cin, cout, packed, (hipStream_t)stream_);
 }
 
 // scale: DF3D_POW2_SCALE_FLOATS floats -- [0] = s, [1] = the largest |value|, the rest the reduction's per-workgroup maxima
@@ -2046,41 +1752,17 @@ extern "C" int df3d_split_rows(const float *features, long long n, int c, void *
   return DF3D_OK;
 }
 
+// The sparse convolution on two-part rows.  tile_rows / ntiles: ntiles == -1 makes tile_rows the [n_out] tiling order of the
+// output-stationary kernel; any other value is accepted and ignored (row ranges of the retired pair-compacted kernel).
 extern "C" int df3d_sparse_conv_split(const void *features_split, int n_in, int cin, const void *packed_filters,
                                       int kvol, int cout, const int32_t *nbr, int n_out, const float *bias,
                                       const float *scale, const float *shift, const float *residual, int relu,
                                       float *out, void *out_split, const int32_t *tile_rows, int ntiles,
                                       void *stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  DF3D_CHECK_ARG(features_split && packed_filters && nbr && (out || out_split), "sparse_conv_split: null argument");
-  DF3D_CHECK_ARG(kvol > 0 && kvol <= DF3D_MAX_KVOL, "sparse_conv_split: kernel volume %d unsupported", kvol);
-  DF3D_CHECK_ARG(split_shape_ok(cin, cout), "sparse_conv_split: cin=%d cout=%d has no split-precision kernel", cin,
-                 cout);
-  DF3D_CHECK_ARG(out || split_layout(cin, cout) == 1, "sparse_conv_split: the pair-compacted kernel always writes fp32 rows");
-  if (n_out == 0) return DF3D_OK;
-  SplitConvArgs a = {(const u32x4 *)features_split, (const u32x4 *)packed_filters, nbr, bias, scale, shift, residual,
-                     out, (u32x4 *)out_split, n_in, n_out, kvol, relu,
-                     getenv("DF3D_OS_DBG") ? atoi(getenv("DF3D_OS_DBG")) : 0,
-                     cin / 4, 0, cout, cout > 128 ? cout / 128 : 1, nullptr};
-  if (ntiles == -1 && tile_rows) a.order = tile_rows;       // tiling order of the output-stationary kernel
-#ifdef DF3D_OS_TRACE
-  a.trace = g_os_trace;
-#endif
-  int rec = timing_rec_begin(cin, cout, kvol, n_out, nbr, 1 | (out && out_split ? 8 : 0), stream);   // bit 3: both row formats written
-  int rc;
-  if (split_layout(cin, cout) == 1) {
-    rc = launch_os_any(cin, cout, a, stream);
-  } else if (cout == 128) {
-    rc = cin == 128 ? launch_split<128, 128>(a, tile_rows, ntiles, stream)
-                    : launch_split<64, 128>(a, tile_rows, ntiles, stream);
-  } else {
-    rc = cin == 64 ? launch_split<64, 64>(a, tile_rows, ntiles, stream)
-                   : launch_split<32, 64>(a, tile_rows, ntiles, stream);
-  }
-  if (rc) return rc;
-  timing_rec_end(rec, stream);
-  DF3D_LAUNCH_CHECK();
-  return DF3D_OK;
+  return conv_launch(conv_format(2), "sparse_conv_split",
+                     ConvCall{features_split, n_in, cin, cin, 0, packed_filters, kvol, cout, 1, nbr, n_out, bias, scale, shift,
+                              residual, relu, out, cout, nullptr, out_split, ntiles == -1 ? tile_rows : nullptr, true},
+                     (hipStream_t)stream_);
 }
 
 extern "C" int df3d_conv_rows_split(const void *in_split, int n_in, int in_channels, int cin, int in_group_stride,
@@ -2088,36 +1770,10 @@ extern "C" int df3d_conv_rows_split(const void *in_split, int n_in, int in_chann
                                     int n_out, const float *bias, const float *scale, const float *shift, int relu,
                                     float *out, int out_channels, const int32_t *out_cols, void *out_split,
                                     void *stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  DF3D_CHECK_ARG(in_split && packed_filters && nbr && (out || out_split), "conv_rows_split: null argument");
-  DF3D_CHECK_ARG(kvol > 0 && kvol <= DF3D_MAX_KVOL, "conv_rows_split: kernel volume %d unsupported", kvol);
-  DF3D_CHECK_ARG(split_shape_ok(cin, cout) && split_layout(cin, cout) == 1,
-                 "conv_rows_split: cin=%d cout=%d has no output-stationary split kernel", cin, cout);
-  DF3D_CHECK_ARG(groups >= 1 && groups <= 65535, "conv_rows_split: groups");
-  DF3D_CHECK_ARG(in_channels % 8 == 0 && in_group_stride % 8 == 0 && in_group_stride >= 0 &&
-                     (long long)(groups - 1) * in_group_stride + cin <= in_channels,
-                 "conv_rows_split: input columns [g*%d, g*%d+%d) must lie inside the %d-channel rows", in_group_stride,
-                 in_group_stride, cin, in_channels);
-  const int blocks = groups * (cout > 128 ? cout / 128 : 1);
-  if (out_cols) {
-    DF3D_CHECK_ARG(cout == 32 && !out_split, "conv_rows_split: compact output columns need cout = 32 and no split output");
-  } else {
-    DF3D_CHECK_ARG(out_channels % 8 == 0 && (long long)groups * cout <= out_channels,
-                   "conv_rows_split: %d x %d output columns do not fit %d-channel rows", groups, cout, out_channels);
-  }
-  if (n_out == 0) return DF3D_OK;
-  SplitConvArgs a = {(const u32x4 *)in_split, (const u32x4 *)packed_filters, nbr, bias, scale, shift, nullptr,
-                     out, (u32x4 *)out_split, n_in, n_out, kvol, relu,
-                     getenv("DF3D_OS_DBG") ? atoi(getenv("DF3D_OS_DBG")) : 0, in_channels / 4, in_group_stride / 4, out_channels, blocks, out_cols};
-#ifdef DF3D_OS_TRACE
-  a.trace = g_os_trace;
-#endif
-  int rec = timing_rec_begin(cin, cout * groups, kvol, n_out, nbr, 1, stream);
-  int rc = launch_os_any(cin, cout, a, stream);
-  if (rc) return rc;
-  timing_rec_end(rec, stream);
-  DF3D_LAUNCH_CHECK();
-  return DF3D_OK;
+  return conv_launch(conv_format(2), "conv_rows_split",
+                     ConvCall{in_split, n_in, in_channels, cin, in_group_stride, packed_filters, kvol, cout, groups, nbr, n_out,
+                              bias, scale, shift, nullptr, relu, out, out_channels, out_cols, out_split, nullptr, false},
+                     (hipStream_t)stream_);
 }
 
 // ---- bf16 rows / bf16 weights, fp32 accumulate (BASELINE configs[2]: "bf16, fp32 accumulate") -------------------
@@ -2145,40 +1801,19 @@ extern "C" int df3d_rows_from_bf16(const void *rows_bf16, long long n, int c, fl
   return DF3D_OK;
 }
 
-extern "C" size_t df3d_conv_packed_weight_bytes_bf16(int kvol, int cin, int cout) {
-  if (!bf16_shape_ok(cin, cout) || kvol <= 0 || kvol > DF3D_MAX_KVOL) return 0;
-  return (size_t)kvol * cin * cout * 2;
-}
+extern "C" size_t df3d_conv_packed_weight_bytes_bf16(int kvol, int cin, int cout) { return conv_format(1).packed_bytes(kvol, cin, cout); }
 
 extern "C" int df3d_conv_pack_weights_bf16(const float *filters, int kvol, int cin, int cout, void *packed,
                                            void *stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  DF3D_CHECK_ARG(filters && packed, "conv_pack_weights_bf16: null argument");
-  DF3D_CHECK_ARG(df3d_conv_packed_weight_bytes_bf16(kvol, cin, cout) != 0,
-                 "conv_pack_weights_bf16: shape K=%d cin=%d cout=%d has no bf16 kernel", kvol, cin, cout);
-  size_t total = (size_t)kvol * cin * cout / 8;
-  hipLaunchKernelGGL(pack_weights_bf16_kernel, dim3(cdiv((long long)total, 256)), dim3(256), 0, stream, filters, kvol,
-                     cin, cout, (u32x4 *)packed);
-  DF3D_LAUNCH_CHECK();
-  return DF3D_OK;
+  return pack_filters(conv_format(1), "conv_pack_weights_bf16", filters, 1, kvol, cin, cout, packed, (hipStream_t)stream_);
 }
 
 extern "C" int df3d_sparse_conv_bf16(const void *features_bf16, int n_in, int cin, const void *packed_filters, int kvol,
                                      int cout, const int32_t *nbr, int n_out, const float *bias, const float *scale,
                                      const float *shift, const void *residual_bf16, int relu, float *out,
                                      void *out_bf16, void *stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  DF3D_CHECK_ARG(features_bf16 && packed_filters && nbr && (out || out_bf16), "sparse_conv_bf16: null argument");
-  DF3D_CHECK_ARG(kvol > 0 && kvol <= DF3D_MAX_KVOL, "sparse_conv_bf16: kernel volume %d unsupported", kvol);
-  DF3D_CHECK_ARG(bf16_shape_ok(cin, cout), "sparse_conv_bf16: cin=%d cout=%d has no bf16 kernel", cin, cout);
-  if (n_out == 0) return DF3D_OK;
-  SplitConvArgs a = {(const u32x4 *)features_bf16, (const u32x4 *)packed_filters, nbr, bias, scale, shift,
-                     (const float *)residual_bf16, out, (u32x4 *)out_bf16, n_in, n_out, kvol, relu, 0,
-                     cin / 8, 0, cout, cout > 128 ? cout / 128 : 1, nullptr};
-  int rec = timing_rec_begin(cin, cout, kvol, n_out, nbr, 2, stream);
-  int rc = launch_os_bf16_any(cin, cout, a, stream);
-  if (rc) return rc;
-  timing_rec_end(rec, stream);
-  DF3D_LAUNCH_CHECK();
-  return DF3D_OK;
+  return conv_launch(conv_format(1), "sparse_conv_bf16",
+                     ConvCall{features_bf16, n_in, cin, cin, 0, packed_filters, kvol, cout, 1, nbr, n_out, bias, scale, shift,
+                              residual_bf16, relu, out, cout, nullptr, out_bf16, nullptr, true},
+                     (hipStream_t)stream_);
 }

@@ -188,17 +188,11 @@ class BackbonePlan(object):
             keep.append(w)
             L.weight = w.data_ptr()
             L.packed = None
-            if _ops.CONV_PRECISION == "bf16" and _ops.conv_bf16_supported(K, c.in_channels, c.out_channels):
-                p = c._packed_weight_bf16(c.weight.detach(), K)
-                keep.append(p)
-                L.packed = p.data_ptr()
-                L.reserved |= 2                      # bf16 rows / weights for this layer
-            elif _ops.conv_split_supported(K, c.in_channels, c.out_channels):
-                p = c._packed_weight(c.weight.detach(), K)
-                keep.append(p)
-                L.packed = p.data_ptr()
-                if _ops.CONV_PRECISION == "split3":
-                    L.reserved |= 8                  # three-part rows / filters
+            filters = _ops.conv_filters(c, c.weight.detach(), K, c.in_channels, c.out_channels)
+            if filters.kind != "fp32":
+                keep.append(filters.packed)
+                L.packed = filters.packed.data_ptr()
+                L.reserved |= {"bf16": 2, "split": 0, "split3": 8}[filters.kind]       # ABI bits of df3d_layer.reserved
             if c.bias is not None:
                 L.bias = c.bias.detach().data_ptr()
             if s.bn is not None:
@@ -295,11 +289,11 @@ class BackbonePlan(object):
             t = SparseConvTensor(f, ind, [v.shape[0], v.shape[1], v.shape[2]], batch_size)
             t.indice_dict, t._directories = idict, dirs
             t._indices_synced = True      # the host has waited for these coordinates (count round trip)
-            if features and v.split and (v.reserved & 2):
-                t._bf16 = (f, view(v.split, v.n * v.channels * 2, torch.bfloat16, (v.n, v.channels)))
-            elif features and v.split:
-                pb = 6 if (v.reserved & 4) else 4
-                t._split = (f, view(v.split, v.n * v.channels * pb, torch.uint8, (v.n, v.channels * pb)))
+            if features and v.split:          # the operand rows the layer's kernel wrote next to (or instead of) the fp32 rows
+                kind = "bf16" if (v.reserved & 2) else ("split3" if (v.reserved & 4) else "split")
+                width = _ops.operand_width(kind, v.channels)
+                t.set_operand(kind, view(v.split, v.n * v.channels * 2 * _ops.FORMATS[kind].parts, _ops.FORMATS[kind].dtype,
+                                         (v.n, width)))
             if v.grid and v.rows_sorted:
                 # the occupancy directory the executor built is handed to the module path (e.g. a conv that runs
                 # after a fusion step): SparseConvTensor.directory() finds it by the identity of `indices`

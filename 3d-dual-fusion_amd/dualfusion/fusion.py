@@ -881,7 +881,7 @@ class VoxelWithPointProjection(nn.Module):
             _lib.check(rc, "df3d_fusion_writeback_split")
             y = x_last.replace_feature(out)
             if osplit is not None:
-                y._split = (out, osplit)
+                y.set_operand("split", osplit)
             return y
         rc = lib.df3d_fusion_writeback(_p(feats), _p(enh), _p(ind), _p(mask), _p(pos), n, C, ncam, max_ne, _p(out),
                                        _ops._stream())

@@ -99,10 +99,7 @@ class _Layer(object):
             self.filters = w.permute(2, 3, 0, 1).reshape(-1, w.shape[0], w.shape[1]).contiguous()
         else:                                # [cout, cin, kh, kw] -> [kh*kw, cin, cout]
             self.filters = w.permute(2, 3, 1, 0).reshape(-1, w.shape[1], w.shape[0]).contiguous()
-        K, cin, cout = self.filters.shape
-        self.packed = _ops.conv_pack_weights(self.filters) if _ops.conv_split_supported(K, cin, cout) else None
-        self.packed16 = (_ops.conv_pack_weights_bf16(self.filters)
-                         if _ops.CONV_PRECISION == "bf16" and _ops.conv_bf16_supported(K, cin, cout) else None)
+        self.weights = _ops.ConvFilters(self.filters)      # packed for the arithmetic the mode gives this shape (`.kind`)
         inv = torch.rsqrt(self.bn.running_var.float() + self.bn.eps)
         self.scale = (self.bn.weight.float() * inv).contiguous()
         self.shift = (self.bn.bias.float() - self.bn.running_mean.float() * self.scale).contiguous()
@@ -225,7 +222,7 @@ class RPN(nn.Module):
             return False
         layer, pad = plan["blocks"][0][0]
         layer.prepare(pad)
-        return layer.packed is not None and layer.packed16 is None
+        return layer.weights.kind == "split"
 
     @staticmethod
     def _cat_width(plan):
@@ -236,33 +233,17 @@ class RPN(nn.Module):
             for layer, pad in lasts:
                 layer.prepare(pad)
             ok = (len(lasts) > 1 and len(lasts) == len(plan["deblocks"]) and os.environ.get("DF3D_NECK_CAT", "1") != "0"
-                  and os.environ.get("DF3D_SPLIT_KERNEL", "o")[:1] != "p"
-                  and all(l.packed is not None and l.packed16 is None and l.filters.shape[2] % 8 == 0 for l, _ in lasts))
+                  and all(l.weights.kind in ("split", "split3") and l.filters.shape[2] % 8 == 0 for l, _ in lasts))
             plan["cat"] = (_ops.CONV_PRECISION, sum(l.filters.shape[2] for l, _ in lasts) if ok else 0)
         return plan["cat"][1]
 
     @staticmethod
     def _run(layer, pad, rows, split, B, H, W, tables):
         nbr, Ho, Wo = RPN._table(layer, pad, B, H, W, tables, rows.device)
-        K, cin, cout = layer.filters.shape
-        n_out = nbr.shape[1]
-        if layer.packed16 is not None:                       # DF3D_CONV_PRECISION=bf16: bf16 rows from layer to layer
-            r16 = split if (split is not None and split.dtype == torch.bfloat16) else _ops.rows_to_bf16(rows)
-            out, o16 = _ops.sparse_conv_bf16(r16, layer.packed16, nbr, n_out, cin, cout, bias=layer.bias,
-                                             scale=layer.scale, shift=layer.shift, relu=layer.relu, want_f32=True)
-            return out, o16, Ho, Wo
-        if split is not None and split.dtype == torch.bfloat16:
-            split = None
-        if layer.packed is not None:
-            if split is None:
-                split = _ops.split_rows(rows)
-            out, osplit = _ops.sparse_conv_split(split, layer.packed, nbr, n_out, cin, cout, bias=layer.bias,
-                                                 scale=layer.scale, shift=layer.shift, relu=layer.relu)
-        else:
-            out = _ops.sparse_conv_fused(rows, layer.filters, nbr, n_out, bias=layer.bias, scale=layer.scale,
-                                         shift=layer.shift, relu=layer.relu)
-            osplit = None
-        return out, osplit, Ho, Wo
+        # `split`: the operand rows the previous layer wrote, used when they are in this layer's format
+        out, orows = _ops.conv(layer.weights, nbr, nbr.shape[1], rows=rows, operand=split, bias=layer.bias, scale=layer.scale,
+                               shift=layer.shift, relu=layer.relu)
+        return out, orows, Ho, Wo
 
     @torch.no_grad()
     def forward_rows(self, rows, B, H, W):
@@ -291,7 +272,7 @@ class RPN(nn.Module):
                         cat_rows = torch.empty((nbr.shape[1], cat), dtype=torch.float32, device=x.device)
                         cat_split = torch.empty((nbr.shape[1], _ops.split_width(cat)), dtype=torch.uint8, device=x.device)
                     K, cin, cout = layer.filters.shape
-                    _ops.conv_rows_split(us if us is not None else _ops.split_rows(u), cin, 0, layer.packed, cout, 1, nbr,
+                    _ops.conv_rows_split(us if us is not None else _ops.split_rows(u), cin, 0, layer.weights.packed, cout, 1, nbr,
                                          nbr.shape[1], layer.bias, layer.scale, layer.shift, layer.relu,
                                          into=(cat_rows, cat_split, col0))
                     col0 += cout

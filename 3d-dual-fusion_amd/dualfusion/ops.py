@@ -4,6 +4,7 @@ PyTorch supplies device memory and the current HIP stream; all arithmetic happen
 libdf3d_hip.so.  Inputs must be contiguous tensors on one GPU, as the reference's bindings
 require (ms_deform_attn_cuda.cu:28-38).  Nothing here falls back to the CPU.
 """
+import collections
 import ctypes
 import os
 
@@ -354,15 +355,11 @@ class KernelTimer(object):
 
 
 def conv_tiles(nbr, cin, cout):
-    """Pair-balanced row ranges for the compute-bound conv kernel (None when not applicable)."""
+    """Pair-balanced row ranges for the exact-fp32 pair kernel (cout 128, cin 64 | 128), the only kernel that consumes them;
+    None for every other shape."""
     lib = _lib.load()
     K, n_out = nbr.shape
-    # only the pair-compacted kernels consume the ranges: the fp32 kernel for cout 128, or the split-precision
-    # pair kernel when DF3D_SPLIT_KERNEL=pair selects it; the output-stationary split kernel cuts equal tiles
-    if conv_split_supported(K, cin, cout):
-        if not os.environ.get("DF3D_SPLIT_KERNEL", "").startswith("p"):
-            return None
-    elif not (int(cout) == 128 and int(cin) in (64, 128)):
+    if not (int(cout) == 128 and int(cin) in (64, 128)):
         return None
     nt = lib.df3d_conv_tile_count(int(n_out), int(cin), int(cout), int(K))
     if nt <= 0 or n_out == 0:
@@ -442,7 +439,7 @@ def sparse_conv_fused(features, filters, nbr, n_out, bias=None, scale=None, shif
     return out
 
 
-# ---- split-precision convolution (csrc/spconv_split.hip) --------------------------------------------------
+# ---- convolution arithmetic (csrc/spconv_split.hip) -------------------------------------------------------
 # "split": C >= 32 layers run on the 16-bit matrix cores with fp32 operands split into fp16 hi + lo (csrc/common.h; round 5:
 #          22 significand bits, ~1e-6 of the output scale against float64 = the grade of the exact-fp32 kernels; operands
 #          must stay inside fp16's range after a fixed scaling -- |activation| < 2047, |filter| < 511 --, which every
@@ -452,26 +449,8 @@ def sparse_conv_fused(features, filters, nbr, n_out, bias=None, scale=None, shif
 #          fp32-grade results with fp32's exponent range at twice the matrix work of "split".  The functions below (`split_rows`, `conv_pack_weights`,
 #          `sparse_conv_split`, `conv_rows_split`) then produce / consume three-part buffers: their callers treat split rows
 #          and packed filters as opaque, so the sparse backbone, the BEV neck and the head run on it unchanged.
+# "bf16":  bf16 rows and filters, fp32 accumulate (BASELINE configs[2]).
 CONV_PRECISION = os.environ.get("DF3D_CONV_PRECISION", "split")
-
-
-class precision(object):
-    """`with precision("split"): ...` -- the convolution arithmetic of the calls inside (the TransFusion head keeps its own
-    convolutions fp32-grade while backbone and neck run bf16: BASELINE configs[2] / [3])."""
-
-    def __init__(self, mode):
-        self.mode = mode
-
-    def __enter__(self):
-        global CONV_PRECISION
-        self.old, CONV_PRECISION = CONV_PRECISION, self.mode
-        return self
-
-    def __exit__(self, *exc):
-        global CONV_PRECISION
-        CONV_PRECISION = self.old
-        return False
-
 
 # True inside `reference_arithmetic()`: every matrix product of the hot path in plain fp32 -- the convolutions on the exact-fp32
 # MFMA kernels (CONV_PRECISION "fp32"), the feed-forward blocks / query linears / image projection / value GEMM on the library's
@@ -480,11 +459,13 @@ class precision(object):
 ALL_FP32 = False
 
 
-class reference_arithmetic(object):
+class _Arithmetic(object):
+    """`with ...:` -- (CONV_PRECISION, ALL_FP32) of the calls inside; `_inside(precision, all_fp32)` says what they become."""
+
     def __enter__(self):
         global CONV_PRECISION, ALL_FP32
         self.old = (CONV_PRECISION, ALL_FP32)
-        CONV_PRECISION, ALL_FP32 = "fp32", True
+        CONV_PRECISION, ALL_FP32 = self._inside(*self.old)
         return self
 
     def __exit__(self, *exc):
@@ -493,95 +474,148 @@ class reference_arithmetic(object):
         return False
 
 
-class grad_precision(object):
+class precision(_Arithmetic):
+    """`with precision("split"): ...` -- the convolution arithmetic of the calls inside (the TransFusion head keeps its own
+    convolutions fp32-grade while backbone and neck run bf16: BASELINE configs[2] / [3])."""
+
+    def __init__(self, mode):
+        self.mode = mode
+
+    def _inside(self, mode, all_fp32):
+        return self.mode, all_fp32
+
+
+class reference_arithmetic(_Arithmetic):
+    def _inside(self, mode, all_fp32):
+        return "fp32", True
+
+
+class grad_precision(_Arithmetic):
     """Context of a backward pass: gradient rows have no fixed scale (1e-8 .. 1e+2 within one step), which the fp16 parts of
     the "split" mode cannot hold -- input-gradient convolutions run in the three-part mode (bf16 parts: fp32's exponent range)."""
 
-    def __enter__(self):
-        global CONV_PRECISION
-        self.old = CONV_PRECISION
-        if CONV_PRECISION == "split":
-            CONV_PRECISION = "split3"
-        return self
+    def _inside(self, mode, all_fp32):
+        return ("split3" if mode == "split" else mode), all_fp32
 
-    def __exit__(self, *exc):
-        global CONV_PRECISION
-        CONV_PRECISION = self.old
-        return False
+
+# The operand formats of the matrix-core kernels, by the mode that selects them: 16-bit parts per value (rows and packed filters
+# hold 2 * parts bytes per channel), the dtype their rows travel as, and the library entries: size query (0 = no kernel for the
+# shape), filter packing (one bank / G banks), row conversion, sparse convolution, grouped row convolution.  The shapes each
+# format serves are listed once, in csrc/spconv_split.hip (DF3D_CONV_SHAPES).  The exported entries differ in their argument
+# lists (the ABI is frozen), so each call site below spells out its own call: `conv` is the name of the entry `_conv_operands`
+# calls for the format (its label in error texts), _PACK_TAKES_GROUPS names the packing entries that take a bank count,
+# and only the three-part `conv_rows` entry has a residual parameter.
+_Format = collections.namedtuple("_Format", "parts dtype packed_bytes pack pack_groups rows conv conv_rows")
+FORMATS = {
+    "bf16": _Format(1, torch.bfloat16, "df3d_conv_packed_weight_bytes_bf16", "df3d_conv_pack_weights_bf16", None,
+                    "df3d_rows_to_bf16", "df3d_sparse_conv_bf16", None),
+    "split": _Format(2, torch.uint8, "df3d_conv_packed_weight_bytes", "df3d_conv_pack_weights", "df3d_conv_pack_weights_groups",
+                     "df3d_split_rows", "df3d_sparse_conv_split", "df3d_conv_rows_split"),
+    "split3": _Format(3, torch.uint8, "df3d_conv_packed_weight_bytes3", "df3d_conv_pack_weights3", "df3d_conv_pack_weights3",
+                      "df3d_split_rows3", "df3d_conv_rows_split3", "df3d_conv_rows_split3"),
+}
+_PACK_TAKES_GROUPS = ("df3d_conv_pack_weights_groups", "df3d_conv_pack_weights3")
+
+
+def split_kind():
+    """The format the `split_*` / `conv_*_split` wrappers work in: three parts in the "split3" mode, two otherwise."""
+    return "split3" if CONV_PRECISION == "split3" else "split"
+
+
+def operand_width(kind, channels):
+    """Elements (of the format's dtype) per operand row of a `channels`-wide map."""
+    fmt = FORMATS[kind]
+    return 2 * fmt.parts * int(channels) // fmt.dtype.itemsize
 
 
 def split_parts():
     """16-bit parts per value of the split rows / packed filters of the current precision mode."""
-    return 3 if CONV_PRECISION == "split3" else 2
+    return FORMATS[split_kind()].parts
 
 
 def split_width(channels):
     """Bytes per row of the split rows of a `channels`-wide map in the current precision mode."""
-    return 2 * split_parts() * int(channels)
+    return operand_width(split_kind(), channels)
+
+
+def conv_kind(kvol, cin, cout):
+    """The arithmetic a (kvol, cin, cout) convolution runs in under the current mode: "bf16" | "split" | "split3" where that
+    format has a kernel for the shape, else "fp32" (the exact-fp32 kernels).  The one place that combines the mode with the
+    shape tables."""
+    fmt = FORMATS.get(CONV_PRECISION)
+    if fmt is not None and getattr(_lib.load(), fmt.packed_bytes)(int(kvol), int(cin), int(cout)) > 0:
+        return CONV_PRECISION
+    return "fp32"
 
 
 def conv_split_supported(kvol, cin, cout):
-    if CONV_PRECISION == "split3":
-        return _lib.load().df3d_conv_packed_weight_bytes3(int(kvol), int(cin), int(cout)) > 0
-    if CONV_PRECISION != "split":
-        return False
-    return _lib.load().df3d_conv_packed_weight_bytes(int(kvol), int(cin), int(cout)) > 0
+    return CONV_PRECISION in ("split", "split3") and conv_kind(kvol, cin, cout) != "fp32"
+
+
+def conv_bf16_supported(kvol, cin, cout):
+    return _lib.load().df3d_conv_packed_weight_bytes_bf16(int(kvol), int(cin), int(cout)) > 0
+
+
+def _pack_filters(kind, filters, grouped=False):
+    """filters [K, cin, cout] (grouped: [G, K, cin, cout], cout <= 128, banks back to back) fp32 -> packed operands of `kind`."""
+    lib = _lib.load()
+    fmt = FORMATS[kind]
+    _chk(filters, torch.float32, "filters")
+    G = filters.shape[0] if grouped else 1
+    K, cin, cout = filters.shape[-3:]
+    entry = fmt.pack_groups if grouped else fmt.pack
+    nbytes = getattr(lib, fmt.packed_bytes)(K, cin, cout)
+    if entry is None or nbytes == 0 or (grouped and cout > 128):
+        raise _lib.Df3dError("no %s%s kernel for K=%d cin=%d cout=%d" % ("grouped " if grouped else "", kind, K, cin, cout))
+    packed = torch.empty((G * nbytes,), dtype=torch.uint8, device=filters.device)
+    args = (_ptr(filters),) + ((G,) if entry in _PACK_TAKES_GROUPS else ()) + (K, cin, cout, _ptr(packed), _stream())
+    _lib.check(getattr(lib, entry)(*args), entry)
+    return packed
 
 
 def conv_pack_weights(filters):
-    """filters [K, cin, cout] fp32 -> packed hi/lo bf16 MFMA operands (uint8 buffer)."""
-    lib = _lib.load()
-    _chk(filters, torch.float32, "filters")
-    K, cin, cout = filters.shape
-    if CONV_PRECISION == "split3":
-        nbytes = lib.df3d_conv_packed_weight_bytes3(K, cin, cout)
-        if nbytes == 0:
-            raise _lib.Df3dError("no three-part kernel for K=%d cin=%d cout=%d" % (K, cin, cout))
-        packed = torch.empty((nbytes,), dtype=torch.uint8, device=filters.device)
-        _lib.check(lib.df3d_conv_pack_weights3(_ptr(filters), 1, K, cin, cout, _ptr(packed), _stream()), "df3d_conv_pack_weights3")
-        return packed
-    nbytes = lib.df3d_conv_packed_weight_bytes(K, cin, cout)
-    if nbytes == 0:
-        raise _lib.Df3dError("no split-precision kernel for K=%d cin=%d cout=%d" % (K, cin, cout))
-    packed = torch.empty((nbytes,), dtype=torch.uint8, device=filters.device)
-    rc = lib.df3d_conv_pack_weights(_ptr(filters), K, cin, cout, _ptr(packed), _stream())
-    _lib.check(rc, "df3d_conv_pack_weights")
-    return packed
+    """filters [K, cin, cout] fp32 -> packed MFMA operands of the split mode in force (uint8 buffer)."""
+    return _pack_filters(split_kind(), filters)
 
 
 def conv_pack_weights_groups(filters):
     """filters [G, K, cin, cout] fp32 (cout <= 128) -> the G packed banks back to back (what `conv_rows_split` takes)."""
+    return _pack_filters(split_kind(), filters, grouped=True)
+
+
+def conv_pack_weights_bf16(filters):
+    """filters [K, cin, cout] fp32 -> packed bf16 MFMA operands (uint8 buffer)."""
+    return _pack_filters("bf16", filters)
+
+
+def operand_rows(kind, features):
+    """features [n, c] fp32 -> their operand rows in the format `kind` ([n, operand_width(kind, c)] of the format's dtype)."""
     lib = _lib.load()
-    _chk(filters, torch.float32, "filters")
-    G, K, cin, cout = filters.shape
-    if CONV_PRECISION == "split3":
-        nbytes = lib.df3d_conv_packed_weight_bytes3(K, cin, cout)
-        if nbytes == 0 or cout > 128:
-            raise _lib.Df3dError("no grouped three-part kernel for K=%d cin=%d cout=%d" % (K, cin, cout))
-        packed = torch.empty((G * nbytes,), dtype=torch.uint8, device=filters.device)
-        _lib.check(lib.df3d_conv_pack_weights3(_ptr(filters), G, K, cin, cout, _ptr(packed), _stream()), "df3d_conv_pack_weights3")
-        return packed
-    nbytes = lib.df3d_conv_packed_weight_bytes(K, cin, cout)
-    if nbytes == 0 or cout > 128:
-        raise _lib.Df3dError("no grouped split-precision kernel for K=%d cin=%d cout=%d" % (K, cin, cout))
-    packed = torch.empty((G * nbytes,), dtype=torch.uint8, device=filters.device)
-    rc = lib.df3d_conv_pack_weights_groups(_ptr(filters), G, K, cin, cout, _ptr(packed), _stream())
-    _lib.check(rc, "df3d_conv_pack_weights_groups")
-    return packed
+    fmt = FORMATS[kind]
+    _chk(features, torch.float32, "features")
+    n, c = features.shape
+    out = torch.empty((n, operand_width(kind, c)), dtype=fmt.dtype, device=features.device)
+    _lib.check(getattr(lib, fmt.rows)(_ptr(features), n, c, _ptr(out), _stream()), fmt.rows)
+    return out
 
 
 def split_rows(features):
-    """features [n, c] fp32 -> split rows (uint8 [n, 4c]: per 8 channels 16 B of bf16 hi, 16 B of bf16 lo)."""
+    """features [n, c] fp32 -> split rows (uint8 [n, 4c]: per 8 channels 16 B of fp16 hi, 16 B of fp16 lo; [n, 6c] in the
+    "split3" mode)."""
+    return operand_rows(split_kind(), features)
+
+
+def rows_to_bf16(features):
+    """fp32 [n, c] -> torch.bfloat16 [n, c] (round to nearest even)."""
+    return operand_rows("bf16", features)
+
+
+def rows_from_bf16(rows):
     lib = _lib.load()
-    _chk(features, torch.float32, "features")
-    n, c = features.shape
-    if CONV_PRECISION == "split3":
-        out = torch.empty((n, 6 * c), dtype=torch.uint8, device=features.device)
-        _lib.check(lib.df3d_split_rows3(_ptr(features), n, c, _ptr(out), _stream()), "df3d_split_rows3")
-        return out
-    out = torch.empty((n, 4 * c), dtype=torch.uint8, device=features.device)
-    rc = lib.df3d_split_rows(_ptr(features), n, c, _ptr(out), _stream())
-    _lib.check(rc, "df3d_split_rows")
+    _chk(rows, torch.bfloat16, "rows")
+    n, c = rows.shape
+    out = torch.empty((n, c), dtype=torch.float32, device=rows.device)
+    _lib.check(lib.df3d_rows_from_bf16(_ptr(rows), n, c, _ptr(out), _stream()), "df3d_rows_from_bf16")
     return out
 
 
@@ -600,101 +634,110 @@ def split_rows_scaled(features, inv_channels):
     return out, inv, scale
 
 
-def sparse_conv_split(features_split, packed, nbr, n_out, cin, cout, bias=None, scale=None, shift=None,
-                      residual=None, relu=False, tiles=None, emit_split=True, order=None):
-    """Split-precision twin of sparse_conv_fused.  Returns (out fp32 [n_out, cout], split rows of out or None).
-    order: optional int32 [n_out] tiling order of the output-stationary kernel (which rows share a workgroup tile)."""
+def _conv_operands(kind, rows, packed, nbr, n_out, cin, cout, bias, scale, shift, residual, relu, want_f32, want_rows,
+                   order=None):
+    """The fused sparse convolution on operand rows / packed filters of `kind`; residual in the form the kernel reads (bf16
+    rows for "bf16", fp32 rows otherwise).  -> (out fp32 [n_out, cout] or None, operand rows of out or None)."""
     lib = _lib.load()
-    _chk(features_split, torch.uint8, "features_split")
+    fmt = FORMATS[kind]
+    _chk(rows, fmt.dtype, "operand rows")
     _chk(packed, torch.uint8, "packed")
     _chk(nbr, torch.int32, "nbr")
-    n_in = features_split.shape[0]
     K = nbr.shape[0]
-    pb = 2 * split_parts()
-    if features_split.shape[1] != pb * cin or packed.numel() != K * cin * cout * pb:
-        raise _lib.Df3dError("split operands do not match K=%d cin=%d cout=%d (%d parts)" % (K, cin, cout, split_parts()))
-    for t, nm in ((bias, "bias"), (scale, "scale"), (shift, "shift"), (residual, "residual")):
+    if rows.shape[1] != operand_width(kind, cin) or packed.numel() != K * cin * cout * 2 * fmt.parts:
+        raise _lib.Df3dError("%s operands do not match K=%d cin=%d cout=%d" % (kind, K, cin, cout))
+    for t, nm in ((bias, "bias"), (scale, "scale"), (shift, "shift")):
         if t is not None:
             _chk(t, torch.float32, nm)
-    out = torch.empty((n_out, cout), dtype=torch.float32, device=nbr.device)
-    if CONV_PRECISION == "split3":
-        out_split = torch.empty((n_out, 6 * cout), dtype=torch.uint8, device=nbr.device) if emit_split else None
-        rc = lib.df3d_conv_rows_split3(_ptr(features_split), n_in, cin, cin, 0, _ptr(packed), K, cout, 1, _ptr(nbr), n_out,
-                                       _ptr(bias), _ptr(scale), _ptr(shift), _ptr(residual), int(bool(relu)), _ptr(out), cout,
-                                       None, _ptr(out_split), _stream())
-        _lib.check(rc, "df3d_conv_rows_split3")
-        return out, out_split
-    out_split = torch.empty((n_out, 4 * cout), dtype=torch.uint8, device=nbr.device) if emit_split else None
-    rc = lib.df3d_sparse_conv_split(_ptr(features_split), n_in, cin, _ptr(packed), K, cout, _ptr(nbr), n_out,
-                                    _ptr(bias), _ptr(scale), _ptr(shift), _ptr(residual), int(bool(relu)), _ptr(out),
-                                    _ptr(out_split), _ptr(order if order is not None else tiles),
-                                    -1 if order is not None else ((tiles.shape[0] - 1) if tiles is not None else 0),
-                                    _stream())
-    _lib.check(rc, "df3d_sparse_conv_split")
-    return out, out_split
+    if residual is not None:
+        _chk(residual, torch.bfloat16 if kind == "bf16" else torch.float32, "residual")
+    dev = nbr.device
+    out = torch.empty((n_out, cout), dtype=torch.float32, device=dev) if want_f32 else None
+    orows = torch.empty((n_out, operand_width(kind, cout)), dtype=fmt.dtype, device=dev) if want_rows else None
+    head = (_ptr(rows), rows.shape[0], cin)
+    epilogue = (_ptr(bias), _ptr(scale), _ptr(shift), _ptr(residual), int(bool(relu)))
+    if kind == "bf16":
+        rc = lib.df3d_sparse_conv_bf16(*head, _ptr(packed), K, cout, _ptr(nbr), int(n_out), *epilogue, _ptr(out), _ptr(orows),
+                                       _stream())
+    elif kind == "split":
+        rc = lib.df3d_sparse_conv_split(*head, _ptr(packed), K, cout, _ptr(nbr), int(n_out), *epilogue, _ptr(out), _ptr(orows),
+                                        _ptr(order), -1 if order is not None else 0, _stream())
+    else:                                   # the grouped three-part entry with one group
+        rc = lib.df3d_conv_rows_split3(*head, cin, 0, _ptr(packed), K, cout, 1, _ptr(nbr), int(n_out), *epilogue, _ptr(out), cout,
+                                       None, _ptr(orows), _stream())
+    _lib.check(rc, fmt.conv)
+    return out, orows
 
 
-# ---- bf16 rows / bf16 weights (BASELINE configs[2]: bf16 with fp32 accumulate) ------------------------------------
-def conv_bf16_supported(kvol, cin, cout):
-    return _lib.load().df3d_conv_packed_weight_bytes_bf16(int(kvol), int(cin), int(cout)) > 0
-
-
-def rows_to_bf16(features):
-    """fp32 [n, c] -> torch.bfloat16 [n, c] (round to nearest even)."""
-    lib = _lib.load()
-    _chk(features, torch.float32, "features")
-    n, c = features.shape
-    out = torch.empty((n, c), dtype=torch.bfloat16, device=features.device)
-    _lib.check(lib.df3d_rows_to_bf16(_ptr(features), n, c, _ptr(out), _stream()), "df3d_rows_to_bf16")
-    return out
-
-
-def rows_from_bf16(rows):
-    lib = _lib.load()
-    _chk(rows, torch.bfloat16, "rows")
-    n, c = rows.shape
-    out = torch.empty((n, c), dtype=torch.float32, device=rows.device)
-    _lib.check(lib.df3d_rows_from_bf16(_ptr(rows), n, c, _ptr(out), _stream()), "df3d_rows_from_bf16")
-    return out
-
-
-def conv_pack_weights_bf16(filters):
-    """filters [K, cin, cout] fp32 -> packed bf16 MFMA operands (uint8 buffer)."""
-    lib = _lib.load()
-    _chk(filters, torch.float32, "filters")
-    K, cin, cout = filters.shape
-    nbytes = lib.df3d_conv_packed_weight_bytes_bf16(K, cin, cout)
-    if nbytes == 0:
-        raise _lib.Df3dError("no bf16 conv kernel for K=%d cin=%d cout=%d" % (K, cin, cout))
-    packed = torch.empty((nbytes,), dtype=torch.uint8, device=filters.device)
-    _lib.check(lib.df3d_conv_pack_weights_bf16(_ptr(filters), K, cin, cout, _ptr(packed), _stream()),
-               "df3d_conv_pack_weights_bf16")
-    return packed
+def sparse_conv_split(features_split, packed, nbr, n_out, cin, cout, bias=None, scale=None, shift=None,
+                      residual=None, relu=False, emit_split=True, order=None):
+    """Split-precision twin of sparse_conv_fused.  Returns (out fp32 [n_out, cout], split rows of out or None).
+    order: optional int32 [n_out] tiling order of the output-stationary kernel (which rows share a workgroup tile)."""
+    return _conv_operands(split_kind(), features_split, packed, nbr, n_out, cin, cout, bias, scale, shift, residual, relu,
+                          True, emit_split, order)
 
 
 def sparse_conv_bf16(rows, packed, nbr, n_out, cin, cout, bias=None, scale=None, shift=None, residual=None, relu=False,
                      want_f32=False, want_bf16=True):
     """bf16 twin of sparse_conv_fused: rows / residual torch.bfloat16 [n, c]; -> (out fp32 or None, out bf16 or None)."""
-    lib = _lib.load()
-    _chk(rows, torch.bfloat16, "rows")
-    _chk(packed, torch.uint8, "packed")
-    _chk(nbr, torch.int32, "nbr")
-    K = nbr.shape[0]
-    if rows.shape[1] != cin or packed.numel() != K * cin * cout * 2:
-        raise _lib.Df3dError("bf16 operands do not match K=%d cin=%d cout=%d" % (K, cin, cout))
-    for t, nm in ((bias, "bias"), (scale, "scale"), (shift, "shift")):
-        if t is not None:
-            _chk(t, torch.float32, nm)
-    if residual is not None:
-        _chk(residual, torch.bfloat16, "residual")
-    dev = nbr.device
-    out = torch.empty((n_out, cout), dtype=torch.float32, device=dev) if want_f32 else None
-    ob = torch.empty((n_out, cout), dtype=torch.bfloat16, device=dev) if want_bf16 else None
-    rc = lib.df3d_sparse_conv_bf16(_ptr(rows), rows.shape[0], cin, _ptr(packed), K, cout, _ptr(nbr), int(n_out),
-                                   _ptr(bias), _ptr(scale), _ptr(shift), _ptr(residual), int(bool(relu)), _ptr(out),
-                                   _ptr(ob), _stream())
-    _lib.check(rc, "df3d_sparse_conv_bf16")
-    return out, ob
+    return _conv_operands("bf16", rows, packed, nbr, n_out, cin, cout, bias, scale, shift, residual, relu, want_f32, want_bf16)
+
+
+# ---- the dispatch: which arithmetic a layer runs in, what its operands look like, how it is launched -----------------------
+class ConvFilters(object):
+    """[K, cin, cout] fp32 filters and their operand image, tagged with the kind (`conv_kind`) they were packed for."""
+    __slots__ = ("filters", "kind", "packed")
+
+    def __init__(self, filters, kind=None):
+        K, cin, cout = filters.shape
+        self.filters = filters
+        self.kind = conv_kind(K, cin, cout) if kind is None else kind
+        self.packed = _pack_filters(self.kind, filters) if self.kind != "fp32" else None
+
+
+def conv_filters(owner, weight, kvol, cin, cout):
+    """The ConvFilters of `weight` ([..., cin, cout] in any kernel shape) for the current mode, kept in `owner.__dict__` and
+    rebuilt when the parameter (address, version, device) or the kind changes; one slot per kind."""
+    kind = conv_kind(kvol, cin, cout)
+    key = (weight.data_ptr(), weight._version, str(weight.device), kind)
+    cache = owner.__dict__.setdefault("_conv_filters", {})
+    hit = cache.get(kind)
+    if hit is None or hit[0] != key:
+        hit = cache[kind] = (key, ConvFilters(weight.detach().contiguous().float().view(kvol, cin, cout), kind))
+    return hit[1]
+
+
+def is_operand(kind, rows, channels):
+    """True when `rows` are operand rows of `kind` for a `channels`-wide map."""
+    fmt = FORMATS.get(kind)
+    return (fmt is not None and isinstance(rows, torch.Tensor) and rows.dtype == fmt.dtype and rows.dim() == 2
+            and rows.shape[1] == operand_width(kind, channels))
+
+
+def conv(filters, nbr, n_out, rows=None, operand=None, bias=None, scale=None, shift=None, residual=None, relu=False,
+         want_f32=True, want_operand=True, tiles=None, order=None):
+    """out = act((conv(x) + bias) * scale + shift + residual) in the arithmetic `filters` (ConvFilters) were packed for.
+    x comes as fp32 `rows` and / or as `operand` rows; the operand rows are converted here only when the caller has none of
+    the filters' kind.  residual: fp32 rows (bf16 rows are taken as they are by the bf16 kernel).  tiles: row ranges of the
+    exact-fp32 pair kernel (`conv_tiles`); order: tiling order of the two-part kernel.
+    -> (fp32 rows or None, operand rows of the result or None); the exact-fp32 and the split kernels always write fp32 rows."""
+    kind = filters.kind
+    K, cin, cout = filters.filters.shape
+    if kind == "fp32":
+        return sparse_conv_fused(rows, filters.filters, nbr, n_out, bias=bias, scale=scale, shift=shift, residual=residual,
+                                 relu=relu, tiles=tiles), None
+    if kind != CONV_PRECISION:
+        raise _lib.Df3dError("conv: filters packed for %r cannot run in the %r mode; pack them again (conv_filters does)"
+                             % (kind, CONV_PRECISION))
+    if not is_operand(kind, operand, cin):
+        operand = operand_rows(kind, rows)
+    if kind == "bf16":
+        if residual is not None and residual.dtype != torch.bfloat16:
+            residual = rows_to_bf16(residual.contiguous().float())
+        return _conv_operands(kind, operand, filters.packed, nbr, n_out, cin, cout, bias, scale, shift, residual, relu,
+                              want_f32, want_operand)
+    return _conv_operands(kind, operand, filters.packed, nbr, n_out, cin, cout, bias, scale, shift, residual, relu, True,
+                          want_operand, order)
 
 
 def invert_neighbors(nbr, n_in):
@@ -807,19 +850,23 @@ def sparse_conv_backward(features, filters, grad_out, nbr, subm, inv=None, bf16=
         blocks = wt.view(K, cout, cin // 128, 128).permute(2, 0, 1, 3).contiguous()
         g_in, _ = conv_rows_split(gs, cout, 0, conv_pack_weights_groups(blocks), 128, cin // 128, inv, n_in, scale=inv_s)
         return g_in, sparse_conv_grad_filters(features.contiguous(), grad_out, nbr, grad_scale=sc)
-    with grad_precision():
-        if bf16 and conv_bf16_supported(K, cout, cin):
-            g_in, _ = sparse_conv_bf16(rows_to_bf16(grad_out), conv_pack_weights_bf16(wt), inv, n_in, cout, cin, want_f32=True,
-                                       want_bf16=False)
-        elif conv_split_supported(K, cout, cin):
-            g_in, _ = sparse_conv_split(split_rows(grad_out), conv_pack_weights(wt), inv, n_in, cout, cin, emit_split=False)
-        elif cin > 128 and cin % 128 == 0 and conv_split_supported(K, cout, 128):
+    # the transposed shape in the arithmetic of the gradient mode -- except that the bf16 kernel is the forward's choice
+    # (`bf16`, whatever the mode), never this function's own: without it the bf16 mode runs the exact-fp32 kernel
+    if bf16 and conv_bf16_supported(K, cout, cin):
+        mode = precision("bf16")
+    elif CONV_PRECISION == "bf16":
+        mode = precision("fp32")
+    else:
+        mode = grad_precision()
+    with mode:
+        w = ConvFilters(wt)
+        if w.kind == "fp32" and cin > 128 and cin % 128 == 0 and conv_split_supported(K, cout, 128):
             # many input channels (the head's shared conv 512 -> 64, transposed): 128-column blocks of one grouped launch
             blocks = wt.view(K, cout, cin // 128, 128).permute(2, 0, 1, 3).contiguous()
             g_in, _ = conv_rows_split(split_rows(grad_out), cout, 0, conv_pack_weights_groups(blocks), 128, cin // 128, inv,
                                       n_in)
         else:
-            g_in = sparse_conv_fused(grad_out, wt, inv, n_in)
+            g_in, _ = conv(w, inv, n_in, rows=grad_out, want_operand=False)
     return g_in, sparse_conv_grad_filters(features.contiguous(), grad_out, nbr, bf16=bf16)
 
 
@@ -834,8 +881,8 @@ def conv_rows_split(in_split, cin, in_group_stride, packed, cout, groups, nbr, n
     _chk(in_split, torch.uint8, "in_split")
     _chk(packed, torch.uint8, "packed")
     _chk(nbr, torch.int32, "nbr")
-    p3 = CONV_PRECISION == "split3"
-    pb = 6 if p3 else 4
+    fmt = FORMATS[split_kind()]
+    pb = 2 * fmt.parts
     n_in, in_channels = in_split.shape[0], in_split.shape[1] // pb
     K = nbr.shape[0]
     if packed.numel() != groups * K * cin * cout * pb or in_split.shape[1] != pb * in_channels:
@@ -846,16 +893,11 @@ def conv_rows_split(in_split, cin, in_group_stride, packed, cout, groups, nbr, n
     dev = in_split.device
 
     def launch(po, oc, pcols, ps):
-        if p3:
-            rc = lib.df3d_conv_rows_split3(_ptr(in_split), n_in, in_channels, int(cin), int(in_group_stride), _ptr(packed), K,
-                                           int(cout), int(groups), _ptr(nbr), int(n_out), _ptr(bias), _ptr(scale),
-                                           _ptr(shift), None, int(bool(relu)), po, oc, pcols, ps, _stream())
-            _lib.check(rc, "df3d_conv_rows_split3")
-        else:
-            rc = lib.df3d_conv_rows_split(_ptr(in_split), n_in, in_channels, int(cin), int(in_group_stride), _ptr(packed), K,
-                                          int(cout), int(groups), _ptr(nbr), int(n_out), _ptr(bias), _ptr(scale),
-                                          _ptr(shift), int(bool(relu)), po, oc, pcols, ps, _stream())
-            _lib.check(rc, "df3d_conv_rows_split")
+        residual = (None,) if fmt.parts == 3 else ()          # (only the three-part entry has the parameter)
+        rc = getattr(lib, fmt.conv_rows)(_ptr(in_split), n_in, in_channels, int(cin), int(in_group_stride), _ptr(packed), K,
+                                         int(cout), int(groups), _ptr(nbr), int(n_out), _ptr(bias), _ptr(scale), _ptr(shift),
+                                         *residual, int(bool(relu)), po, oc, pcols, ps, _stream())
+        _lib.check(rc, fmt.conv_rows)
 
     if into is not None:
         out, osp, col0 = into

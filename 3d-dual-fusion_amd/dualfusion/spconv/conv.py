@@ -45,21 +45,13 @@ class SparseConvFunction(torch.autograd.Function):
         w = filters.detach().contiguous().view(K, cin, cout)
         b = bias.detach() if bias is not None else None
         ctx.mode = _ops.CONV_PRECISION                     # the backward runs in the arithmetic the forward was called in
-        ctx.amp = _ops.CONV_PRECISION == "bf16" and _ops.conv_bf16_supported(K, cin, cout)
-        if ctx.amp:
-            # bf16 mixed-precision training (the reference's fp16-AMP configurations): operands rounded to
-            # bf16 for the matrix cores, fp32 accumulate and fp32 rows out (BatchNorm, residuals, losses and the master
-            # weights stay fp32, as under torch.autocast); the backward does the same for the input gradient
-            return _ops.sparse_conv_bf16(_ops.rows_to_bf16(features), _ops.conv_pack_weights_bf16(w), nbr, n_out, cin, cout,
-                                         bias=b, want_f32=True, want_bf16=False)[0]
-        if _ops.conv_split_supported(K, cin, cout):            # same split-precision kernel as inference (~1e-5 rel.)
-            return _ops.sparse_conv_split(_ops.split_rows(features), _ops.conv_pack_weights(w), nbr, n_out, cin, cout,
-                                          bias=b, emit_split=False)[0]
-        if _ops.CONV_PRECISION == "split" and cin > 128 and cin % 128 == 0 and cout % 8 == 0 and cout <= 128:
-            # many input channels (a head's shared convolution 512 -> 128 over the BEV rows): the row kernel that walks the
-            # input channels in 128-column blocks (the inference path's launch, csrc/spconv_split.hip loader / consumer)
-            return _ops.conv_rows_split(_ops.split_rows(features), cin, 0, _ops.conv_pack_weights(w), cout, 1, nbr, n_out, b)[0]
-        return _ops.sparse_conv_fused(features, w, nbr, n_out, bias=b)
+        packed = _ops.ConvFilters(w)                       # (packed per call: the parameter changes with every step)
+        # "bf16" = mixed-precision training (the reference's fp16-AMP configurations): operands rounded to
+        # bf16 for the matrix cores, fp32 accumulate and fp32 rows out (BatchNorm, residuals, losses and the master weights
+        # stay fp32, as under torch.autocast); the backward does the same for the input gradient.  "split" / "split3": the
+        # same kernels as inference (~1e-5 rel.).
+        ctx.amp = packed.kind == "bf16"
+        return _ops.conv(packed, nbr, n_out, rows=features, bias=b, want_operand=False)[0]
 
     @staticmethod
     @torch.autograd.function.once_differentiable
@@ -225,44 +217,27 @@ class SparseConvolution(SparseModule):
             out = SparseConvTensor(out_features, rb.outids, rb.out_spatial_shape, input.batch_size)
             out.indice_dict, out.grid, out._directories = input.indice_dict, input.grid, input._directories
             return out
-        w = self.weight.detach()
         bias = self.bias.detach() if self.bias is not None else None
-        tiles = rb.tiles(self.in_channels, self.out_channels)
-        out_split = None
-        if _ops.CONV_PRECISION == "bf16" and _ops.conv_bf16_supported(K, self.in_channels, self.out_channels):
-            # BASELINE configs[2]: bf16 rows and weights, fp32 accumulate; the fp32 copy of the result serves the
-            # layers without a bf16 kernel (C <= 16) and the fusion adapter
-            if input.features is not feats:
-                input = input.replace_feature(feats)
-            if residual is None:
-                res16 = None
-            elif res_sct is not None:
-                res16 = res_sct.bf16_features()
-            else:
-                res16 = _ops.rows_to_bf16(residual.contiguous().float())
-            out_features, out16 = _ops.sparse_conv_bf16(input.bf16_features(), self._packed_weight_bf16(w, K), rb.nbr,
-                                                        n_out, self.in_channels, self.out_channels, bias=bias,
-                                                        scale=scale, shift=shift, residual=res16, relu=relu,
-                                                        want_f32=True, want_bf16=True)
-            out = SparseConvTensor(out_features, rb.outids, rb.out_spatial_shape, input.batch_size)
-            out.indice_dict, out.grid, out._directories = input.indice_dict, input.grid, input._directories
-            out._bf16 = (out_features, out16)
-            return out
-        if _ops.conv_split_supported(K, self.in_channels, self.out_channels):
-            if input.features is not feats:
-                input = input.replace_feature(feats)
-            out_features, out_split = _ops.sparse_conv_split(
-                input.split_features(), self._packed_weight(w, K), rb.nbr, n_out, self.in_channels,
-                self.out_channels, bias=bias, scale=scale, shift=shift, residual=residual, relu=relu, tiles=tiles)
+        filters = _ops.conv_filters(self, self.weight.detach(), K, self.in_channels, self.out_channels)
+        kind, operand, tiles = filters.kind, None, None
+        if kind == "fp32":
+            feats = feats.contiguous()
+            tiles = rb.tiles(self.in_channels, self.out_channels)
         else:
-            out_features = _ops.sparse_conv_fused(feats.contiguous(),
-                                                  w.contiguous().view(K, self.in_channels, self.out_channels),
-                                                  rb.nbr, n_out, bias=bias, scale=scale, shift=shift,
-                                                  residual=residual, relu=relu, tiles=tiles)
+            # matrix-core kernels read the operand rows the producing convolution wrote (or convert them once per tensor);
+            # in the bf16 mode the fp32 copy of the result serves the layers without a bf16 kernel (C <= 16) and the fusion
+            # adapter (BASELINE configs[2])
+            if input.features is not feats:
+                input = input.replace_feature(feats)
+            operand = input.operand_features(kind)
+            if kind == "bf16" and res_sct is not None:
+                residual = res_sct.operand_features(kind)
+        out_features, out_rows = _ops.conv(filters, rb.nbr, n_out, rows=feats, operand=operand, bias=bias, scale=scale,
+                                           shift=shift, residual=residual, relu=relu, tiles=tiles)
         out = SparseConvTensor(out_features, rb.outids, rb.out_spatial_shape, input.batch_size)
         out.indice_dict, out.grid, out._directories = input.indice_dict, input.grid, input._directories
-        if out_split is not None:
-            out._split = (out_features, out_split)
+        if out_rows is not None:
+            out.set_operand(kind, out_rows)
         return out
 
     def _twin3d(self):
@@ -278,23 +253,6 @@ class SparseConvolution(SparseModule):
             twin.output_padding = [0] + list(self.output_padding) if isinstance(self.output_padding, (list, tuple)) else self.output_padding
             self.__dict__["_twin"] = twin
         return twin
-
-    def _packed_weight_bf16(self, w, K):
-        key = (w.data_ptr(), w._version, str(w.device))
-        hit = getattr(self, "_packed16", None)
-        if hit is None or hit[0] != key:
-            hit = (key, _ops.conv_pack_weights_bf16(w.contiguous().float().view(K, self.in_channels, self.out_channels)))
-            self._packed16 = hit
-        return hit[1]
-
-    def _packed_weight(self, w, K):
-        """hi/lo bf16 MFMA operands of the filter bank, rebuilt only when the parameter changes."""
-        key = (w.data_ptr(), w._version, str(w.device), _ops.split_parts())
-        hit = getattr(self, "_packed", None)
-        if hit is None or hit[0] != key:
-            hit = (key, _ops.conv_pack_weights(w.contiguous().view(K, self.in_channels, self.out_channels)))
-            self._packed = hit
-        return hit[1]
 
     def forward(self, input):
         return self.forward_fused(input)

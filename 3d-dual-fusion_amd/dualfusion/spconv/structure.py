@@ -110,28 +110,34 @@ class SparseConvTensor(object):
         # occupancy directories keyed by the identity of the indices tensor they index; shared by
         # reference with derived tensors exactly like indice_dict
         self._directories = DirectoryCache()
-        # (features tensor, its split rows) when a split-precision conv produced or consumed these features
-        self._split = None
+        # operand rows of `features` for the matrix-core kernels, one slot per kind (ops.FORMATS): {kind: (features tensor,
+        # its operand rows)}
+        self._operands = {}
         # rulebooks built ahead of time for specific conv modules (dualfusion/executor.py), keyed by id(module)
         self._prebuilt = {}
 
+    def operand_features(self, kind):
+        """`features` as operand rows of `kind` ("bf16" | "split" | "split3"): emitted by the producing conv's epilogue when
+        there is one (`set_operand`), otherwise converted here once."""
+        hit = self._operands.get(kind)
+        if hit is None or hit[0] is not self.features:
+            hit = self._operands[kind] = (self.features, _ops.operand_rows(kind, self.features.contiguous().float()))
+        return hit[1]
+
+    def set_operand(self, kind, rows):
+        """`rows` are the operand rows of kind `kind` of the present `features`."""
+        self._operands[kind] = (self.features, rows)
+
+    @property
+    def _bf16(self):
+        """(features, their bf16 rows) when a bf16 kernel produced or consumed these features, else None."""
+        return self._operands.get("bf16")
+
     def split_features(self):
-        """Split rows (bf16 hi | lo) of `features` for the split-precision conv kernels; emitted by the producing
-        conv's epilogue when there is one, otherwise computed here once."""
-        if (self._split is None or self._split[0] is not self.features
-                or self._split[1].shape[1] != _ops.split_width(self.features.shape[1])):      # (another precision mode's rows)
-            feats = self.features.contiguous()
-            self._split = (self.features, _ops.split_rows(feats))
-        return self._split[1]
+        return self.operand_features(_ops.split_kind())
 
     def bf16_features(self):
-        """`features` as bf16 rows for the bf16 conv kernels (DF3D_CONV_PRECISION=bf16); emitted by the producing
-        conv's epilogue when there is one, otherwise converted here once."""
-        hit = getattr(self, "_bf16", None)
-        if hit is None or hit[0] is not self.features:
-            hit = (self.features, _ops.rows_to_bf16(self.features.contiguous().float()))
-            self._bf16 = hit
-        return hit[1]
+        return self.operand_features("bf16")
 
     # ---- 2-D tensors run on the 3-D kernels as a one-slice volume ------------------------------------------------
     def lift3d(self):
@@ -142,19 +148,19 @@ class SparseConvTensor(object):
             ind = self.indices
             ind3 = torch.cat([ind[:, :1], torch.zeros_like(ind[:, :1]), ind[:, 1:]], 1).contiguous()
             t = SparseConvTensor(self.features, ind3, [1] + self.spatial_shape, self.batch_size, self.grid)
-            t.indice_dict, t._directories = self.indice_dict, self._directories
+            t.indice_dict, t._directories, t._operands = self.indice_dict, self._directories, self._operands
             hit = (self.indices, t)
             self.__dict__["_lift"] = hit
         t = hit[1]
         if t.features is not self.features:
-            t.features, t._split = self.features, self._split
+            t.features = self.features
         return t
 
     def drop_z(self):
         """inverse of lift3d for a tensor produced by a (1, kh, kw) kernel."""
         ind2 = self.indices[:, [0, 2, 3]].contiguous()
         t = SparseConvTensor(self.features, ind2, self.spatial_shape[1:], self.batch_size, self.grid)
-        t.indice_dict, t._directories, t._split = self.indice_dict, self._directories, self._split
+        t.indice_dict, t._directories, t._operands = self.indice_dict, self._directories, self._operands
         t.__dict__["_lift"] = (ind2, self)
         return t
 

@@ -790,6 +790,9 @@ int df3d_assemble_queries2_compact(const float *features, const float *point_inv
  *   df3d_sparse_conv_split:  out fp32 [n_out][cout]; out_split (optional) receives the split rows of `out`
  *                            so that the next convolution needs no df3d_split_rows pass.  out may be NULL when
  *                            out_split is given (a layer whose only reader is the next split-precision convolution).
+ *                            tile_rows / ntiles: ntiles == -1 makes tile_rows the [n_out] tiling order of the
+ *                            output-stationary kernel; every other value is accepted and ignored (the kernel that
+ *                            took row ranges here is retired).
  * ---------------------------------------------------------------------------------- */
 size_t df3d_conv_packed_weight_bytes(int kvol, int cin, int cout);
 int df3d_conv_pack_weights(const float *filters, int kvol, int cin, int cout, void *packed, void *stream);

@@ -237,22 +237,104 @@ def test_sparse_conv_split_precision(dev, cin, cout, n_seeds):
         outids, nbr, _ = _hip_rulebook(ind_t, batch, shape, ks, st, pd, dl, subm)
         n_out = outids.shape[0]
         res = detgen.randn("csr%d" % cout, (n_out, cout))
-        for tiles in (None, ops.conv_tiles(nbr, cin, cout)):
-            y, ys = ops.sparse_conv_split(fsplit, packed, nbr, n_out, cin, cout, bias=T(bias, dev),
-                                          scale=T(scale, dev), shift=T(shift, dev), residual=T(res, dev), relu=True,
-                                          tiles=tiles)
-            nb = nbr.cpu().numpy()
-            acc = np.zeros((n_out, cout), np.float64)
-            for k in range(27):
-                m = nb[k] >= 0
-                acc[m] += feats[nb[k][m]].astype(np.float64) @ filt[k].astype(np.float64)
-            ref = np.maximum((acc + bias) * scale + shift + res, 0)
-            err = np.abs(y.cpu().numpy() - ref).max() / np.abs(ref).max()
-            assert err < 4e-6, err
-            assert torch.equal(ys, ops.split_rows(y))
+        y, ys = ops.sparse_conv_split(fsplit, packed, nbr, n_out, cin, cout, bias=T(bias, dev),
+                                      scale=T(scale, dev), shift=T(shift, dev), residual=T(res, dev), relu=True)
+        nb = nbr.cpu().numpy()
+        acc = np.zeros((n_out, cout), np.float64)
+        for k in range(27):
+            m = nb[k] >= 0
+            acc[m] += feats[nb[k][m]].astype(np.float64) @ filt[k].astype(np.float64)
+        ref = np.maximum((acc + bias) * scale + shift + res, 0)
+        err = np.abs(y.cpu().numpy() - ref).max() / np.abs(ref).max()
+        assert err < 4e-6, err
+        assert torch.equal(ys, ops.split_rows(y))
         y32 = ops.sparse_conv_fused(T(feats, dev), T(filt, dev), nbr, n_out, bias=T(bias, dev), scale=T(scale, dev),
                                     shift=T(shift, dev), residual=T(res, dev), relu=True)
         assert np.abs(y32.cpu().numpy() - ref).max() / np.abs(ref).max() < 5e-6
+
+
+_DISPATCH_MODES = ("fp32", "bf16", "split", "split3")
+
+
+def _dispatch_tables(dev):
+    """[(nbr, n_in, n_out)]: a K = 27 SubM rulebook and a stride-2 rulebook over clustered voxels, one dense 3x3 table."""
+    from dualfusion import ops
+    shape, batch = [9, 48, 48], 2
+    ind_t = T(detgen.clustered_voxels("dispatch", batch, shape, n_seeds=4, walk=200), dev)
+    tables = []
+    for subm in (1, 0):
+        outids, nbr, _ = _hip_rulebook(ind_t, batch, shape, [3, 3, 3], [2, 2, 2], [1, 1, 1], [1, 1, 1], subm)
+        tables.append((nbr, ind_t.shape[0], outids.shape[0]))
+    nbr, Ho, Wo = ops.conv2d_neighbors(1, 12, 12, 3, 3, 1, 1, False, dev)
+    tables.append((nbr, 144, nbr.shape[1]))
+    return tables
+
+
+@pytest.mark.parametrize("cin,cout", [(16, 16), (32, 64), (128, 32), (512, 64)])
+def test_conv_dispatch_launches_what_the_direct_wrappers_launch(dev, cin, cout):
+    """`ops.conv_kind` / `ops.ConvFilters` / `ops.conv` against the wrapper the hand-written ladders picked, per mode and
+    table: the same kind, and fp32 rows and operand rows equal bit for bit under the full epilogue (bias, scale, shift,
+    residual, relu) -- with the operand rows converted by the dispatch and handed over by the caller.  Filters packed under
+    one mode and used under another are repacked by the cache; used directly they are refused, unless they are plain fp32
+    filters, which run the exact-fp32 kernel on fp32 rows."""
+    import types
+    from dualfusion import _lib, ops
+
+    def expected_kind(mode):
+        if mode == "fp32" or (cin, cout) == (16, 16):
+            return "fp32"
+        if mode == "bf16" and (cin, cout) in ((128, 32), (512, 64)):
+            return "fp32"
+        return mode
+
+    bias, scale, shift = (T(detgen.randn("dp%s%d" % (t, cout), (cout,), 0.1), dev) for t in "bsh")
+    scale = scale + 1
+    for ti, (nbr, n_in, n_out) in enumerate(_dispatch_tables(dev)):
+        K = nbr.shape[0]
+        x = T(detgen.randn("dpx%d_%d" % (ti, cin), (n_in, cin)), dev)
+        res = T(detgen.randn("dpr%d_%d" % (ti, cout), (n_out, cout)), dev)
+        w = T(detgen.randn("dpw%d_%d_%d" % (K, cin, cout), (K, cin, cout), 0.5 / np.sqrt(cin)), dev)
+        epi = dict(bias=bias, scale=scale, shift=shift, relu=True)
+        owner = types.SimpleNamespace()
+        direct, packed = {}, {}
+        for mode in _DISPATCH_MODES:
+            with ops.precision(mode):
+                kind = ops.conv_kind(K, cin, cout)
+                assert kind == expected_kind(mode), (mode, kind)
+                if kind == "fp32":
+                    want = (ops.sparse_conv_fused(x, w, nbr, n_out, residual=res, **epi), None)
+                elif kind == "bf16":
+                    want = ops.sparse_conv_bf16(ops.rows_to_bf16(x), ops.conv_pack_weights_bf16(w), nbr, n_out, cin, cout,
+                                                residual=ops.rows_to_bf16(res), want_f32=True, **epi)
+                else:
+                    want = ops.sparse_conv_split(ops.split_rows(x), ops.conv_pack_weights(w), nbr, n_out, cin, cout,
+                                                 residual=res, **epi)
+                direct[mode] = want
+                filt = packed[mode] = ops.conv_filters(owner, w, K, cin, cout)
+                assert filt.kind == kind and ops.ConvFilters(w).kind == kind
+                got = ops.conv(filt, nbr, n_out, rows=x, residual=res, **epi)
+                assert torch.equal(got[0], want[0]), mode
+                assert (got[1] is None and want[1] is None) or torch.equal(got[1], want[1]), mode
+                if kind != "fp32":
+                    assert ops.is_operand(kind, got[1], cout)
+                    again = ops.conv(filt, nbr, n_out, operand=ops.operand_rows(kind, x), residual=res, **epi)
+                    assert torch.equal(again[0], want[0]) and torch.equal(again[1], want[1]), mode
+        for mode in _DISPATCH_MODES:                 # every mode after every other one
+            for was in _DISPATCH_MODES:
+                if was == mode:
+                    continue
+                with ops.precision(mode):
+                    filt = ops.conv_filters(owner, w, K, cin, cout)          # the cache follows the mode
+                    assert filt.kind == expected_kind(mode)
+                    got = ops.conv(filt, nbr, n_out, rows=x, residual=res, **epi)
+                    assert torch.equal(got[0], direct[mode][0]), (was, mode)
+                    stale = packed[was]
+                    if stale.kind in ("fp32", mode):
+                        got = ops.conv(stale, nbr, n_out, rows=x, residual=res, **epi)
+                        assert torch.equal(got[0], direct[was][0]), (was, mode)
+                    else:
+                        with pytest.raises(_lib.Df3dError):
+                            ops.conv(stale, nbr, n_out, rows=x, residual=res, **epi)
 
 
 @pytest.mark.parametrize("cin,cout", [(128, 128), (64, 128), (128, 256)])

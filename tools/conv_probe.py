@@ -54,12 +54,10 @@ print("stage %s N=%d C=%d R=%d pairs/row=%.1f : fp32 kernel %.1f us/launch, %.1f
 if ops.conv_split_supported(rb.nbr.shape[0], C, C):
     packed = ops.conv_pack_weights(w)
     fs = ops.split_rows(f)
-    us, (ys, _) = timeit(lambda: ops.sparse_conv_split(fs, packed, rb.nbr, n, C, C, relu=True, tiles=tiles))
+    us, (ys, _) = timeit(lambda: ops.sparse_conv_split(fs, packed, rb.nbr, n, C, C, relu=True))
     err = float((ys - y32).abs().max() / y32.abs().max())
-    print("  split-precision kernel (%s) %.1f us/launch, %.1f TF useful, %.2f TB/s algorithmic (%.1f%% of 8 TB/s HBM), "
-          "max |diff| vs fp32 kernel %.2e of scale" % (os.environ.get("DF3D_SPLIT_KERNEL", "default"), us,
-                                                      fl / us / 1e6, abytes / us / 1e6, abytes / us / 1e6 / 8 * 100,
-                                                      err))
+    print("  split-precision kernel %.1f us/launch, %.1f TF useful, %.2f TB/s algorithmic (%.1f%% of 8 TB/s HBM), "
+          "max |diff| vs fp32 kernel %.2e of scale" % (us, fl / us / 1e6, abytes / us / 1e6, abytes / us / 1e6 / 8 * 100, err))
     us, _ = timeit(lambda: ops.split_rows(f))
     print("  split_rows pass %.1f us" % us)
 # ---- tile balance statistics (rows cut into 256 equal tiles, as the pair kernel does)

@@ -1,5 +1,5 @@
 // Output-stationary split-precision sparse convolution, third structure (round 3): INPUT ROWS STAGED THROUGH LDS.
-// Included by spconv_split.hip (shares SplitConvArgs, the packed-weight layout 1, split rows, the MFMA macro).
+// Included by spconv_split.hip (shares SplitConvArgs, the packed-weight layout, split rows, the MFMA macro).
 //
 // What rounds 1-2 measured about the two kernels above: a (offset, 32-channel) step costs ~1400 clocks whatever its
 // matrix work, because every step GATHERS its A operands from L2 -- a fragment-shaped register gather is 64 line

@@ -1,5 +1,5 @@
 // Weight-stationary split-precision sparse convolution (round 3).  Included by spconv_split.hip (shares SplitConvArgs, the
-// packed-weight layout 1, the split rows, the zero row and the MFMA macro).
+// packed-weight layout, the split rows, the zero row and the MFMA macro).
 //
 // What rounds 1-3 measured about the output-stationary kernels: a (offset, 32-channel) step costs ~1400 clocks whatever its
 // matrix work, because all waves of a workgroup walk the steps in lockstep -- one barrier per step, the step's filter tile
@@ -162,7 +162,7 @@ __global__ __launch_bounds__(NW * 64) void spconv_ws_kernel(SplitConvArgs a, int
     }
   }
 
-  // ---- epilogue: lane (n, g) holds rows 4g .. 4g+3 of a tile, columns n * CT .. n * CT + CT - 1 (packed-weight layout 1) ----
+  // ---- epilogue: lane (n, g) holds rows 4g .. 4g+3 of a tile, columns n * CT .. n * CT + CT - 1 (the packed-weight layout) ----
   if constexpr (CT == 2) {
     const int col = n * 2;
     const float2 bi = a.bias ? *(const float2 *)(a.bias + col) : make_float2(0.f, 0.f);

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """The three stride-2 SparseConv3d layers of the CenterPoint backbone (16 -> 32, 32 -> 64, 64 -> 128): few pairs per output
 row (an input feeds <= 8 outputs), so an output-stationary kernel multiplies mostly zero rows.  Time per kernel choice.
-usage: stride_probe.py [iters]   (DF3D_SPLIT_KERNEL=pair selects the pair-compacted kernel)"""
+usage: stride_probe.py [iters]"""
 import os
 import sys
 
@@ -48,8 +48,7 @@ for name, xin, stage in (("16->32", xs[0], "conv2"), ("32->64", xs[1], "conv3"),
     if ops.conv_split_supported(27, cin, cout):
         fs = ops.split_rows(f)
         packed = ops.conv_pack_weights(w)
-        tiles = ops.conv_tiles(rb.nbr, cin, cout)
-        us = timeit(lambda: ops.sparse_conv_split(fs, packed, rb.nbr, n_out, cin, cout, relu=True, tiles=tiles))
+        us = timeit(lambda: ops.sparse_conv_split(fs, packed, rb.nbr, n_out, cin, cout, relu=True))
         line += "  split %.1f us" % us
         # rows sorted by their active-offset mask: a tile then needs only the offsets its rows use
         bits = (rb.nbr >= 0).to(torch.int32) << torch.arange(27, device=dev, dtype=torch.int32)[:, None]
