@@ -651,69 +651,116 @@ extern "C" int df3d_invert_neighbors(const int32_t *nbr, int kvol, int n_out, in
   return DF3D_OK;
 }
 
-extern "C" int df3d_sparse_conv_grad_filters(const float *features, int n_in, int cin, const float *grad_out, int n_out,
-                                             int cout, const int32_t *nbr, int kvol, float *grad_filters,
-                                             void *stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  DF3D_CHECK_ARG(kvol > 0 && kvol <= DF3D_MAX_KVOL && cin > 0 && cout > 0 && n_in >= 0 && n_out >= 0,
-                 "sparse_conv_grad_filters: bad sizes");
-  DF3D_CHECK_ARG(grad_filters, "sparse_conv_grad_filters: null output");
-  DF3D_HIP(hipMemsetAsync(grad_filters, 0, (size_t)kvol * cin * cout * sizeof(float), stream));
-  if (n_out == 0 || n_in == 0) return DF3D_OK;
-  DF3D_CHECK_ARG(features && grad_out && nbr, "sparse_conv_grad_filters: null argument");
-  const char *env = getenv("DF3D_WGRAD");                    // read per call: tests switch between the kernels
-  // 0 = grad_filters_kernel, 1 = wgrad_f32_kernel (exact fp32 products), 3 = wgrad_split3_kernel (three bf16 parts, six
-  // products: fp32-grade); default: 3 where it measured faster (tools/ubench/wgrad3_probe.py, MI355X: 128 -> 128 K = 27 230 ->
-  // 171 us, dense 3 x 3 128 -> 128 121 -> 112, 256 -> 256 118 -> 108, 256 -> 128 202 -> 179, the head's 64 -> 36 x 64 1257 -> 940;
+// ---- the filter gradient: which kernel runs, and the one launch path of the five entries below ---------------------------
+// What an entry asks for: the plain entries, _bf16 (one rounded bf16 part per operand), _scaled (fp16 pairs, a gradient operand
+// under its power-of-two block scale) ...
+enum WgradForm { WGRAD_PLAIN = 0, WGRAD_BF16 = 1, WGRAD_SCALED = 2 };
+// ... and what runs: grad_filters_kernel (direct), wgrad_f32_kernel (rows staged through LDS, exact fp32 products) or
+// wgrad_split3_kernel (16-bit matrix cores, 1 / 2 / 3 parts per operand); df3d_grad_filters_kernel reports `code()`.
+struct WgradChoice {
+  enum Family { REFUSED = -1, DIRECT = 0, STAGED = 1, MATRIX = 10 } family;
+  int parts;
+  int code() const { return family == MATRIX ? MATRIX + parts : family; }
+};
+
+// kvol = 0: the table-less rows form (df3d_rows_grad_weights*).  scale_given: the scaled form came with a device scale.
+static WgradChoice choose_wgrad(int form, int kvol, int cin, int cout, int n_out, bool scale_given) {
+  const bool quads = cin % 4 == 0 && cout % 4 == 0;                // the staged kernels load 4 channels at a time
+  if (kvol == 0) {                                                 // rows: matrix cores only, DF3D_WGRAD is not consulted
+    if (!quads || form == WGRAD_BF16) return {WgradChoice::REFUSED, 0};
+    return {WgradChoice::MATRIX, form == WGRAD_SCALED ? 2 : 3};
+  }
+  // Under 64 channels on a side the 64-wide blocks of the matrix-core kernel are half empty: the one- and two-part forms
+  // hand such layers to the plain rule.  Measured (tools/ubench/wgrad3_probe.py, MI355X, us: exact-fp32 kernel / three bf16
+  // parts / two-part form): conv4 128 -> 128 K = 27 226 / 167 / 117, conv3 64 -> 64 116 / 147 / 96, dense 3 x 3 256 -> 128
+  // 202 / 175 / 127, 512 -> 64 202 / 208 / 146, the head's 64 -> 36 x 64 1254 / 918 / 582; 32 -> 32 K = 27 40 / 149 / 107.
+  const bool fills_blocks = quads && cin >= 64 && cout >= 64;
+  const char *env = getenv("DF3D_WGRAD");                          // read per call: tests switch between the kernels
+  if (form == WGRAD_BF16 && fills_blocks) return {WgradChoice::MATRIX, 1};          // (whatever DF3D_WGRAD says)
+  if (form == WGRAD_SCALED && fills_blocks && scale_given && !env) return {WgradChoice::MATRIX, 2};
+  // The plain rule; a set DF3D_WGRAD brings the scaled form here too.  DF3D_WGRAD: 0 = direct, 1 = staged fp32, 3 = three
+  // bf16 parts (six products: fp32-grade); default: 3 where it measured faster (wgrad3_probe.py: 128 -> 128 K = 27 230 -> 171
+  // us, dense 3 x 3 128 -> 128 121 -> 112, 256 -> 256 118 -> 108, 256 -> 128 202 -> 179, the head's 64 -> 36 x 64 1257 -> 940;
   // slower on 64 -> 64 K = 27 116 -> 138, 512 -> 64 198 -> 214 and on maps under 16 k rows), else 1
   const bool wide = (cin >= 128 && cout >= 128 && n_out >= 16384) || cout >= 1024;
-  const int kernel_choice = env ? atoi(env) : (wide ? 3 : 1);
-  if (kernel_choice == 3 && cin % 4 == 0 && cout % 4 == 0) {
-    WgradArgs a{features, grad_out, nbr, grad_filters, n_out, cin, cout, 0, 1, 0, 0, 0, {0}};
-    int rc = launch_wgrad3_any(a, kvol, stream);
+  const int want = env ? atoi(env) : (wide ? 3 : 1);
+  if (want == 3 && quads) return {WgradChoice::MATRIX, 3};
+  if (want && quads) return {WgradChoice::STAGED, 0};
+  if (cout <= 128) return {WgradChoice::DIRECT, 0};
+  return {WgradChoice::REFUSED, 0};
+}
+
+static void launch_wgrad_staged(WgradArgs &a, int kvol, hipStream_t stream) {
+  const int cin = a.cin, cout = a.cout, n_out = a.n_out;
+  // enough workgroups to fill the chip a few times over, slices of at least 1024 rows (the atomics of a slice are
+  // amortised over its pairs)
+  const int tiles = cdiv(cin, cin >= 64 ? 64 : (cin > 16 ? 32 : 16)) * cdiv(cout, cout >= 64 ? 64 : (cout > 16 ? 32 : 16));
+  const int want = std::max(1, cdiv(3072, kvol * tiles));
+  const int slices = std::min(want, cdiv(n_out, 1024));
+  a.slice = cdiv(cdiv(n_out, slices), 256) * 256;
+  if (cin >= 64) launch_wgrad_ct<4>(a, kvol, stream);
+  else if (cin > 16) launch_wgrad_ct<2>(a, kvol, stream);
+  else launch_wgrad_ct<1>(a, kvol, stream);
+}
+
+static void launch_wgrad_direct(const WgradArgs &a, int kvol, hipStream_t stream) {
+  const dim3 grid(cdiv(a.n_out, GF_ROWS), kvol, cdiv(cdiv(a.cin, 16), 4));
+  const int ct = cdiv(a.cout, 16);
+  if (ct <= 1) hipLaunchKernelGGL(grad_filters_kernel<1>, grid, dim3(256), 0, stream, a.feat, a.gout, a.nbr, a.n_out, a.cin, a.cout, a.gw);
+  else if (ct <= 2) hipLaunchKernelGGL(grad_filters_kernel<2>, grid, dim3(256), 0, stream, a.feat, a.gout, a.nbr, a.n_out, a.cin, a.cout, a.gw);
+  else if (ct <= 4) hipLaunchKernelGGL(grad_filters_kernel<4>, grid, dim3(256), 0, stream, a.feat, a.gout, a.nbr, a.n_out, a.cin, a.cout, a.gw);
+  else hipLaunchKernelGGL(grad_filters_kernel<8>, grid, dim3(256), 0, stream, a.feat, a.gout, a.nbr, a.n_out, a.cin, a.cout, a.gw);
+}
+
+// The body of every filter-gradient entry.  table: a convolution over `nbr` [kvol][n_out]; else x and grad_out pair row by
+// row (n_in == n_out rows, kvol unused).  sa / sg: device scales of the two operands in the two-part form (NULL: the fixed
+// activation scale).  gw ([kvol][cin][cout], or [cin][cout]) is zero-filled here.
+static int wgrad_entry(const char *name, int form, bool table, const float *x, long long n_in, int cin, const float *grad_out,
+                       long long n_out, int cout, const int32_t *nbr, int kvol, const float *sa, const float *sg, float *gw,
+                       hipStream_t stream) {
+  DF3D_CHECK_ARG(cin > 0 && cout > 0 && n_in >= 0 && n_out >= 0 && n_out < (1ll << 31) &&
+                 (!table || (kvol > 0 && kvol <= DF3D_MAX_KVOL)), "%s: bad sizes", name);
+  DF3D_CHECK_ARG(gw, "%s: null output", name);
+  if (!table) kvol = 1;
+  const WgradChoice c = choose_wgrad(form, table ? kvol : 0, cin, cout, (int)n_out, form == WGRAD_SCALED && sg);
+  DF3D_CHECK_ARG(table || c.family != WgradChoice::REFUSED, "%s: channel counts must be multiples of 4 (got %d, %d)", name, cin,
+                 cout);
+  DF3D_HIP(hipMemsetAsync(gw, 0, (size_t)kvol * cin * cout * sizeof(float), stream));
+  if (n_out == 0 || n_in == 0) return DF3D_OK;
+  DF3D_CHECK_ARG(x && grad_out && (nbr || !table), "%s: null argument", name);
+  DF3D_CHECK_ARG(c.family != WgradChoice::REFUSED, "%s: at most 128 output channels (got %d) unless both channel counts are "
+                 "multiples of 4", name, cout);
+  WgradArgs a{x, grad_out, table ? nbr : nullptr, gw, (int)n_out, cin, cout, 0, 1, 0, 0, 0, {0}};
+  if (c.family == WgradChoice::MATRIX) {
+    if (c.parts == 2) a.sa = sa, a.sg = sg;
+    const int rc = launch_wgrad3_any(a, kvol, stream, c.parts);
     if (rc) return rc;
-    DF3D_LAUNCH_CHECK();
-    return DF3D_OK;
+  } else if (c.family == WgradChoice::STAGED) {
+    launch_wgrad_staged(a, kvol, stream);
+  } else {
+    launch_wgrad_direct(a, kvol, stream);
   }
-  if (kernel_choice && cin % 4 == 0 && cout % 4 == 0) {
-    WgradArgs a{features, grad_out, nbr, grad_filters, n_out, cin, cout, 0, 1, 0, 0, 0, {0}};
-    // enough workgroups to fill the chip a few times over, slices of at least 1024 rows (the atomics of a slice are
-    // amortised over its pairs)
-    const int tiles = cdiv(cin, cin >= 64 ? 64 : (cin > 16 ? 32 : 16)) * cdiv(cout, cout >= 64 ? 64 : (cout > 16 ? 32 : 16));
-    const int want = std::max(1, cdiv(3072, kvol * tiles));
-    const int slices = std::min(want, cdiv(n_out, 1024));
-    a.slice = cdiv(cdiv(n_out, slices), 256) * 256;
-    if (cin >= 64) launch_wgrad_ct<4>(a, kvol, stream);
-    else if (cin > 16) launch_wgrad_ct<2>(a, kvol, stream);
-    else launch_wgrad_ct<1>(a, kvol, stream);
-    DF3D_LAUNCH_CHECK();
-    return DF3D_OK;
-  }
-  DF3D_CHECK_ARG(cout <= 128, "sparse_conv_grad_filters: at most 128 output channels (got %d) unless both channel counts "
-                 "are multiples of 4", cout);
-  const dim3 grid(cdiv(n_out, GF_ROWS), kvol, cdiv(cdiv(cin, 16), 4));
-  const int ct = cdiv(cout, 16);
-  if (ct <= 1) hipLaunchKernelGGL(grad_filters_kernel<1>, grid, dim3(256), 0, stream, features, grad_out, nbr, n_out, cin, cout, grad_filters);
-  else if (ct <= 2) hipLaunchKernelGGL(grad_filters_kernel<2>, grid, dim3(256), 0, stream, features, grad_out, nbr, n_out, cin, cout, grad_filters);
-  else if (ct <= 4) hipLaunchKernelGGL(grad_filters_kernel<4>, grid, dim3(256), 0, stream, features, grad_out, nbr, n_out, cin, cout, grad_filters);
-  else hipLaunchKernelGGL(grad_filters_kernel<8>, grid, dim3(256), 0, stream, features, grad_out, nbr, n_out, cin, cout, grad_filters);
   DF3D_LAUNCH_CHECK();
   return DF3D_OK;
 }
 
+extern "C" int df3d_grad_filters_kernel(int form, int kvol, int cin, int cout, int n_out) {
+  if (form < WGRAD_PLAIN || form > WGRAD_SCALED || kvol < 0 || kvol > DF3D_MAX_KVOL || cin <= 0 || cout <= 0 || n_out < 0)
+    return -1;
+  return choose_wgrad(form, kvol, cin, cout, n_out, true).code();
+}
+
+extern "C" int df3d_sparse_conv_grad_filters(const float *features, int n_in, int cin, const float *grad_out, int n_out,
+                                             int cout, const int32_t *nbr, int kvol, float *grad_filters,
+                                             void *stream_) {
+  return wgrad_entry("sparse_conv_grad_filters", WGRAD_PLAIN, true, features, n_in, cin, grad_out, n_out, cout, nbr, kvol, nullptr,
+                     nullptr, grad_filters, (hipStream_t)stream_);
+}
+
 extern "C" int df3d_rows_grad_weights(const float *x, const float *grad_out, long long n, int cin, int cout, float *grad_weights,
                                       void *stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  DF3D_CHECK_ARG(grad_weights && cin > 0 && cout > 0 && n >= 0 && n < (1ll << 31), "rows_grad_weights: bad sizes");
-  DF3D_CHECK_ARG(cin % 4 == 0 && cout % 4 == 0, "rows_grad_weights: channel counts must be multiples of 4 (got %d, %d)", cin, cout);
-  DF3D_HIP(hipMemsetAsync(grad_weights, 0, (size_t)cin * cout * sizeof(float), stream));
-  if (n == 0) return DF3D_OK;
-  DF3D_CHECK_ARG(x && grad_out, "rows_grad_weights: null argument");
-  WgradArgs a{x, grad_out, nullptr, grad_weights, (int)n, cin, cout, 0, 1, 0, 0, 0, {0}};
-  int rc = launch_wgrad3_any(a, 1, stream);
-  if (rc) return rc;
-  DF3D_LAUNCH_CHECK();
-  return DF3D_OK;
+  return wgrad_entry("rows_grad_weights", WGRAD_PLAIN, false, x, n, cin, grad_out, n, cout, nullptr, 0, nullptr, nullptr,
+                     grad_weights, (hipStream_t)stream_);
 }
 
 // bf16 mixed-precision training (round 6; BASELINE configs[2] / [3] are bf16 configurations): both operands rounded to ONE bf16
@@ -721,19 +768,8 @@ extern "C" int df3d_rows_grad_weights(const float *x, const float *grad_out, lon
 // (spconv_ops.h:363-456 under autocast), at a third of the two-part kernel's matrix work and half of its staging.
 extern "C" int df3d_sparse_conv_grad_filters_bf16(const float *features, int n_in, int cin, const float *grad_out, int n_out,
                                                   int cout, const int32_t *nbr, int kvol, float *grad_filters, void *stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  if (cin % 4 || cout % 4 || cin < 64 || cout < 64)             // narrow layers: the fp32 kernels (the 64-wide blocks would be half empty)
-    return df3d_sparse_conv_grad_filters(features, n_in, cin, grad_out, n_out, cout, nbr, kvol, grad_filters, stream_);
-  DF3D_CHECK_ARG(kvol > 0 && kvol <= DF3D_MAX_KVOL && n_in >= 0 && n_out >= 0, "sparse_conv_grad_filters_bf16: bad sizes");
-  DF3D_CHECK_ARG(grad_filters, "sparse_conv_grad_filters_bf16: null output");
-  DF3D_HIP(hipMemsetAsync(grad_filters, 0, (size_t)kvol * cin * cout * sizeof(float), stream));
-  if (n_out == 0 || n_in == 0) return DF3D_OK;
-  DF3D_CHECK_ARG(features && grad_out && nbr, "sparse_conv_grad_filters_bf16: null argument");
-  WgradArgs a{features, grad_out, nbr, grad_filters, n_out, cin, cout, 0, 1, 0, 0, 0, {0}};
-  int rc = launch_wgrad3_any(a, kvol, stream, 1);
-  if (rc) return rc;
-  DF3D_LAUNCH_CHECK();
-  return DF3D_OK;
+  return wgrad_entry("sparse_conv_grad_filters_bf16", WGRAD_BF16, true, features, n_in, cin, grad_out, n_out, cout, nbr, kvol,
+                     nullptr, nullptr, grad_filters, (hipStream_t)stream_);
 }
 
 // Two-part forms (second half of round 5): fp16 pairs, three products.  grad_scale / x_scale / g_scale point at the power-of-two
@@ -742,39 +778,12 @@ extern "C" int df3d_sparse_conv_grad_filters_bf16(const float *features, int n_i
 extern "C" int df3d_sparse_conv_grad_filters_scaled(const float *features, int n_in, int cin, const float *grad_out, int n_out,
                                                     int cout, const int32_t *nbr, int kvol, const float *grad_scale,
                                                     float *grad_filters, void *stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  const char *env = getenv("DF3D_WGRAD");                    // (a forced kernel choice: the unscaled entry decides)
-  // measured (tools/ubench/wgrad3_probe.py, us: exact-fp32 kernel / three bf16 parts / this): conv4 128 -> 128 K = 27 226 / 167 /
-  // 117, conv3 64 -> 64 116 / 147 / 96, dense 3 x 3 256 -> 128 202 / 175 / 127, 512 -> 64 202 / 208 / 146, the head's 64 -> 36 x 64
-  // 1254 / 918 / 582; 32 -> 32 K = 27 40 / 149 / 107: the 64-wide blocks are half empty there -- the fp32 kernel keeps < 64 channels
-  const bool fits = cin % 4 == 0 && cout % 4 == 0 && cin >= 64 && cout >= 64 && grad_scale;
-  if (env || !fits)
-    return df3d_sparse_conv_grad_filters(features, n_in, cin, grad_out, n_out, cout, nbr, kvol, grad_filters, stream_);
-  DF3D_CHECK_ARG(kvol > 0 && kvol <= DF3D_MAX_KVOL && n_in >= 0 && n_out >= 0, "sparse_conv_grad_filters_scaled: bad sizes");
-  DF3D_CHECK_ARG(grad_filters, "sparse_conv_grad_filters_scaled: null output");
-  DF3D_HIP(hipMemsetAsync(grad_filters, 0, (size_t)kvol * cin * cout * sizeof(float), stream));
-  if (n_out == 0 || n_in == 0) return DF3D_OK;
-  DF3D_CHECK_ARG(features && grad_out && nbr, "sparse_conv_grad_filters_scaled: null argument");
-  WgradArgs a{features, grad_out, nbr, grad_filters, n_out, cin, cout, 0, 1, 0, 0, 0, {0}};
-  a.sa = nullptr, a.sg = grad_scale;
-  int rc = launch_wgrad3_any(a, kvol, stream, 2);
-  if (rc) return rc;
-  DF3D_LAUNCH_CHECK();
-  return DF3D_OK;
+  return wgrad_entry("sparse_conv_grad_filters_scaled", WGRAD_SCALED, true, features, n_in, cin, grad_out, n_out, cout, nbr, kvol,
+                     nullptr, grad_scale, grad_filters, (hipStream_t)stream_);
 }
 
 extern "C" int df3d_rows_grad_weights_scaled(const float *x, const float *grad_out, long long n, int cin, int cout,
                                              const float *x_scale, const float *g_scale, float *grad_weights, void *stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  DF3D_CHECK_ARG(grad_weights && cin > 0 && cout > 0 && n >= 0 && n < (1ll << 31), "rows_grad_weights_scaled: bad sizes");
-  DF3D_CHECK_ARG(cin % 4 == 0 && cout % 4 == 0, "rows_grad_weights_scaled: channel counts must be multiples of 4 (got %d, %d)", cin, cout);
-  DF3D_HIP(hipMemsetAsync(grad_weights, 0, (size_t)cin * cout * sizeof(float), stream));
-  if (n == 0) return DF3D_OK;
-  DF3D_CHECK_ARG(x && grad_out, "rows_grad_weights_scaled: null argument");
-  WgradArgs a{x, grad_out, nullptr, grad_weights, (int)n, cin, cout, 0, 1, 0, 0, 0, {0}};
-  a.sa = x_scale, a.sg = g_scale;
-  int rc = launch_wgrad3_any(a, 1, stream, 2);
-  if (rc) return rc;
-  DF3D_LAUNCH_CHECK();
-  return DF3D_OK;
+  return wgrad_entry("rows_grad_weights_scaled", WGRAD_SCALED, false, x, n, cin, grad_out, n, cout, nullptr, 0, x_scale, g_scale,
+                     grad_weights, (hipStream_t)stream_);
 }

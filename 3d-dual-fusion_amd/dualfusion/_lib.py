@@ -156,6 +156,7 @@ SIGNATURES = {
                                                     c_void_p, c_void_p]),
     "df3d_sparse_conv_grad_filters_bf16": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p]),
     "df3d_rows_grad_weights_scaled": (c_int, [c_void_p, c_void_p, c_longlong, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "df3d_grad_filters_kernel": (c_int, [c_int, c_int, c_int, c_int, c_int]),
     "df3d_pow2_scale_floats": (c_int, []),
     "df3d_rows_pow2_scale": (c_int, [c_void_p, c_longlong, c_void_p, c_void_p]),
     "df3d_rows_grad_weights": (c_int, [c_void_p, c_void_p, c_longlong, c_int, c_int, c_void_p, c_void_p]),

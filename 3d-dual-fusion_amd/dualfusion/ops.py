@@ -450,6 +450,7 @@ def sparse_conv_fused(features, filters, nbr, n_out, bias=None, scale=None, shif
 #          `sparse_conv_split`, `conv_rows_split`) then produce / consume three-part buffers: their callers treat split rows
 #          and packed filters as opaque, so the sparse backbone, the BEV neck and the head run on it unchanged.
 # "bf16":  bf16 rows and filters, fp32 accumulate (BASELINE configs[2]).
+# A forward layer's arithmetic is `conv_kind`'s answer, that of its gradients `conv_grad_plan`'s.
 CONV_PRECISION = os.environ.get("DF3D_CONV_PRECISION", "split")
 
 # True inside `reference_arithmetic()`: every matrix product of the hot path in plain fp32 -- the convolutions on the exact-fp32
@@ -492,7 +493,8 @@ class reference_arithmetic(_Arithmetic):
 
 class grad_precision(_Arithmetic):
     """Context of a backward pass: gradient rows have no fixed scale (1e-8 .. 1e+2 within one step), which the fp16 parts of
-    the "split" mode cannot hold -- input-gradient convolutions run in the three-part mode (bf16 parts: fp32's exponent range)."""
+    the "split" mode cannot hold -- input-gradient convolutions run in the three-part mode (bf16 parts: fp32's exponent range).
+    One rule of `conv_grad_plan`, which decides the arithmetic of a convolution's gradients; backward code asks the plan."""
 
     def _inside(self, mode, all_fp32):
         return ("split3" if mode == "split" else mode), all_fp32
@@ -554,6 +556,50 @@ def conv_split_supported(kvol, cin, cout):
 
 def conv_bf16_supported(kvol, cin, cout):
     return _lib.load().df3d_conv_packed_weight_bytes_bf16(int(kvol), int(cin), int(cout)) > 0
+
+
+def grad_scaled():
+    """DF3D_GRAD_SCALED=0 (an A/B switch): no block-scaled two-part gradient operands, the three-part forms instead."""
+    return os.environ.get("DF3D_GRAD_SCALED", "1") != "0"
+
+
+ConvGradPlan = collections.namedtuple("ConvGradPlan", "mode scaled blocks wgrad_bf16 fixed_scale")
+
+
+def conv_grad_plan(kvol, cin, cout, amp, grouped=False):
+    """The arithmetic of the gradients of a forward (kvol, cin, cout) convolution under the current mode; amp: the forward's
+    `bf16=` flag.  The one place that combines the mode, that flag, the shape tables (host queries) and DF3D_GRAD_SCALED.
+    -> mode: what `with precision(mode)` sets around the input gradient, a convolution of the transposed shape;  scaled: over
+    two-part gradient rows under their own power-of-two scale (`split_rows_scaled`; epilogue scale = 1 / s, filter gradient
+    with grad_scale);  blocks: the transposed filters as 128-column blocks of one grouped launch;  wgrad_bf16: the filter
+    gradient on single bf16 parts.
+    grouped: the head's grouped row convolutions (`conv_rows_split`, G branches 64 -> 64 over one table), which exist for the
+    two split formats only: in the "bf16" and "fp32" modes their gradient rows are two-part rows at the forward's FIXED
+    activation scale (`fixed_scale`: a known limit)."""
+    kvol, cin, cout, amp = int(kvol), int(cin), int(cout), bool(amp)
+    mode = CONV_PRECISION
+
+    def serves(m, c_in, c_out):
+        return m in FORMATS and getattr(_lib.load(), FORMATS[m].packed_bytes)(kvol, c_in, c_out) > 0
+
+    if grouped:
+        if mode == "split" and grad_scaled():
+            return ConvGradPlan("split", True, False, False, False)
+        if mode in ("split", "split3"):
+            return ConvGradPlan("split3", False, False, False, False)
+        return ConvGradPlan("split", False, False, False, True)
+    in_blocks = cin > 128 and cin % 128 == 0
+    if mode == "split" and not amp and cout % 8 == 0 and grad_scaled():
+        whole = serves("split", cout, cin)
+        if whole or (in_blocks and serves("split", cout, 128)):
+            return ConvGradPlan("split", True, not whole, False, False)
+    if amp and serves("bf16", cout, cin):           # the bf16 kernel is the forward's choice, whatever the mode
+        return ConvGradPlan("bf16", False, False, True, False)
+    if mode == "bf16":                              # (without it the bf16 mode runs the exact-fp32 kernel)
+        return ConvGradPlan("fp32", False, False, amp, False)
+    mode = "split3" if mode == "split" else mode    # = grad_precision
+    # a shape left on the exact-fp32 kernel (the head's shared conv 512 -> 64, transposed) runs in blocks the format serves
+    return ConvGradPlan(mode, False, in_blocks and not serves(mode, cout, cin) and serves(mode, cout, 128), amp, False)
 
 
 def _pack_filters(kind, filters, grouped=False):
@@ -763,8 +809,9 @@ def rows_pow2_scale(x):
 
 def sparse_conv_grad_filters(features, grad_out, nbr, grad_scale=None, bf16=False):
     """-> grad_filters [K, cin, cout] = sum over rulebook pairs of features[in]^T grad_out[out].
-    grad_scale: device scale of grad_out (`split_rows_scaled(...)[2]` / `rows_pow2_scale`): the two-part kernel
-    (df3d_sparse_conv_grad_filters_scaled) where it applies."""
+    grad_scale: device scale of grad_out (`split_rows_scaled(...)[2]` / `rows_pow2_scale`): the two-part form
+    (df3d_sparse_conv_grad_filters_scaled); bf16: one rounded bf16 part per operand (df3d_sparse_conv_grad_filters_bf16,
+    bf16 mixed-precision training).  The kernel each form runs on is the library's choice (df3d_grad_filters_kernel)."""
     lib = _lib.load()
     _chk(features, torch.float32, "features")
     _chk(grad_out, torch.float32, "grad_out")
@@ -774,22 +821,15 @@ def sparse_conv_grad_filters(features, grad_out, nbr, grad_scale=None, bf16=Fals
         raise ValueError("grad_out rows do not match the neighbour table")
     cin, cout = features.shape[1], grad_out.shape[1]
     gw = torch.empty((K, cin, cout), dtype=torch.float32, device=features.device)
+    entry, scale = "df3d_sparse_conv_grad_filters", ()
     if bf16 and os.environ.get("DF3D_WGRAD_BF16", "1") != "0":
-        # bf16 mixed-precision training: one rounded part per operand, one product (df3d_sparse_conv_grad_filters_bf16)
-        rc = lib.df3d_sparse_conv_grad_filters_bf16(_ptr(features), features.shape[0], cin, _ptr(grad_out), n_out, cout, _ptr(nbr),
-                                                    K, _ptr(gw), _stream())
-        _lib.check(rc, "df3d_sparse_conv_grad_filters_bf16")
-        return gw
-    if (grad_scale is not None and os.environ.get("DF3D_GRAD_SCALED", "1") != "0"
-            and os.environ.get("DF3D_WGRAD_SCALED", "1") != "0"):        # (A/B switch of the two-part filter gradient alone)
+        entry += "_bf16"
+    elif grad_scale is not None and grad_scaled():
         _chk(grad_scale, torch.float32, "grad_scale")
-        rc = lib.df3d_sparse_conv_grad_filters_scaled(_ptr(features), features.shape[0], cin, _ptr(grad_out), n_out, cout,
-                                                      _ptr(nbr), K, _ptr(grad_scale), _ptr(gw), _stream())
-        _lib.check(rc, "df3d_sparse_conv_grad_filters_scaled")
-        return gw
-    rc = lib.df3d_sparse_conv_grad_filters(_ptr(features), features.shape[0], cin, _ptr(grad_out), n_out, cout, _ptr(nbr),
-                                           K, _ptr(gw), _stream())
-    _lib.check(rc, "df3d_sparse_conv_grad_filters")
+        entry, scale = entry + "_scaled", (_ptr(grad_scale),)
+    rc = getattr(lib, entry)(_ptr(features), features.shape[0], cin, _ptr(grad_out), n_out, cout, _ptr(nbr), K, *scale, _ptr(gw),
+                             _stream())
+    _lib.check(rc, entry)
     return gw
 
 
@@ -806,21 +846,27 @@ def rows_grad_weights(x, grad_out, x_scale=None, g_scale=None, two_part=False):
         raise _lib.Df3dError("rows_grad_weights: %d rows against %d" % (n, grad_out.shape[0]))
     cout = grad_out.shape[1]
     gw = torch.empty((cin, cout), dtype=torch.float32, device=x.device)
-    if (two_part or x_scale is not None or g_scale is not None) and os.environ.get("DF3D_GRAD_SCALED", "1") != "0":
-        rc = lib.df3d_rows_grad_weights_scaled(_ptr(x), _ptr(grad_out), int(n), int(cin), int(cout), _ptr(x_scale), _ptr(g_scale),
-                                               _ptr(gw), _stream())
-        _lib.check(rc, "df3d_rows_grad_weights_scaled")
-        return gw
-    rc = lib.df3d_rows_grad_weights(_ptr(x), _ptr(grad_out), int(n), int(cin), int(cout), _ptr(gw), _stream())
-    _lib.check(rc, "df3d_rows_grad_weights")
+    entry, scales = "df3d_rows_grad_weights", ()
+    if (two_part or x_scale is not None or g_scale is not None) and grad_scaled():
+        entry, scales = entry + "_scaled", (_ptr(x_scale), _ptr(g_scale))
+    _lib.check(getattr(lib, entry)(_ptr(x), _ptr(grad_out), int(n), int(cin), int(cout), *scales, _ptr(gw), _stream()), entry)
     return gw
+
+
+def _column_blocks(wt):
+    """Transposed filters [K, cout, cin] (cin a multiple of 128) -> [cin / 128, K, cout, 128]: the banks of one grouped launch
+    whose group g writes the input-gradient columns 128 g .. 128 g + 127."""
+    K, cout, cin = wt.shape
+    return wt.view(K, cout, cin // 128, 128).permute(2, 0, 1, 3).contiguous()
 
 
 def sparse_conv_backward(features, filters, grad_out, nbr, subm, inv=None, bf16=False):
     """indice_conv backward from the kernel-facing rulebook: -> (grad_features [n_in, cin], grad_filters [K, cin, cout]).
-    filters [K, cin, cout].  bf16: the input gradient on the bf16 kernel (mixed-precision training: gradient rows and
-    transposed filters rounded to bf16, fp32 accumulate, fp32 rows out), and the filter gradient on single bf16 parts
-    (df3d_sparse_conv_grad_filters_bf16)."""
+    filters [K, cin, cout].  The input gradient is the forward convolution of the gradient rows with the transposed filters
+    over the inverse table; `conv_grad_plan` says in which arithmetic, and which form of the filter gradient goes with it.
+    bf16: the forward ran on the bf16 kernel (mixed-precision training) -- the input gradient on the bf16 kernel too
+    (gradient rows and transposed filters rounded to bf16, fp32 accumulate, fp32 rows out), the filter gradient on single
+    bf16 parts."""
     K = nbr.shape[0]
     n_in = features.shape[0]
     grad_out = grad_out.contiguous()
@@ -834,40 +880,19 @@ def sparse_conv_backward(features, filters, grad_out, nbr, subm, inv=None, bf16=
             inv = invert_neighbors(nbr, n_in)
     wt = filters.transpose(1, 2).contiguous()                     # [K, cout, cin]
     cout, cin = wt.shape[1], wt.shape[2]
-    if (CONV_PRECISION == "split" and not bf16 and cout % 8 == 0 and conv_split_supported(K, cout, cin)
-            and os.environ.get("DF3D_GRAD_SCALED", "1") != "0"):
-        # (round 5, second half) two-part rows of the gradient under ITS OWN power-of-two scale instead of three bf16 parts: a
-        # gradient tensor is narrow relative to its largest value, whatever that is; the convolution's epilogue multiplies by
-        # 1 / s.  DF3D_GRAD_SCALED=0: the three-part path below
-        gs, inv_s, sc = split_rows_scaled(grad_out, cin)
-        g_in, _ = sparse_conv_split(gs, conv_pack_weights(wt), inv, n_in, cout, cin, scale=inv_s, emit_split=False)
-        return g_in, sparse_conv_grad_filters(features.contiguous(), grad_out, nbr, grad_scale=sc)
-    if (CONV_PRECISION == "split" and not bf16 and cout % 8 == 0 and cin > 128 and cin % 128 == 0
-            and conv_split_supported(K, cout, 128) and os.environ.get("DF3D_GRAD_SCALED", "1") != "0"):
-        # the same for many input channels (the head's shared conv 512 -> 128, transposed): 128-column blocks of one grouped launch
-        # over the scaled two-part gradient rows (round 6: the three-part forms were 1.8 ms of the TransFusion training step)
-        gs, inv_s, sc = split_rows_scaled(grad_out, cin)
-        blocks = wt.view(K, cout, cin // 128, 128).permute(2, 0, 1, 3).contiguous()
-        g_in, _ = conv_rows_split(gs, cout, 0, conv_pack_weights_groups(blocks), 128, cin // 128, inv, n_in, scale=inv_s)
-        return g_in, sparse_conv_grad_filters(features.contiguous(), grad_out, nbr, grad_scale=sc)
-    # the transposed shape in the arithmetic of the gradient mode -- except that the bf16 kernel is the forward's choice
-    # (`bf16`, whatever the mode), never this function's own: without it the bf16 mode runs the exact-fp32 kernel
-    if bf16 and conv_bf16_supported(K, cout, cin):
-        mode = precision("bf16")
-    elif CONV_PRECISION == "bf16":
-        mode = precision("fp32")
-    else:
-        mode = grad_precision()
-    with mode:
-        w = ConvFilters(wt)
-        if w.kind == "fp32" and cin > 128 and cin % 128 == 0 and conv_split_supported(K, cout, 128):
-            # many input channels (the head's shared conv 512 -> 64, transposed): 128-column blocks of one grouped launch
-            blocks = wt.view(K, cout, cin // 128, 128).permute(2, 0, 1, 3).contiguous()
-            g_in, _ = conv_rows_split(split_rows(grad_out), cout, 0, conv_pack_weights_groups(blocks), 128, cin // 128, inv,
-                                      n_in)
+    plan = conv_grad_plan(K, cin, cout, bf16)
+    rows = inv_s = g_scale = None
+    with precision(plan.mode):
+        if plan.scaled:
+            # a gradient tensor is narrow relative to its largest value, whatever that is: two-part rows under ITS OWN
+            # power-of-two scale s, and the convolution's epilogue multiplies by 1 / s
+            rows, inv_s, g_scale = split_rows_scaled(grad_out, cin)
+        if plan.blocks:           # (the head's shared conv 512 -> 64, transposed: the formats have no kernel 64 -> 512)
+            g_in, _ = conv_rows_split(rows if plan.scaled else split_rows(grad_out), cout, 0,
+                                      conv_pack_weights_groups(_column_blocks(wt)), 128, cin // 128, inv, n_in, scale=inv_s)
         else:
-            g_in, _ = conv(w, inv, n_in, rows=grad_out, want_operand=False)
-    return g_in, sparse_conv_grad_filters(features.contiguous(), grad_out, nbr, bf16=bf16)
+            g_in, _ = conv(ConvFilters(wt), inv, n_in, rows=grad_out, operand=rows, scale=inv_s, want_operand=False)
+    return g_in, sparse_conv_grad_filters(features.contiguous(), grad_out, nbr, grad_scale=g_scale, bf16=plan.wgrad_bf16)
 
 
 def conv_rows_split(in_split, cin, in_group_stride, packed, cout, groups, nbr, n_out, bias=None, scale=None, shift=None,

@@ -30,9 +30,10 @@ GEOMETRY_STREAM_KEY = "__df3d_geometry_stream"
 
 class SparseConvFunction(torch.autograd.Function):
     """indice_conv + its backward (TF/mmdet3d/ops/spconv/functional.py:20-75 -> ops.indice_conv /
-    ops.indice_conv_backward) on the kernel-facing rulebook: forward = the exact-fp32 fused kernel (conv + bias),
-    backward = input gradient by the same kernel on the inverse table, filter gradient by
-    df3d_sparse_conv_grad_filters, bias gradient = column sums."""
+    ops.indice_conv_backward) on the kernel-facing rulebook: forward = conv + bias in the arithmetic of the mode
+    (`ops.conv_kind` / `ops.conv`), backward = `ops.sparse_conv_backward` in the mode the forward ran in (input gradient =
+    the forward kernels on the inverse table, filter gradient = df3d_sparse_conv_grad_filters*; `ops.conv_grad_plan`
+    says which), bias gradient = column sums."""
 
     @staticmethod
     def forward(ctx, features, filters, bias, nbr, n_out, mirror, inv=None):

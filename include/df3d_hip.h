@@ -295,6 +295,10 @@ int df3d_rows_grad_weights_scaled(const float *x, const float *grad_out, long lo
  * take df3d_sparse_conv_grad_filters. */
 int df3d_sparse_conv_grad_filters_bf16(const float *features, int n_in, int cin, const float *grad_out, int n_out, int cout,
                                        const int32_t *nbr, int kvol, float *grad_filters, void *stream);
+/* Host only: the kernel the filter-gradient entries above pick for a shape -- form 0 = the plain entries, 1 = _bf16, 2 = _scaled
+ * (with a scale); kvol = 0: the rows entries.  -> 0 direct kernel, 1 LDS-staged exact fp32, 10 + parts on the 16-bit matrix cores
+ * (11 / 12 / 13), negative where the entry refuses the shape.  Reads DF3D_WGRAD per call, as the entries do. */
+int df3d_grad_filters_kernel(int form, int kvol, int cin, int cout, int n_out);
 int df3d_rows_pow2_scale(const float *x, long long n_elems, float *scale, void *stream);
 int df3d_pow2_scale_floats(void);
 /* out[n][c] = sum_s x[n][c][s] * g[n][s] over channel-first maps x [nmaps][channels][S], g [nmaps][S]: the weight gradient of a

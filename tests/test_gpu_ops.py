@@ -337,6 +337,124 @@ def test_conv_dispatch_launches_what_the_direct_wrappers_launch(dev, cin, cout):
                             ops.conv(stale, nbr, n_out, rows=x, residual=res, **epi)
 
 
+def _column_blocks_of(wt):
+    K, cout, cin = wt.shape
+    return wt.view(K, cout, cin // 128, 128).permute(2, 0, 1, 3).contiguous()
+
+
+def _ladder_input_gradient(ops, mode, amp, wt, g, inv, n_in):
+    """The input gradient as `sparse_conv_backward` wrote it out before `conv_grad_plan` (DF3D_GRAD_SCALED on), on the
+    low-level wrappers.  wt [K, cout, cin] transposed filters -> (grad rows, device scale of the scaled rows or None)."""
+    K, cout, cin = wt.shape
+    with ops.precision(mode):
+        if mode == "split" and not amp and cout % 8 == 0 and ops.conv_split_supported(K, cout, cin):
+            gs, inv_s, sc = ops.split_rows_scaled(g, cin)
+            return ops.sparse_conv_split(gs, ops.conv_pack_weights(wt), inv, n_in, cout, cin, scale=inv_s, emit_split=False)[0], sc
+        if (mode == "split" and not amp and cout % 8 == 0 and cin > 128 and cin % 128 == 0
+                and ops.conv_split_supported(K, cout, 128)):
+            gs, inv_s, sc = ops.split_rows_scaled(g, cin)
+            packed = ops.conv_pack_weights_groups(_column_blocks_of(wt))
+            return ops.conv_rows_split(gs, cout, 0, packed, 128, cin // 128, inv, n_in, scale=inv_s)[0], sc
+    if amp and ops.conv_bf16_supported(K, cout, cin):
+        with ops.precision("bf16"):
+            return ops.sparse_conv_bf16(ops.rows_to_bf16(g), ops.conv_pack_weights_bf16(wt), inv, n_in, cout, cin, want_f32=True,
+                                        want_bf16=False)[0], None
+    with ops.precision("fp32" if mode == "bf16" else "split3" if mode == "split" else mode):
+        if ops.conv_split_supported(K, cout, cin):
+            return ops.sparse_conv_split(ops.split_rows(g), ops.conv_pack_weights(wt), inv, n_in, cout, cin, emit_split=False)[0], None
+        if cin > 128 and cin % 128 == 0 and ops.conv_split_supported(K, cout, 128):
+            packed = ops.conv_pack_weights_groups(_column_blocks_of(wt))
+            return ops.conv_rows_split(ops.split_rows(g), cout, 0, packed, 128, cin // 128, inv, n_in)[0], None
+        return ops.sparse_conv_fused(g, wt, inv, n_in), None
+
+
+def _pairs_float64(x, g, nbr):
+    """sum over the pairs of x[in]^T g[out] per offset, in float64 on the host -> [K, cin, cout]."""
+    x, g, nbr = x.cpu().double(), g.cpu().double(), nbr.cpu().long()
+    ref = torch.zeros((nbr.shape[0], x.shape[1], g.shape[1]), dtype=torch.float64)
+    for k in range(nbr.shape[0]):
+        o = (nbr[k] >= 0).nonzero(as_tuple=True)[0]
+        ref[k] = x[nbr[k][o]].t() @ g[o]
+    return ref
+
+
+def _check_filter_gradient(got, x, g, nbr, form):
+    """Against float64 at the bounds of test_filter_gradient_kernels_against_float64; which one applies is the library's
+    answer (df3d_grad_filters_kernel, pinned by tests/test_grad_dispatch.py): 4e-6 of scale on the matrix cores -- with one bf16
+    part against the bf16-rounded operands --, 2e-5 on the fp32 kernels."""
+    from dualfusion import _lib
+    K, n_out = nbr.shape
+    kernel = _lib.load().df3d_grad_filters_kernel(form, K, x.shape[1], g.shape[1], n_out)
+    assert kernel in (0, 1, 11, 12, 13), kernel
+    ref = _pairs_float64(x, g, nbr)
+    scale = max(1.0, float(ref.abs().max()))
+    if kernel == 11:
+        ref = _pairs_float64(x.bfloat16().float(), g.bfloat16().float(), nbr)
+    err = float((got.cpu().double() - ref).abs().max())
+    assert err <= (2e-5 if kernel in (0, 1) else 4e-6) * scale, (kernel, err / scale)
+
+
+@pytest.mark.parametrize("cin,cout", [(16, 16), (64, 128), (256, 64), (512, 64), (32, 64)])
+def test_backward_dispatch_launches_what_the_hand_written_ladder_launched(dev, cin, cout):
+    """`ops.sparse_conv_backward` over `ops.conv_grad_plan`, per mode and table (bf16=True under "bf16"): the input gradient
+    equals bit for bit the ladder of low-level wrappers it replaced, the filter gradient (float atomics) float64."""
+    from dualfusion import ops
+    try:
+        for ti, (nbr, n_in, n_out) in enumerate(_dispatch_tables(dev)):
+            K = nbr.shape[0]
+            x = T(detgen.randn("bdx%d_%d" % (ti, cin), (n_in, cin)), dev)
+            g = T(detgen.randn("bdg%d_%d" % (ti, cout), (n_out, cout)), dev)
+            w = T(detgen.randn("bdw%d_%d_%d" % (K, cin, cout), (K, cin, cout), 0.5 / np.sqrt(cin)), dev)
+            subm = ti == 0
+            inv = nbr.flip(0).contiguous() if subm else ops.invert_neighbors(nbr, n_in)
+            for mode in _DISPATCH_MODES:
+                amp = mode == "bf16"
+                want, sc = _ladder_input_gradient(ops, mode, amp, w.transpose(1, 2).contiguous(), g, inv, n_in)
+                with ops.precision(mode):
+                    g_in, g_w = ops.sparse_conv_backward(x, w, g, nbr, subm, bf16=amp)
+                    assert ops.CONV_PRECISION == mode
+                assert torch.equal(g_in, want), (ti, mode)
+                _check_filter_gradient(g_w, x, g, nbr, 1 if amp else (2 if sc is not None else 0))
+    finally:
+        flag = ops.split_overflow(reset=True)
+    assert not flag[0], flag
+
+
+@pytest.mark.parametrize("mode", ["split", "split3", "bf16"])
+def test_head_branch_backward_launches_what_its_two_branches_launched(dev, mode):
+    """`heads._BranchConvFunction.backward` over the grouped plan (G = 4 branches on a 12x12 map): d rows bit-equal to the two
+    branches it had -- block-scaled two-part rows in "split", else `grad_precision` (which under "bf16" means two-part rows at
+    the fixed activation scale) --, d w against float64."""
+    from dualfusion import ops
+    from dualfusion.heads import _BranchConvFunction
+    nbr, P, _ = _dispatch_tables(dev)[2]
+    mirror = nbr.flip(0).contiguous()
+    G, K, cin, cout = 4, 9, 64, 64
+    rows = T(detgen.randn("hbx", (P, cin)), dev).requires_grad_()
+    w = T(detgen.randn("hbw", (G, K, cin, cout), 0.5 / np.sqrt(cin)), dev).requires_grad_()
+    go = T(detgen.randn("hbg", (P, G * cout)), dev)
+    try:
+        with ops.precision(mode):
+            _BranchConvFunction.apply(rows, w, None, nbr, mirror).backward(go)
+            packed_t = None
+            if mode == "split":
+                packed_t = ops.conv_pack_weights_groups(w.detach().transpose(2, 3).contiguous())
+                gs, inv_s, _ = ops.split_rows_scaled(go, G * cin)
+                part, _ = ops.conv_rows_split(gs, cout, cout, packed_t, cin, G, mirror, P, None, inv_s, None, relu=False)
+            else:
+                with ops.grad_precision():
+                    packed_t = ops.conv_pack_weights_groups(w.detach().transpose(2, 3).contiguous())
+                    part, _ = ops.conv_rows_split(ops.split_rows(go), cout, cout, packed_t, cin, G, mirror, P, None, None, None,
+                                                  relu=False)
+            assert packed_t.numel() == G * K * cin * cout * (6 if mode == "split3" else 4)
+        assert torch.equal(rows.grad, part.view(P, G, cin).sum(1))
+        g_w = w.grad.permute(1, 2, 0, 3).reshape(K, cin, G * cout)
+        _check_filter_gradient(g_w, rows.detach(), go, nbr, 2 if mode == "split" else 0)
+    finally:
+        flag = ops.split_overflow(reset=True)
+    assert not flag[0], flag
+
+
 @pytest.mark.parametrize("cin,cout", [(128, 128), (64, 128), (128, 256)])
 def test_loader_consumer_conv_kernel_forced_on_small_and_ragged_shapes(dev, cin, cout):
     """The loader / consumer LDS-DMA kernel normally serves layers of >= 190 workgroups; forced on (DF3D_OS_LC=1) it must
