@@ -239,3 +239,72 @@ def small_inputs(batch, seed=0, in_hw=(128, 224), n_gt=5):
         gts.append(box)
         labels.append(rs.randint(0, 10, n).astype(np.int64))
     return points, img, metas, gts, labels
+
+
+# ------------------------------------------------------------------------------------------------ CenterPoint fusion adapter
+# The adapter (`VoxelWithPointProjection`) on the inputs of tests/golden/fusion_cp.npz: `oracle_models.centerpoint_fusion_torch`
+# -- pinned to the reference module's own output by that golden -- evaluated in float64 is the ground truth of the values AND
+# the gradients; the same port in float32 is the yardstick of what plain fp32 arithmetic makes of them.
+CP_BLIND_CAMERA = "CAM_FRONT_RIGHT"                              # third in camera order: an empty range INSIDE the write-back loop
+_cp_cache = {}
+
+
+def cp_fusion_case(g):
+    """g: the loaded fusion_cp.npz -> its inputs as numpy (parameter shapes, detgen weights, voxel sets and features of
+    x_conv2..4, camera maps, calibration, the loss weights of `sum(out * w)`)."""
+    if "case" not in _cp_cache:
+        from dualfusion import synth
+        from make_golden import FUS
+        import detgen
+        shapes = {str(k): tuple(eval(str(s))) for k, s in zip(g["param_names"], g["param_shapes"])}
+        sets = [g["coords%d" % i].astype(np.int32) for i in (2, 3, 4)]
+        cams = synth.nusc_cameras(image_hw=FUS["raw_hw"], focal=FUS["focal"], yaw_offset_deg=FUS["yaw_offset_deg"])
+        B = FUS["batch"]
+        _cp_cache["case"] = dict(
+            shapes=shapes, sd=detgen.det_state_dict(shapes), sets=sets, cams=cams,
+            feats=[detgen.randn("fus_feat%d" % i, (len(s), c)) for i, (s, c) in enumerate(zip(sets, [32, 64, 128]))],
+            img={n: detgen.randn("fus_img_" + n, (B, 256) + tuple(FUS["feat_hw"])) for n in synth.NUSC_CAMS},
+            calib={n: (np.stack([cams[n][0]] * B), np.stack([cams[n][1]] * B)) for n in synth.NUSC_CAMS},
+            w=detgen.randn("fus_train_w", (len(sets[2]), 128)), out=np.asarray(g["out"]))
+    return _cp_cache["case"]
+
+
+def cp_depth_thres(blind=False):
+    """The fixture's depth thresholds; blind: CP_BLIND_CAMERA's beyond every voxel, so that the camera sees nothing."""
+    from make_golden import FUS
+    thres = dict(FUS["depth_thres"])
+    if blind:
+        thres[CP_BLIND_CAMERA] = 1e6
+    return thres
+
+
+def cp_fusion_port(case, P, feats, relu=True, blind=False):
+    """The port on tensors: P {name: tensor}, feats the three levels' features -> (out [n, 128], integer work)."""
+    import oracle_models as om
+    from dualfusion import synth
+    from make_golden import FUS
+    dt = feats[-1].dtype
+    img = {n: torch.from_numpy(v).to(dt) for n, v in case["img"].items()}
+    return om.centerpoint_fusion_torch(P, list(zip(case["sets"], feats)), img, case["calib"], FUS["img_hw"], synth.NUSC_CAMS,
+                                       FUS["voxel_size"], FUS["pc_range"], FUS["image_scale"], cp_depth_thres(blind),
+                                       act=F.relu if relu else (lambda x: x))
+
+
+def cp_fusion_leaves(case, dtype):
+    """-> (P, feats): every parameter and every level's features as a leaf that takes a gradient."""
+    P = {k: torch.from_numpy(v).to(dtype).requires_grad_(True) for k, v in case["sd"].items()}
+    return P, [torch.from_numpy(f).to(dtype).requires_grad_(True) for f in case["feats"]]
+
+
+def cp_fusion_gradients(case, dtype, relu=True, blind=False):
+    """One forward and backward of `sum(out * w)` through the port, evaluated once per variant and kept: -> dict(out, work,
+    grads {parameter name | 'leaf<i>': gradient}, unreached [names of leaves no gradient arrives at])."""
+    key = (dtype, relu, blind)
+    if key not in _cp_cache:
+        P, feats = cp_fusion_leaves(case, dtype)
+        out, work = cp_fusion_port(case, P, feats, relu, blind)
+        (out * torch.from_numpy(case["w"]).to(dtype)).sum().backward()
+        leaves = dict(P, **{"leaf%d" % i: f for i, f in enumerate(feats)})
+        _cp_cache[key] = dict(out=out.detach(), work=work, grads={k: v.grad for k, v in leaves.items() if v.grad is not None},
+                              unreached=sorted(k for k, v in leaves.items() if v.grad is None))
+    return _cp_cache[key]

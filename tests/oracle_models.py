@@ -210,77 +210,91 @@ def _t(a):
     return torch.from_numpy(np.ascontiguousarray(a))
 
 
-def actr_forward(sd, v_feat, grid, i_feat, lidar_grid, v_i_feat, num_layers=2, n_heads=8, n_points=4, prefix=""):
+def _msda_numpy(value, shapes, loc, aw):
+    """The numpy sampling oracle behind a tensor interface (no gradient passes through it)."""
+    return _t(orc.ms_deform_attn(value.numpy(), shapes, loc.numpy(), aw.numpy()))
+
+
+def actr_forward_torch(P, v_feat, grid, i_feat, lidar_grid, v_i_feat, num_layers=2, n_heads=8, n_points=4, prefix="",
+                       act=None, msda=None):
     """ACTR.forward with feature_modal='hybrid', pos_encode_method='depth', q_method 'sum' / rep_place
     ['weight'], BiGateSum1D_2 (CP/det3d/models/model_utils/actr.py:131-187, actr_transformer.py:399-426,
     473-511, ops/modules/ms_deform_attn.py:98-190, attentions.py:96-117, position_encoding.py:107-120).
-    Dense layers in torch-CPU fp32, deformable sampling by the numpy oracle."""
+    The torch path: P maps names to tensors (leaves with requires_grad included), the five inputs are tensors of P's
+    dtype, nothing is detached on the way and the result is a tensor -- in float64 the ground truth of the module's values
+    AND gradients.  act: the rectifier of the feed-forward blocks (F.relu; an identity evaluates the port without
+    rectifiers).  msda(value [N, S, M, D], [(H, W)], loc, aw) -> [N, Q, M * D]: f64_reference.msda_core_f64 by default."""
     import torch
     import torch.nn.functional as F
-    P = lambda k: _t(sd[prefix + k])
-    v_feat, grid, i_feat, lidar_grid, v_i_feat = [_t(np.asarray(a, np.float32)) for a in
-                                                  (v_feat, grid, i_feat, lidar_grid, v_i_feat)]
+    if act is None:
+        act = F.relu
+    if msda is None:
+        from f64_reference import msda_core_f64 as msda
+    p = lambda k: P[prefix + k]                                                    # noqa: E731
+    dt = v_feat.dtype
     N, Q, C = v_feat.shape
     H, W = i_feat.shape[2:]
-    qi = F.conv1d(v_i_feat.transpose(1, 2), P("i_input_proj.0.weight"), P("i_input_proj.0.bias"))
-    qi = F.group_norm(qi, 32, P("i_input_proj.1.weight"), P("i_input_proj.1.bias"), 1e-5).transpose(1, 2)
+    qi = F.conv1d(v_i_feat.transpose(1, 2), p("i_input_proj.0.weight"), p("i_input_proj.0.bias"))
+    qi = F.group_norm(qi, 32, p("i_input_proj.1.weight"), p("i_input_proj.1.bias"), 1e-5).transpose(1, 2)
     d = lidar_grid[..., 0] / 60.0 * (2 * np.pi)
-    dim_t = torch.arange(C, dtype=torch.float32)
+    dim_t = torch.arange(C, dtype=dt)
     dim_t = 10000 ** (2 * torch.div(dim_t, 2, rounding_mode="floor") / C)
     pd = d[:, :, None] / dim_t
     q_pos = torch.stack((pd[:, :, 0::2].sin(), pd[:, :, 1::2].cos()), dim=3).flatten(2)
-    src = F.group_norm(F.conv2d(i_feat, P("input_proj.0.0.weight"), P("input_proj.0.0.bias")), 32,
-                       P("input_proj.0.1.weight"), P("input_proj.0.1.bias"), 1e-5)
+    src = F.group_norm(F.conv2d(i_feat, p("input_proj.0.0.weight"), p("input_proj.0.0.bias")), 32,
+                       p("input_proj.0.1.weight"), p("input_proj.0.1.bias"), 1e-5)
     src = src.flatten(2).transpose(1, 2)                                   # [N, HW, C]
     q = v_feat
     D = C // n_heads
     for i in range(num_layers):
         L = "transformer.encoder.layers.%d." % i
-        value = F.linear(src, P(L + "self_attn.value_proj.weight"), P(L + "self_attn.value_proj.bias"))
+        value = F.linear(src, p(L + "self_attn.value_proj.weight"), p(L + "self_attn.value_proj.bias"))
         query, iq = q + q_pos, qi + q_pos
-        off = F.linear(query, P(L + "self_attn.sampling_offsets.weight"), P(L + "self_attn.sampling_offsets.bias"))
-        aw = F.linear(query + iq, P(L + "self_attn.attention_weights.weight"), P(L + "self_attn.attention_weights.bias"))
+        off = F.linear(query, p(L + "self_attn.sampling_offsets.weight"), p(L + "self_attn.sampling_offsets.bias"))
+        aw = F.linear(query + iq, p(L + "self_attn.attention_weights.weight"), p(L + "self_attn.attention_weights.bias"))
         aw = torch.softmax(aw.view(N, Q, n_heads, n_points), -1).view(N, Q, n_heads, 1, n_points)
         off = off.view(N, Q, n_heads, 1, n_points, 2)
-        loc = grid[:, :, None, None, None, :] + off / torch.tensor([W, H], dtype=torch.float32)
-        att = orc.ms_deform_attn(value.view(N, H * W, n_heads, D).numpy(), [(H, W)], loc.numpy(), aw.numpy())
-        att = F.linear(_t(att), P(L + "self_attn.output_proj.weight"), P(L + "self_attn.output_proj.bias"))
-        qi = F.layer_norm(qi + att, (C,), P(L + "norm1.weight"), P(L + "norm1.bias"))
-        qi = F.layer_norm(qi + F.linear(F.relu(F.linear(qi, P(L + "linear1.weight"), P(L + "linear1.bias"))),
-                                        P(L + "linear2.weight"), P(L + "linear2.bias")), (C,),
-                          P(L + "norm2.weight"), P(L + "norm2.bias"))
-        q = F.layer_norm(q + F.linear(F.relu(F.linear(q, P(L + "linear3.weight"), P(L + "linear3.bias"))),
-                                      P(L + "linear4.weight"), P(L + "linear4.bias")), (C,),
-                         P(L + "norm3.weight"), P(L + "norm3.bias"))
+        loc = grid[:, :, None, None, None, :] + off / torch.tensor([W, H], dtype=dt)
+        att = msda(value.view(N, H * W, n_heads, D), [(H, W)], loc, aw)
+        att = F.linear(att, p(L + "self_attn.output_proj.weight"), p(L + "self_attn.output_proj.bias"))
+        qi = F.layer_norm(qi + att, (C,), p(L + "norm1.weight"), p(L + "norm1.bias"))
+        qi = F.layer_norm(qi + F.linear(act(F.linear(qi, p(L + "linear1.weight"), p(L + "linear1.bias"))),
+                                        p(L + "linear2.weight"), p(L + "linear2.bias")), (C,),
+                          p(L + "norm2.weight"), p(L + "norm2.bias"))
+        q = F.layer_norm(q + F.linear(act(F.linear(q, p(L + "linear3.weight"), p(L + "linear3.bias"))),
+                                      p(L + "linear4.weight"), p(L + "linear4.bias")), (C,),
+                         p(L + "norm3.weight"), p(L + "norm3.bias"))
         fuse = (q + qi).transpose(1, 2)
-        s1 = torch.sigmoid(F.conv1d(fuse, P(L + "fusion_layer.b_conv1d.weight"), P(L + "fusion_layer.b_conv1d.bias"))).transpose(1, 2)
-        s2 = torch.sigmoid(F.conv1d(fuse, P(L + "fusion_layer.a_conv1d.weight"), P(L + "fusion_layer.a_conv1d.bias"))).transpose(1, 2)
+        s1 = torch.sigmoid(F.conv1d(fuse, p(L + "fusion_layer.b_conv1d.weight"), p(L + "fusion_layer.b_conv1d.bias"))).transpose(1, 2)
+        s2 = torch.sigmoid(F.conv1d(fuse, p(L + "fusion_layer.a_conv1d.weight"), p(L + "fusion_layer.a_conv1d.bias"))).transpose(1, 2)
         q, qi = q + qi * s1, qi + q * s2
-    return q.numpy()
+    return q
 
 
-def centerpoint_fusion(sd, levels, img_feats, calib, image_hw, cams, voxel_size, pc_range, image_scale, depth_thres,
-                       d_factors=(2, 4, 8), ifat_idx=(0, 2), debug=None):
-    """VoxelWithPointProjection.forward, fuse_mode 'pfat' + ifat gate (CP/det3d/models/fusion/
-    voxel_with_point_projection.py:131-385, point_to_image_projection.py:63-231,
-    model_utils/attention.py:31-61,422-468) restated with explicit loops.
-    levels: [(indices [n,4], features [n,C])] for x_conv2..4 (rows batch-sorted); img_feats {cam: [B,256,h,w]};
-    calib {cam: (lidar2cam [B,4,4], intrinsic [B,3,3])}; image_hw (H, W) of the network input image.
-    Returns the fused features of the last level."""
+def actr_forward(sd, v_feat, grid, i_feat, lidar_grid, v_i_feat, num_layers=2, n_heads=8, n_points=4, prefix=""):
+    """`actr_forward_torch` on numpy arrays: dense layers in torch-CPU fp32, deformable sampling by the numpy oracle."""
+    P = {k: _t(v) for k, v in sd.items() if k.startswith(prefix)}
+    args = [_t(np.asarray(a, np.float32)) for a in (v_feat, grid, i_feat, lidar_grid, v_i_feat)]
+    return actr_forward_torch(P, *args, num_layers=num_layers, n_heads=n_heads, n_points=n_points, prefix=prefix,
+                              msda=_msda_numpy).numpy()
+
+
+def centerpoint_projection(levels, calib, image_hw, feat_hw, cams, voxel_size, pc_range, image_scale, depth_thres,
+                           d_factors=(2, 4, 8)):
+    """The integer work of the adapter (point_to_image_projection.py:63-231), always in fp32 whatever the features'
+    precision: voxel corner -> camera -> pixel, truncated once at image and once at feature-map resolution, the in-image
+    and depth masks.  -> {(level, camera): [(grid [n_b, 2] int64 (x, y), mask [n_b] bool, corner xyz [n_b, 3] fp32)
+    per sample]} over the sample's rows of that level."""
     import torch
-    import torch.nn.functional as F
-    P = lambda k: _t(sd[k])
-    B = next(iter(img_feats.values())).shape[0]
     H, W = image_hw
+    h_, w_ = feat_hw
     pc_min = torch.tensor(pc_range[:3], dtype=torch.float32)
     vs = torch.tensor(voxel_size, dtype=torch.float32)
-    n_last = len(levels) - 1
-    per = {}                    # (b, cam) -> dict
-    img_gated = {}
+    proj = {}
     for ci, cam in enumerate(cams):
         l2c, K = [_t(np.asarray(x, np.float32)) for x in calib[cam]]
-        proj = []
-        for (ind, _), dfac in zip(levels, d_factors):
+        B = l2c.shape[0]
+        for li, ((ind, _), dfac) in enumerate(zip(levels, d_factors)):
             ind_t = _t(ind).float()
             xyz = ind_t[:, [3, 2, 1]] * (vs * dfac) + pc_min                       # voxel corner
             out = []
@@ -297,67 +311,107 @@ def centerpoint_fusion(sd, levels, img_feats, calib, image_hw, cams, voxel_size,
                 g = uv.long()
                 g = (image_scale * g.float()).long()
                 m = (g[:, 0] > 0) & (g[:, 0] < W) & (g[:, 1] > 0) & (g[:, 1] < H) & (depth > depth_thres[cam])
-                h_, w_ = img_feats[cam].shape[2:]
                 gf = g.float()
                 gf[:, 0] *= (w_ / W)
                 gf[:, 1] *= (h_ / H)
                 out.append((gf.long(), m, p))
-            proj.append(out)
+            proj[(li, ci)] = out
+    return proj
+
+
+def centerpoint_fusion_torch(P, levels, img_feats, calib, image_hw, cams, voxel_size, pc_range, image_scale, depth_thres,
+                             d_factors=(2, 4, 8), ifat_idx=(0, 2), act=None, msda=None, debug=None):
+    """VoxelWithPointProjection.forward, fuse_mode 'pfat' + ifat gate (CP/det3d/models/fusion/
+    voxel_with_point_projection.py:131-385, point_to_image_projection.py:63-231,
+    model_utils/attention.py:31-61,422-468) restated per sample and camera.
+    The torch path: P {name: tensor}; levels [(indices [n,4] numpy, features [n,C] tensor)] for x_conv2..4 (rows
+    batch-sorted); img_feats {cam: [B,256,h,w] tensor}; calib {cam: (lidar2cam [B,4,4], intrinsic [B,3,3])} numpy;
+    image_hw (H, W) of the network input image.  Parameters and features may be leaves with requires_grad: nothing is
+    detached between them and the result.  act / msda: see actr_forward_torch.
+    -> (fused features of the last level [n, C], {(level, camera): (grid [n, 2] int64, mask [n] bool)} over ALL rows of
+    the level -- the integer work, which does not depend on the precision of the floating-point stages)."""
+    import torch
+    import torch.nn.functional as F
+    first = next(iter(img_feats.values()))
+    B, dt = first.shape[0], first.dtype
+    h_, w_ = first.shape[2:]
+    n_last = len(levels) - 1
+    proj = centerpoint_projection(levels, calib, image_hw, (h_, w_), cams, voxel_size, pc_range, image_scale, depth_thres,
+                                  d_factors)
+    per = {}                    # (b, cam) -> dict
+    img_gated = {}
+    for ci, cam in enumerate(cams):
         for b in range(B):
-            img = _t(img_feats[cam][b])
-            h_, w_ = img.shape[1:]
+            img = img_feats[cam][b]
             # ---- image-side gate
             pt_img = None
             for li in ifat_idx:
                 ind, feat = levels[li]
-                sel = ind[:, 0] == b
-                g, m, p = proj[li][b]
-                vf = torch.cat([_t(feat[sel])[m], p[m]], 1)
-                canvas = torch.zeros(h_ + 1, w_ + 1, vf.shape[1])
-                gy, gx = g[m][:, 1], g[m][:, 0]
-                for j in range(len(vf)):                                          # sequential: last writer wins
-                    canvas[gy[j], gx[j]] = vf[j]
-                canvas = canvas[:-1, :-1].permute(2, 0, 1)[None]
+                sel = _t(ind[:, 0] == b)
+                g, m, p = proj[(li, ci)][b]
+                vf = torch.cat([feat[sel][m], p[m].to(dt)], 1)
+                # the reference writes the rows one after the other (canvas[gy[j], gx[j]] = vf[j]): the LAST row of a
+                # pixel stays.  Here: the last occurrence of every pixel, written once.
+                lin = (g[m][:, 1] * (w_ + 1) + g[m][:, 0]).numpy()
+                _, rev = np.unique(lin[::-1], return_index=True)
+                last = _t(len(lin) - 1 - rev)
+                canvas = vf.new_zeros(((h_ + 1) * (w_ + 1), vf.shape[1])).index_put((_t(lin)[last],), vf[last])
+                canvas = canvas.view(h_ + 1, w_ + 1, -1)[:-1, :-1].permute(2, 0, 1)[None]
                 if li != ifat_idx[-1]:
-                    canvas = F.conv2d(canvas, P("ifat.reduced_dim.%d.weight" % li), P("ifat.reduced_dim.%d.bias" % li))
+                    canvas = F.conv2d(canvas, P["ifat.reduced_dim.%d.weight" % li], P["ifat.reduced_dim.%d.bias" % li])
                 pt_img = canvas if pt_img is None else pt_img + canvas
-            pt_img = F.conv2d(pt_img, P("ifat.reduced_dim2.weight"), P("ifat.reduced_dim2.bias"))
-            gate = F.conv2d(img[None], P("ifat.reduced_dim3.weight"), P("ifat.reduced_dim3.bias"))
-            att = torch.sigmoid(F.conv2d(gate + pt_img, P("ifat.spatial_basic.weight"), P("ifat.spatial_basic.bias"), padding=1))
+            pt_img = F.conv2d(pt_img, P["ifat.reduced_dim2.weight"], P["ifat.reduced_dim2.bias"])
+            gate = F.conv2d(img[None], P["ifat.reduced_dim3.weight"], P["ifat.reduced_dim3.bias"])
+            att = torch.sigmoid(F.conv2d(gate + pt_img, P["ifat.spatial_basic.weight"], P["ifat.spatial_basic.bias"], padding=1))
             img = (img[None] * att)[0]
             img_gated[(b, ci)] = img
             ind, feat = levels[n_last]
-            sel = ind[:, 0] == b
-            g, m, p = proj[n_last][b]
-            per[(b, ci)] = dict(grid=g[m], pts=p[m], feat=_t(feat[sel])[m], mask=m,
-                                ifeat=img[:, g[m][:, 1], g[m][:, 0]].t())
+            sel = _t(ind[:, 0] == b)
+            g, m, p = proj[(n_last, ci)][b]
+            per[(b, ci)] = dict(grid=g[m], pts=p[m], feat=feat[sel][m], mask=m, ifeat=img[:, g[m][:, 1], g[m][:, 0]].t())
     if debug is not None:
         debug.update(per=per)
     ncam = len(cams)
     max_ne = max(len(v["grid"]) for v in per.values())
-    C = levels[n_last][1].shape[1]
-    h_, w_ = next(iter(img_feats.values())).shape[2:]
-    v_feat = np.zeros((B * ncam, max_ne, C), np.float32)
-    v_i = np.zeros((B * ncam, max_ne, 256), np.float32)
-    grid = np.zeros((B * ncam, max_ne, 2), np.float32)
-    pts = np.zeros((B * ncam, max_ne, 3), np.float32)
-    imgs = np.zeros((B * ncam, 256, h_, w_), np.float32)
-    for (b, ci), v in per.items():
-        n = len(v["grid"])
-        i = b * ncam + ci
-        v_feat[i, :n], v_i[i, :n], pts[i, :n] = v["feat"].numpy(), v["ifeat"].numpy(), v["pts"].numpy()
-        grid[i, :n] = v["grid"].float().numpy()
-        imgs[i] = img_gated[(b, ci)].numpy()
-    grid = (_t(grid) / torch.tensor([w_, h_], dtype=torch.float32)).numpy()
-    enh = actr_forward(sd, v_feat, grid, imgs, pts, v_i, prefix="pfat.")
+    order = [per[(b, ci)] for b in range(B) for ci in range(ncam)]                 # image index = b * ncam + camera
+    pad = lambda x: F.pad(x, (0, 0, 0, max_ne - len(x)))                           # noqa: E731
+    v_feat = torch.stack([pad(v["feat"]) for v in order])
+    v_i = torch.stack([pad(v["ifeat"]) for v in order])
+    pts = torch.stack([pad(v["pts"]) for v in order]).to(dt)
+    grid = torch.stack([pad(v["grid"].float()) for v in order])
+    grid = (grid / torch.tensor([w_, h_], dtype=torch.float32)).to(dt)
+    imgs = torch.stack([img_gated[(b, ci)] for b in range(B) for ci in range(ncam)])
+    enh = actr_forward_torch(P, v_feat, grid, imgs, pts, v_i, prefix="pfat.", act=act, msda=msda)
     ind, feat = levels[n_last]
-    out = np.array(feat, np.float32, copy=True)
+    out = feat
     for b in range(B):
-        rows = np.nonzero(ind[:, 0] == b)[0]
+        rows = _t(np.nonzero(ind[:, 0] == b)[0])
         for ci in range(ncam):
-            m = per[(b, ci)]["mask"].numpy()
-            out[rows[m]] += enh[b * ncam + ci][:int(m.sum())]
-    return out
+            m = per[(b, ci)]["mask"]
+            out = out.index_add(0, rows[m], enh[b * ncam + ci][:int(m.sum())])
+    work = {}
+    for (li, ci), parts in proj.items():
+        g_all = torch.zeros((len(levels[li][0]), 2), dtype=torch.long)
+        m_all = torch.zeros(len(levels[li][0]), dtype=torch.bool)
+        for b, (g, m, _) in enumerate(parts):
+            sel = _t(levels[li][0][:, 0] == b)
+            g_all[sel], m_all[sel] = g, m
+        work[(li, ci)] = (g_all, m_all)
+    return out, work
+
+
+def centerpoint_fusion(sd, levels, img_feats, calib, image_hw, cams, voxel_size, pc_range, image_scale, depth_thres,
+                       d_factors=(2, 4, 8), ifat_idx=(0, 2), debug=None):
+    """`centerpoint_fusion_torch` on numpy arrays, in fp32 with the numpy sampling oracle.
+    levels: [(indices [n,4], features [n,C])] for x_conv2..4 (rows batch-sorted); img_feats {cam: [B,256,h,w]};
+    calib {cam: (lidar2cam [B,4,4], intrinsic [B,3,3])}; image_hw (H, W) of the network input image.
+    Returns the fused features of the last level."""
+    P = {k: _t(v) for k, v in sd.items()}
+    levels = [(ind, _t(np.asarray(feat, np.float32))) for ind, feat in levels]
+    img_feats = {cam: _t(np.asarray(v, np.float32)) for cam, v in img_feats.items()}
+    out, _ = centerpoint_fusion_torch(P, levels, img_feats, calib, image_hw, cams, voxel_size, pc_range, image_scale,
+                                      depth_thres, d_factors, ifat_idx, msda=_msda_numpy, debug=debug)
+    return out.numpy()
 
 
 # ------------------------------------------------------------------------- TransFusion fusion layer (round 6)
