@@ -265,10 +265,10 @@ extern "C" int df3d_project_voxels(const int32_t *indices, int n, int batch, int
                                    const float *feat_scale, int32_t *grid_xy, uint8_t *mask, float *point_inv,
                                    float *depth, const float *aug_inv, void *stream_) {
   hipStream_t stream = (hipStream_t)stream_;
+  if (n == 0) return DF3D_OK;        // an empty voxel set: its per-row tensors have no storage (null pointers), nothing to write
   DF3D_CHECK_ARG(indices && lidar2cam && intrinsic && raw_hw && depth_thres && feat_scale && grid_xy && mask &&
                      point_inv && scale_xyz && pc_min,
                  "project_voxels: null argument");
-  if (n == 0) return DF3D_OK;
   ProjArgs a = {indices, n, batch, ncam, scale_xyz[0], scale_xyz[1], scale_xyz[2], pc_min[0], pc_min[1], pc_min[2],
                 lidar2cam, intrinsic, raw_hw, depth_thres, image_scale, feat_scale, grid_xy, mask, point_inv, depth, aug_inv};
   hipLaunchKernelGGL(project_voxels_kernel, dim3(cdiv((long long)n * ncam, 256)), dim3(256), 0, stream, a);

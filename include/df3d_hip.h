@@ -681,7 +681,13 @@ int df3d_gather_points_grad(const float *grad_out, const int32_t *idx, int B, in
  * df3d_assemble_queries: zero-padded per-camera query tensors for ACTR; pos [ncam,n] i32 = slot
  *   of a visible voxel inside its (b, cam) list (exclusive count of visible rows before it).
  * df3d_fusion_writeback: out[row] = features[row] + sum_cam enh[b*ncam+cam][pos] in camera order
- *   (voxel_with_point_projection.py:368-377).
+ *   (voxel_with_point_projection.py:368-377); a visible row whose slot is >= max_ne adds nothing (the assembly entries
+ *   drop such a row in the same way).
+ * Pixel range: with feat_scale = (W / W_raw, H / H_raw) df3d_project_voxels gives a visible row a pixel inside the
+ *   [H, W] feature map (0 < x_raw < W_raw truncates to 0 <= x < W).  The scatter entries (df3d_scatter_to_image,
+ *   df3d_scatter_winner, df3d_gate_scatter*) test the range themselves and drop a visible row outside it; the assembly
+ *   entries (df3d_assemble_queries*) and df3d_query_pixel_rows do NOT: they index the map with the pixel as given, so
+ *   their grid_xy must come from that projection, or otherwise keep the visible rows inside the map.
  * ---------------------------------------------------------------------------------- */
 int df3d_project_voxels(const int32_t *indices, int n, int batch, int ncam,
                         const float *scale_xyz_host, const float *pc_min_host,
