@@ -474,6 +474,275 @@ __global__ __launch_bounds__(256) void msda_bin_reduce_kernel(MsdaBinArgs a) {
   }
 }
 
+// ---------------------------------------------------------------------------------------------------------
+// The same without global atomics for L >= 1 levels (L * P <= 16) and heads of 16 / 32 / 64 channels (msda_binml_*).  A bin is
+// a (level, tile, head): the levels' tiles are numbered one level after the other (tbase), every level has its own map size,
+// tile row length and first pixel, and grad_value [N][S][M][D] is still written exactly once because the levels tile S without
+// gaps (checked on the host: df3d_ms_deform_attn_backward_plan).  A head of D = 16 * NS channels is NS column slices of the same
+// product: the A operand (the bilinear weights) is formed once per point and row tile and multiplies NS gradient rows, the
+// slab is [81][D].  The scan kernel above is shared (its bins are just numbered 0 .. nbm - 1).
+//
+// ORDERED (df3d_ms_deform_attn_backward_binned_ml(..., ordered = 1)): the scatter of msda_bin*_kernel leaves the points of a bin
+// in the order in which lanes and workgroups won LDS / global integer atomics, and the fp32 sums of the accumulate kernel follow
+// that order.  msda_bin_sort_kernel puts every bin's packed ids (q << 4 | lp, unique within a bin) in ascending order first; the
+// work items are then every MB_CHUNK ids of that sequence, so grad_value is a function of the inputs alone.  A workgroup per
+// bin: <= 64 ids are ranked by counting inside one wave, <= 1024 go through a bitonic network in LDS, and a larger bin (the
+// pile-up on the unseen voxels' reference point: thousands to tens of thousands of ids) is written out from a bit directory --
+// one bit per possible id in 256 Ki-id windows, set with LDS integer atomics, read back in order with a popcount scan: linear
+// in the ids (the network's log^2 passes over 8192 ids cost more than the rest of the backward at the training shape).
+constexpr int MB_LMAX = 16, MS_WORDS = 8192, MS_WINDOW = MS_WORDS * 32, MS_NETWORK = 1024;
+#define MS_PHYS(i) ((i) + ((i) >> 5))                         // (a thread walks 32 consecutive words: one pad word per 32)
+
+struct MsdaMlArgs {
+  const float *loc, *aw, *gout;
+  const unsigned char *nz;
+  float *gvalue;
+  int N, S, M, D, Lq, L, P, LP, nbm, mw;
+  int H[MB_LMAX], W[MB_LMAX], tx[MB_LMAX], start[MB_LMAX], tbase[MB_LMAX + 1];   // per level; tbase: first tile of the level
+  unsigned *count, *cursor, *offset, *binw, *nwork, *work;   // as in MsdaBinArgs
+  const unsigned *items;                                      // what the accumulate kernel reads (the ordered copy if there is one)
+  unsigned *scattered, *sorted;                               // [N][ppm] each: the scatter's output; the ordered copy
+  float *slabs;                                               // [N][mw][MB_FOOT][D]
+};
+
+__device__ __forceinline__ bool mb_point_hw(int H, int W, float lx, float ly, int &hl, int &wl, float &lh, float &lw) {
+  const float h_im = ly * (float)H - 0.5f, w_im = lx * (float)W - 0.5f;
+  const bool in = h_im > -1.f && w_im > -1.f && h_im < (float)H && w_im < (float)W;
+  hl = (int)floorf(h_im), wl = (int)floorf(w_im);
+  lh = h_im - (float)hl, lw = w_im - (float)wl;
+  return in;
+}
+__device__ __forceinline__ int mb_level_of_tile(const MsdaMlArgs &a, int tile) {
+  int l = 0;
+  while (l + 1 < a.L && tile >= a.tbase[l + 1]) ++l;
+  return l;
+}
+
+// msda_bin_kernel with the level of a point deciding map size and tile numbering
+template <bool SCATTER>
+__global__ __launch_bounds__(256) void msda_binml_kernel(MsdaMlArgs a) {
+  extern __shared__ unsigned mb_hist[];                      // [nbm] counts, then (scatter) [nbm] bases
+  const int n = blockIdx.y, tid = threadIdx.x, nbm = a.nbm;
+  for (int t = tid; t < nbm; t += 256) mb_hist[t] = 0u;
+  __syncthreads();
+  const long long g = (long long)blockIdx.x * 256 + tid;     // (q, m) of this map
+  const bool live = g < (long long)a.Lq * a.M && a.nz[(size_t)n * a.Lq * a.M + g];
+  const int m = (int)(g % a.M);
+  const float *loc = a.loc + ((size_t)n * a.Lq * a.M + (size_t)(live ? g : 0)) * a.LP * 2;
+  unsigned rank[16];
+  int bin[16];
+#pragma unroll 1
+  for (int lp = 0; lp < a.LP; ++lp) {
+    bin[lp & 15] = -1;
+    if (!live) continue;
+    const int l = lp / a.P;
+    int hl, wl;
+    float lh, lw;
+    if (!mb_point_hw(a.H[l], a.W[l], loc[lp * 2], loc[lp * 2 + 1], hl, wl, lh, lw)) continue;
+    const int t = (a.tbase[l] + (max(hl, 0) / MB_T) * a.tx[l] + max(wl, 0) / MB_T) * a.M + m;
+    bin[lp & 15] = t;
+    rank[lp & 15] = atomicAdd(&mb_hist[t], 1u);
+  }
+  __syncthreads();
+  if (!SCATTER) {
+    for (int t = tid; t < nbm; t += 256)
+      if (mb_hist[t]) atomicAdd(&a.count[(size_t)n * nbm + t], mb_hist[t]);
+    return;
+  }
+  unsigned *base = mb_hist + nbm;
+  for (int t = tid; t < nbm; t += 256)
+    base[t] = mb_hist[t] ? a.offset[(size_t)n * nbm + t] + atomicAdd(&a.cursor[(size_t)n * nbm + t], mb_hist[t]) : 0u;
+  __syncthreads();
+  if (!live) return;
+  const unsigned q = (unsigned)(g / a.M);
+  unsigned *items = a.scattered + (size_t)n * a.Lq * a.M * a.LP;
+  for (int lp = 0; lp < a.LP; ++lp)
+    if (bin[lp & 15] >= 0) items[base[bin[lp & 15]] + rank[lp & 15]] = (q << 4) | (unsigned)lp;
+}
+
+// a workgroup = one bin of map blockIdx.y: its ids from `scattered` to `sorted`, ascending (see ORDERED above).  Two launches
+// over the bins: BIG = false takes the bins of <= MS_NETWORK ids (nearly all of them) with 4 KB of LDS, BIG = true the rest with
+// the 33 KB of the bit directory -- one kernel for both holds every small bin to the large ones' four workgroups per CU.
+template <bool BIG>
+__global__ __launch_bounds__(256) void msda_bin_sort_kernel(MsdaMlArgs a) {
+  constexpr int WORDS = BIG ? MS_WORDS : MS_NETWORK;
+  __shared__ unsigned s[WORDS + WORDS / 32];
+  __shared__ unsigned s_wave[4];
+  const int n = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const size_t bi = (size_t)n * a.nbm + blockIdx.x, first = (size_t)n * a.Lq * a.M * a.LP + a.offset[bi];
+  const unsigned c = a.count[bi];
+  const unsigned *src = a.scattered + first;
+  unsigned *dst = a.sorted + first;
+  if (c == 0 || BIG != (c > (unsigned)MS_NETWORK)) return;
+  if (!BIG && c <= 64) {                                       // rank = the number of smaller ids (one wave, no LDS)
+    if (wave) return;
+    const unsigned key = (unsigned)lane < c ? src[lane] : 0xffffffffu;
+    unsigned rank = 0;
+    for (unsigned j = 0; j < c; ++j) rank += (unsigned)__shfl(key, (int)j, 64) < key ? 1u : 0u;
+    if ((unsigned)lane < c) dst[rank] = key;
+    return;
+  }
+  if (!BIG) {                                                  // bitonic network over the next power of two (pad = ~0 > any id)
+    unsigned n2 = 128;
+    while (n2 < c) n2 <<= 1;
+    for (unsigned i = tid; i < n2; i += 256) s[i] = i < c ? src[i] : 0xffffffffu;
+    __syncthreads();
+    for (unsigned k = 2; k <= n2; k <<= 1)
+      for (unsigned j = k >> 1; j > 0; j >>= 1) {
+        for (unsigned i = tid; i < n2; i += 256) {
+          const unsigned p = i ^ j;
+          if (p > i) {
+            const unsigned x = s[i], y = s[p];
+            if ((x > y) == ((i & k) == 0u)) s[i] = y, s[p] = x;
+          }
+        }
+        __syncthreads();
+      }
+    for (unsigned i = tid; i < c; i += 256) dst[i] = s[i];
+    return;
+  }
+  const unsigned nkeys = (unsigned)a.Lq << 4;                  // (Lq <= 2^20 in ordered mode: no overflow, <= 64 windows)
+  unsigned done = 0;
+  for (unsigned k0 = 0; k0 < nkeys; k0 += MS_WINDOW) {
+    for (int i = tid; i < WORDS + WORDS / 32; i += 256) s[i] = 0u;
+    __syncthreads();
+    for (unsigned i = tid; i < c; i += 256) {
+      const unsigned k = src[i] - k0;                          // (an id below the window wraps to a large number)
+      if (k < (unsigned)MS_WINDOW) atomicOr(&s[MS_PHYS(k >> 5)], 1u << (k & 31u));
+    }
+    __syncthreads();
+    const unsigned w0 = tid * 32;                              // this thread's 32 words = 1024 ids of the window
+    unsigned mine = 0;
+    for (unsigned w = 0; w < 32; ++w) mine += __popc(s[MS_PHYS(w0 + w)]);
+    unsigned incl = mine;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+      const unsigned up = __shfl_up(incl, d);
+      if (lane >= d) incl += up;
+    }
+    if (lane == 63) s_wave[wave] = incl;
+    __syncthreads();
+    unsigned run = done + incl - mine;
+    for (int w = 0; w < wave; ++w) run += s_wave[w];
+    done += s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];
+    for (unsigned w = 0; w < 32; ++w) {
+      unsigned bits = s[MS_PHYS(w0 + w)];
+      while (bits) {
+        dst[run++] = k0 + ((w0 + w) << 5) + (unsigned)(__ffs(bits) - 1);
+        bits &= bits - 1u;
+      }
+    }
+    __syncthreads();                                           // (s and s_wave are rewritten by the next window)
+  }
+}
+
+// msda_bin_accumulate_kernel for a (level, tile, head) bin and NS slices of 16 channels
+template <int NS>
+struct MbPointsMl {
+  float lx[4], ly[4], aw[4], g[4][NS];
+};
+template <int NS>
+__global__ __launch_bounds__(256) void msda_binml_accumulate_kernel(MsdaMlArgs a) {
+  constexpr int D = NS * 16;
+  const int n = blockIdx.y, lane = threadIdx.x & 63, wid = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (wid >= (int)a.nwork[n]) return;
+  const unsigned *work = a.work + ((size_t)n * a.mw + wid) * 3;
+  const unsigned bin = work[0], first = work[1], last = work[2];
+  const int tg = bin / a.M, m = bin - tg * a.M, lv = mb_level_of_tile(a, tg), t = tg - a.tbase[lv];
+  const int H = a.H[lv], W = a.W[lv], tx = a.tx[lv];
+  const int y0 = (t / tx) * MB_T, x0 = (t % tx) * MB_T;
+  const int i16 = lane & 15, kg = lane >> 4;
+  const unsigned *items = a.items + (size_t)n * a.Lq * a.M * a.LP;
+  auto load_ids = [&](unsigned i0, unsigned(&id)[4]) {
+#pragma unroll
+    for (int u = 0; u < 4; ++u) id[u] = items[min(i0 + 4 * u + kg, last - 1)];
+  };
+  auto load_points = [&](const unsigned(&id)[4], MbPointsMl<NS> &v) {
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const size_t qm = ((size_t)n * a.Lq + (id[u] >> 4)) * a.M + m, lp = id[u] & 15u;
+      const float2 l = *(const float2 *)(a.loc + (qm * a.LP + lp) * 2);
+      v.lx[u] = l.x, v.ly[u] = l.y;
+      v.aw[u] = a.aw[qm * a.LP + lp];
+#pragma unroll
+      for (int s = 0; s < NS; ++s) v.g[u][s] = a.gout[qm * D + s * 16 + i16];
+    }
+  };
+  f32x4 acc[NS][6];
+#pragma unroll
+  for (int s = 0; s < NS; ++s)
+#pragma unroll
+    for (int rt = 0; rt < 6; ++rt) acc[s][rt] = (f32x4){0.f, 0.f, 0.f, 0.f};
+  int prow[6], pcol[6];                                        // footprint row / column of this lane's pixel in row tile rt
+#pragma unroll
+  for (int rt = 0; rt < 6; ++rt) prow[rt] = (rt * 16 + i16) / (MB_T + 1), pcol[rt] = (rt * 16 + i16) % (MB_T + 1);
+  unsigned id[4];
+  MbPointsMl<NS> cur, nxt;
+  load_ids(first, id);
+  load_points(id, cur);
+  load_ids(first + 16, id);
+  for (unsigned i0 = first; i0 < last; i0 += 16) {
+    load_points(id, nxt);
+    load_ids(i0 + 32, id);
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      int hl, wl;
+      float lh, lw;
+      mb_point_hw(H, W, cur.lx[u], cur.ly[u], hl, wl, lh, lw);  // (in bounds: it was binned)
+      const float scale = i0 + 4 * u + kg < last ? cur.aw[u] : 0.f;
+      const int ry = hl - y0, rx = wl - x0, ry1 = ry + 1, rx1 = rx + 1;      // footprint row / column of the top-left corner
+      const float wt = hl >= 0 ? 1.f - lh : 0.f, wb = hl + 1 <= H - 1 ? lh : 0.f;
+      const float wl_ = wl >= 0 ? 1.f - lw : 0.f, wr = wl + 1 <= W - 1 ? lw : 0.f;
+#pragma unroll
+      for (int rt = 0; rt < 6; ++rt) {
+        float wy = prow[rt] == ry ? wt : 0.f, wx = pcol[rt] == rx ? wl_ : 0.f;
+        wy = prow[rt] == ry1 ? wb : wy;
+        wx = pcol[rt] == rx1 ? wr : wx;
+        const float wgt = wy * wx;                             // the A operand: once per point and row tile, NS products
+#pragma unroll
+        for (int s = 0; s < NS; ++s)
+          acc[s][rt] = __builtin_amdgcn_mfma_f32_16x16x4f32(wgt, cur.g[u][s] * scale, acc[s][rt], 0, 0, 0);
+      }
+    }
+    cur = nxt;
+  }
+  float *slab = a.slabs + ((size_t)n * a.mw + wid) * MB_FOOT * D;
+#pragma unroll
+  for (int s = 0; s < NS; ++s)
+#pragma unroll
+    for (int rt = 0; rt < 6; ++rt)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int px = rt * 16 + 4 * kg + r;
+        if (px < MB_FOOT) slab[px * D + s * 16 + i16] = acc[s][rt][r];
+      }
+}
+
+// msda_bin_reduce_kernel for a tile of any level: M * D channels per pixel, the level's pixels start at a.start[level]
+__global__ __launch_bounds__(256) void msda_binml_reduce_kernel(MsdaMlArgs a) {
+  const int n = blockIdx.y, tg = blockIdx.x, lv = mb_level_of_tile(a, tg), t = tg - a.tbase[lv];
+  const int H = a.H[lv], W = a.W[lv], tx = a.tx[lv];
+  const int tyi = t / tx, txi = t - tyi * tx, y0 = tyi * MB_T, x0 = txi * MB_T;
+  const int D = a.D, C = a.M * D, C4 = C / 4;
+  const unsigned *binw = a.binw + (size_t)n * (a.nbm + 1);
+  const float *slabs = a.slabs + (size_t)n * a.mw * MB_FOOT * D;
+  for (int i = threadIdx.x; i < MB_T * MB_T * C4; i += 256) {
+    const int px = i / C4, c = (i - px * C4) * 4, ly = px / MB_T, lx = px - ly * MB_T, m = c / D, cc = c - m * D;
+    if (y0 + ly >= H || x0 + lx >= W) continue;
+    f32x4 acc = (f32x4){0.f, 0.f, 0.f, 0.f};
+    auto add = [&](int b, int fy, int fx) {
+      const unsigned w0 = binw[b], w1 = binw[b + 1];
+      for (unsigned w = w0; w < w1; ++w)
+        acc += *(const f32x4 *)(slabs + ((size_t)w * MB_FOOT + fy * (MB_T + 1) + fx) * D + cc);
+    };
+    add(tg * a.M + m, ly, lx);
+    if (ly == 0 && tyi > 0) add((tg - tx) * a.M + m, MB_T, lx);
+    if (lx == 0 && txi > 0) add((tg - 1) * a.M + m, ly, MB_T);
+    if (ly == 0 && lx == 0 && tyi > 0 && txi > 0) add((tg - tx - 1) * a.M + m, MB_T, MB_T);
+    *(f32x4 *)(a.gvalue + ((size_t)n * a.S + (size_t)a.start[lv] + (size_t)(y0 + ly) * W + x0 + lx) * C + c) = acc;
+  }
+}
+
 // any D: one thread per channel, global atomics for all three gradients (the reference's fallback,
 // ms_deform_im2col_cuda.cuh:818-921)
 __global__ __launch_bounds__(256) void msda_bwd_scalar_kernel(MsdaBwdArgs a) {
@@ -667,6 +936,158 @@ extern "C" int df3d_ms_deform_attn_backward_binned(const float *value, const int
   hipLaunchKernelGGL(msda_bin_kernel<true>, bgrid, dim3(256), nbm * 8, stream, b);
   hipLaunchKernelGGL(msda_bin_accumulate_kernel, dim3(cdiv(mw, 4), N), dim3(256), 0, stream, b);
   hipLaunchKernelGGL(msda_bin_reduce_kernel, dim3(tiles, N), dim3(256), 0, stream, b);
+  DF3D_LAUNCH_CHECK();
+  return DF3D_OK;
+}
+
+// ---- binned backward, any number of levels / heads of 16, 32, 64 channels / ordered: see msda_binml_* above -------------------
+// What serves a shape.  Host only (no HIP call).  mode: 0 = default, 1 = atomic, 2 = ordered ("sorted").  -> 0 atomic kernels,
+// 1 binned, 2 binned + ordered, -1 ordered asked for and not served (df3d_last_error names the limit that failed).
+static const char *mb_limit(int N, int S, int M, int D, int Lq, int L, int P, const int64_t *hw, const int64_t *start, bool ordered,
+                            char *buf, size_t nbuf) {
+#define MB_LIMIT(cond, ...)             \
+  if (!(cond)) {                        \
+    snprintf(buf, nbuf, __VA_ARGS__);   \
+    return buf;                         \
+  }
+  MB_LIMIT(D == 16 || D == 32 || D == 64, "head width D = %d (served: 16, 32, 64)", D);
+  MB_LIMIT(L >= 1 && P >= 1 && (long long)L * P <= 16, "L * P = %d * %d points per query and head (limit 16)", L, P);
+  MB_LIMIT(N <= 65535, "N = %d maps (limit 65535)", N);
+  MB_LIMIT(Lq < (1 << 28) && (long long)Lq * M * L * P < (1LL << 31), "Lq = %d queries (limits: Lq < 2^28, Lq * M * L * P < 2^31)", Lq);
+  MB_LIMIT(!ordered || Lq <= (1 << 20), "Lq = %d queries (limit of the ordered pass: 2^20)", Lq);
+  long long tiles = 0, pixels = 0;
+  for (int l = 0; l < L; ++l) {
+    const long long H = hw[l * 2], W = hw[l * 2 + 1];
+    MB_LIMIT(H > 0 && W > 0 && H < (1 << 24) && W < (1 << 24), "level %d is %lld x %lld", l, H, W);
+    MB_LIMIT(start[l] == pixels, "level_start_index[%d] = %lld, not the %lld pixels of the levels before it (grad_value is "
+             "written once: the levels must tile S without gaps)", l, (long long)start[l], pixels);
+    tiles += ((H + MB_T - 1) / MB_T) * ((W + MB_T - 1) / MB_T);
+    pixels += H * W;
+    MB_LIMIT(tiles * M <= 7680, "M * tiles = %d * %lld bins up to level %d (limit 7680: the LDS histogram)", M, tiles, l);
+  }
+  MB_LIMIT(pixels == S, "S = %d pixels per map, the levels hold %lld (grad_value is written once: no pixel outside the levels)", S,
+           pixels);
+#undef MB_LIMIT
+  return nullptr;
+}
+
+extern "C" int df3d_ms_deform_attn_backward_plan(int N, int S, int M, int D, int Lq, int L, int P, const int64_t *level_hw,
+                                                 const int64_t *level_start, int mode) {
+  if (mode == 1) return 0;
+  char buf[256];
+  const bool sane = N >= 0 && S > 0 && M > 0 && D > 0 && Lq >= 0 && L > 0 && P > 0 && level_hw && level_start && mode >= 0 && mode <= 2;
+  const char *why = sane ? mb_limit(N, S, M, D, Lq, L, P, level_hw, level_start, mode == 2, buf, sizeof buf) : "bad sizes / null argument";
+  if (!why) return mode == 2 ? 2 : 1;
+  if (mode != 2) return 0;
+  set_error("ms_deform_attn_backward: the ordered value gradient does not serve %s", why);
+  return -1;
+}
+
+static size_t mb_nbm_ml(int M, int L, const int64_t *hw) {
+  size_t tiles = 0;
+  for (int l = 0; l < L; ++l) tiles += (size_t)cdiv((int)hw[l * 2], MB_T) * cdiv((int)hw[l * 2 + 1], MB_T);
+  return tiles * M;
+}
+static size_t mb_mw_ml(int M, int Lq, int L, int P, const int64_t *hw) { return mb_nbm_ml(M, L, hw) + (size_t)Lq * M * L * P / MB_CHUNK + 1; }
+
+extern "C" size_t df3d_ms_deform_attn_backward_binned_ml_workspace_bytes(int N, int M, int Lq, int L, int P, const int64_t *level_hw,
+                                                                         int ordered) {
+  if (!level_hw || N < 0 || M <= 0 || Lq < 0 || L <= 0 || P <= 0) return 0;
+  const size_t nbm = mb_nbm_ml(M, L, level_hw), n = (size_t)N;
+  return mb_align(n * Lq * M) + mb_align(n * nbm * 4) * 3 + mb_align(n * (nbm + 1) * 4) + mb_align(n * 4) +
+         mb_align(n * mb_mw_ml(M, Lq, L, P, level_hw) * 12) + mb_align(n * Lq * M * L * P * 4) * (ordered ? 2 : 1);
+}
+/* + the work items' footprints: N * mw * 81 * D floats */
+extern "C" size_t df3d_ms_deform_attn_backward_binned_ml_slab_bytes(int N, int M, int D, int Lq, int L, int P, const int64_t *level_hw) {
+  if (!level_hw || N < 0 || M <= 0 || D <= 0 || Lq < 0 || L <= 0 || P <= 0) return 0;
+  return (size_t)N * mb_mw_ml(M, Lq, L, P, level_hw) * MB_FOOT * D * 4;
+}
+
+extern "C" int df3d_ms_deform_attn_backward_binned_ml(const float *value, const int64_t *spatial_shapes, const int64_t *level_start_index,
+                                                      const float *sampling_loc, const float *attn_weight, const float *grad_output,
+                                                      const int64_t *level_hw, const int64_t *level_start, int N, int M, int D, int Lq,
+                                                      int L, int P, int ordered, float *grad_value, float *grad_sampling_loc,
+                                                      float *grad_attn_weight, void *workspace, size_t workspace_bytes, float *slabs,
+                                                      void *stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  DF3D_CHECK_ARG(N >= 0 && M > 0 && D > 0 && Lq >= 0 && L > 0 && P > 0 && level_hw && level_start,
+                 "ms_deform_attn_backward_binned_ml: bad sizes / null level arrays");
+  long long S = 0;
+  for (int l = 0; l < L && l < MB_LMAX; ++l) S += level_hw[l * 2] * level_hw[l * 2 + 1];
+  char buf[256];
+  const char *why = S > 0 && S < (1LL << 31) ? mb_limit(N, (int)S, M, D, Lq, L, P, level_hw, level_start, ordered != 0, buf, sizeof buf)
+                                              : "bad level sizes";
+  DF3D_CHECK_ARG(!why, "ms_deform_attn_backward_binned_ml: not served: %s", why);
+  if (N == 0) return DF3D_OK;
+  DF3D_CHECK_ARG(value && spatial_shapes && level_start_index && grad_value, "ms_deform_attn_backward_binned_ml: null argument");
+  const int C = M * D;
+  if (Lq == 0) {
+    DF3D_HIP(hipMemsetAsync(grad_value, 0, (size_t)N * S * C * sizeof(float), stream));
+    return DF3D_OK;
+  }
+  DF3D_CHECK_ARG(sampling_loc && attn_weight && grad_output && grad_sampling_loc && grad_attn_weight && workspace && slabs,
+                 "ms_deform_attn_backward_binned_ml: null argument");
+  DF3D_CHECK_ARG(workspace_bytes >= df3d_ms_deform_attn_backward_binned_ml_workspace_bytes(N, M, Lq, L, P, level_hw, ordered),
+                 "ms_deform_attn_backward_binned_ml: workspace too small");
+  const size_t nbm = mb_nbm_ml(M, L, level_hw), n = (size_t)N, ppm = (size_t)Lq * M * L * P;
+  const int mw = (int)mb_mw_ml(M, Lq, L, P, level_hw);
+  char *w = (char *)workspace;
+  unsigned char *nz = (unsigned char *)w;
+  w += mb_align(n * Lq * M);
+  unsigned *count = (unsigned *)w;
+  w += mb_align(n * nbm * 4);
+  unsigned *cursor = (unsigned *)w;                            // (adjacent to `count`: one memset clears both)
+  w += mb_align(n * nbm * 4);
+  unsigned *offset = (unsigned *)w;
+  w += mb_align(n * nbm * 4);
+  unsigned *binw = (unsigned *)w;
+  w += mb_align(n * (nbm + 1) * 4);
+  unsigned *nwork = (unsigned *)w;
+  w += mb_align(n * 4);
+  unsigned *work = (unsigned *)w;
+  w += mb_align(n * mw * 12);
+  unsigned *scattered = (unsigned *)w;
+  w += mb_align(n * ppm * 4);
+  unsigned *sorted = ordered ? (unsigned *)w : nullptr;
+  DF3D_HIP(hipMemsetAsync(count, 0, mb_align(n * nbm * 4) * 2, stream));
+  MsdaBwdArgs g = {value, spatial_shapes, level_start_index, sampling_loc, attn_weight, grad_output,
+                   grad_value, grad_sampling_loc, grad_attn_weight, N, (int)S, M, D, Lq, L, P, nz};
+  const long long total = (long long)N * Lq * M * (D / 4);
+  MsdaMlArgs b = {};
+  b.loc = sampling_loc, b.aw = attn_weight, b.gout = grad_output, b.nz = nz, b.gvalue = grad_value;
+  b.N = N, b.S = (int)S, b.M = M, b.D = D, b.Lq = Lq, b.L = L, b.P = P, b.LP = L * P, b.nbm = (int)nbm, b.mw = mw;
+  int tiles = 0;
+  for (int l = 0; l < L; ++l) {
+    b.H[l] = (int)level_hw[l * 2], b.W[l] = (int)level_hw[l * 2 + 1], b.tx[l] = cdiv(b.W[l], MB_T), b.start[l] = (int)level_start[l];
+    b.tbase[l] = tiles;
+    tiles += b.tx[l] * cdiv(b.H[l], MB_T);
+  }
+  for (int l = L; l <= MB_LMAX; ++l) b.tbase[l] = tiles;
+  b.count = count, b.cursor = cursor, b.offset = offset, b.binw = binw, b.nwork = nwork, b.work = work;
+  b.scattered = scattered, b.sorted = sorted, b.items = ordered ? sorted : scattered, b.slabs = slabs;
+  MsdaBinArgs sc = {};                                         // the scan kernel's view: nbm = tiles * M bins, numbered through
+  sc.M = M, sc.tiles = tiles, sc.count = count, sc.offset = offset, sc.binw = binw, sc.nwork = nwork, sc.work = work, sc.mw = mw;
+  const dim3 bgrid(cdiv((long long)Lq * M, 256), N), wgrid(cdiv(mw, 4), N);
+  // location / weight gradients + the groups that carry a gradient (the gather half of the col2im)
+  switch (D) {
+#define DF3D_MSDA_ML_CASE(DD)                                                                                              \
+  case DD:                                                                                                                 \
+    hipLaunchKernelGGL((msda_bwd_vec4_kernel<DD / 4, true>), dim3(cdiv(total, 256)), dim3(256), 0, stream, g);             \
+    hipLaunchKernelGGL(msda_binml_kernel<false>, bgrid, dim3(256), nbm * 4, stream, b);                                    \
+    hipLaunchKernelGGL(msda_bin_scan_kernel, dim3(N), dim3(1024), 0, stream, sc);                                          \
+    hipLaunchKernelGGL(msda_binml_kernel<true>, bgrid, dim3(256), nbm * 8, stream, b);                                     \
+    if (ordered) {                                                                                                         \
+      hipLaunchKernelGGL(msda_bin_sort_kernel<false>, dim3(nbm, N), dim3(256), 0, stream, b);                              \
+      hipLaunchKernelGGL(msda_bin_sort_kernel<true>, dim3(nbm, N), dim3(256), 0, stream, b);                               \
+    }                                                                                                                      \
+    hipLaunchKernelGGL(msda_binml_accumulate_kernel<DD / 16>, wgrid, dim3(256), 0, stream, b);                             \
+    break;
+    DF3D_MSDA_ML_CASE(16)
+    DF3D_MSDA_ML_CASE(32)
+    DF3D_MSDA_ML_CASE(64)
+#undef DF3D_MSDA_ML_CASE
+  }
+  hipLaunchKernelGGL(msda_binml_reduce_kernel, dim3(tiles, N), dim3(256), 0, stream, b);
   DF3D_LAUNCH_CHECK();
   return DF3D_OK;
 }

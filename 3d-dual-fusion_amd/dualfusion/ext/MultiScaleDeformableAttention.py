@@ -27,7 +27,8 @@ def ms_deform_attn_forward(value, spatial_shapes, level_start_index, sampling_lo
 
 @runtime_errors
 def ms_deform_attn_backward(value, spatial_shapes, level_start_index, sampling_loc, attn_weight, grad_output, im2col_step):
-    """-> [grad_value, grad_sampling_loc, grad_attn_weight]."""
+    """-> [grad_value, grad_sampling_loc, grad_attn_weight].  The kernels are `ops.msda_backward_plan`'s choice (DF3D_MSDA_BWD =
+    binned | atomic | sorted; "sorted", the bit-reproducible value gradient, also under torch.use_deterministic_algorithms)."""
     _check(value, spatial_shapes, level_start_index, sampling_loc, attn_weight)
     need_cuda_contiguous(grad_output, "grad_output")
     return list(_ops.ms_deform_attn_backward(value, spatial_shapes, level_start_index, sampling_loc, attn_weight, grad_output))

@@ -19,7 +19,8 @@ class MSDeformAttnFunction(Function):
     """forward(value, spatial_shapes, level_start_index, sampling_locations, attention_weights,
     im2col_step) -> [N, Lq, M*D].  im2col_step is accepted for signature parity; the HIP kernels
     need no batch chunking.  backward -> (grad_value, None, None, grad_sampling_loc, grad_attn_weight, None) like
-    ms_deform_attn_func.py:31-38 (csrc/msda.hip, df3d_ms_deform_attn_backward)."""
+    ms_deform_attn_func.py:31-38 (csrc/msda.hip; which kernels: ops.msda_backward_plan, DF3D_MSDA_BWD = binned | atomic |
+    sorted, "sorted" also under torch.use_deterministic_algorithms)."""
 
     @staticmethod
     def forward(ctx, value, value_spatial_shapes, value_level_start_index, sampling_locations, attention_weights,

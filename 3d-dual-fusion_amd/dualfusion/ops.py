@@ -1837,8 +1837,74 @@ def level_shapes_on_host(spatial_shapes):
     return hit[0]
 
 
+_LEVEL_STARTS = {}
+
+
+def level_starts_on_host(level_start_index):
+    """`level_start_index` as Python ints, cached like `level_shapes_on_host`: one copy to the host per distinct tensor."""
+    key = (level_start_index.data_ptr(), level_start_index._version, tuple(level_start_index.shape), str(level_start_index.device))
+    hit = _LEVEL_STARTS.get(key)
+    if hit is None:
+        if len(_LEVEL_STARTS) >= 64:
+            _LEVEL_STARTS.clear()
+        hit = _LEVEL_STARTS[key] = ([int(v) for v in level_start_index.cpu().tolist()], level_start_index)
+    return hit[0]
+
+
+_MSDA_BWD_MODES = {"binned": 0, "atomic": 1, "sorted": 2}
+_MSDA_BWD_PLANS = {0: "atomic", 1: "binned", 2: "sorted"}
+_msda_bwd_warned = False
+
+
+def msda_backward_mode():
+    """"binned" | "atomic" | "sorted": DF3D_MSDA_BWD (read per call; unset = binned), and "sorted" -- the bit-reproducible value
+    gradient -- whenever torch.use_deterministic_algorithms is on and the variable does not say otherwise."""
+    mode = os.environ.get("DF3D_MSDA_BWD")
+    if mode is None:
+        return "sorted" if torch.are_deterministic_algorithms_enabled() else "binned"
+    if mode not in _MSDA_BWD_MODES:
+        raise _lib.Df3dError("DF3D_MSDA_BWD=%r: expected one of binned, atomic, sorted" % (mode,))
+    return mode
+
+
+def _i64_arr(values):
+    arr = (ctypes.c_int64 * max(1, len(values)))(*[int(v) for v in values])
+    return ctypes.cast(arr, ctypes.c_void_p), arr                    # keep `arr` alive in the caller
+
+
+def msda_backward_plan(N, S, M, D, Lq, L, P, level_hw, level_start, mode=None):
+    """What `ms_deform_attn_backward` runs for a shape: "atomic" (one fp32 atomic per contribution), "binned" (no global
+    atomics) or "sorted" (binned, points of a bin summed in ascending id order: reproducible bit for bit) -- the library's choice
+    (df3d_ms_deform_attn_backward_plan; needs no GPU).  level_hw [(H, W)] * L and level_start [L] are host values; mode None =
+    `msda_backward_mode()`.  A shape the ordered path does not serve raises Df3dError naming the limit -- or, under
+    torch.use_deterministic_algorithms(True, warn_only=True), warns once and returns "atomic"."""
+    global _msda_bwd_warned
+    if mode is None:
+        mode = msda_backward_mode()
+    hw, keep_hw = _i64_arr([v for pair in level_hw for v in pair][:2 * L])
+    st, keep_st = _i64_arr(list(level_start)[:L])
+    if len(keep_hw) < 2 * L or len(keep_st) < L:
+        raise ValueError("level_hw / level_start must hold %d levels" % L)
+    lib = _lib.load()
+    code = int(lib.df3d_ms_deform_attn_backward_plan(int(N), int(S), int(M), int(D), int(Lq), int(L), int(P), hw, st,
+                                                     _MSDA_BWD_MODES[mode]))
+    if code >= 0:
+        return _MSDA_BWD_PLANS[code]
+    why = lib.df3d_last_error()
+    why = why.decode() if why else "shape not served"
+    if torch.is_deterministic_algorithms_warn_only_enabled() and os.environ.get("DF3D_MSDA_BWD") is None:
+        if not _msda_bwd_warned:
+            _msda_bwd_warned = True
+            import warnings
+            warnings.warn("dualfusion: %s; using the atomic kernel, whose grad_value is not reproducible (this warning appears "
+                          "once)." % why)
+        return "atomic"
+    raise _lib.Df3dError(why)
+
+
 def ms_deform_attn_backward(value, spatial_shapes, level_start_index, sampling_locations, attention_weights, grad_output):
-    """-> (grad_value [N,S,M,D], grad_sampling_loc [N,Lq,M,L,P,2], grad_attn_weight [N,Lq,M,L,P])."""
+    """-> (grad_value [N,S,M,D], grad_sampling_loc [N,Lq,M,L,P,2], grad_attn_weight [N,Lq,M,L,P]).  Which kernels run:
+    `msda_backward_plan` (DF3D_MSDA_BWD = binned | atomic | sorted)."""
     lib = _lib.load()
     for t, name in ((value, "value"), (sampling_locations, "sampling_locations"), (attention_weights, "attention_weights"),
                     (grad_output, "grad_output")):
@@ -1852,22 +1918,41 @@ def ms_deform_attn_backward(value, spatial_shapes, level_start_index, sampling_l
     gv = torch.empty_like(value)
     gl = torch.empty_like(sampling_locations)
     ga = torch.empty_like(attention_weights)
-    if (L == 1 and D == 16 and P <= 16 and Lq < (1 << 28) and Lq * M * P < (1 << 31)
-            and os.environ.get("DF3D_MSDA_BWD", "binned") != "atomic"):
-        H, W = level_shapes_on_host(spatial_shapes)[0]
-        if H * W == S and ((H + 7) // 8) * ((W + 7) // 8) * M <= 7680 and N <= 65535:
-            # one single-level map, 16-channel heads: the value gradient as tile-wise matrix products, no global atomics
-            # (df3d_ms_deform_attn_backward_binned)
-            nbytes = int(lib.df3d_ms_deform_attn_backward_binned_workspace_bytes(N, M, Lq, P, H, W))
-            ws = torch.empty((nbytes,), dtype=torch.uint8, device=value.device)
-            slabs = torch.empty((int(lib.df3d_ms_deform_attn_backward_binned_slab_bytes(N, M, D, Lq, P, H, W)) // 4,),
-                                dtype=torch.float32, device=value.device)
-            rc = lib.df3d_ms_deform_attn_backward_binned(_ptr(value), _ptr(spatial_shapes), _ptr(level_start_index),
-                                                         _ptr(sampling_locations), _ptr(attention_weights), _ptr(grad_output), N, M,
-                                                         D, Lq, P, H, W, _ptr(gv), _ptr(gl), _ptr(ga), _ptr(ws), nbytes, _ptr(slabs),
-                                                         _stream())
-            _lib.check(rc, "df3d_ms_deform_attn_backward_binned")
-            return gv, gl, ga
+    mode = msda_backward_mode()
+    plan = "atomic"
+    if mode != "atomic" and spatial_shapes.shape[0] == L and level_start_index.shape[0] == L:
+        level_hw, level_start = level_shapes_on_host(spatial_shapes), level_starts_on_host(level_start_index)
+        plan = msda_backward_plan(N, S, M, D, Lq, L, P, level_hw, level_start, mode)
+    if plan == "binned" and L == 1 and D == 16:
+        # one single-level map, 16-channel heads: the value gradient as tile-wise matrix products, no global atomics
+        # (df3d_ms_deform_attn_backward_binned)
+        H, W = level_hw[0]
+        nbytes = int(lib.df3d_ms_deform_attn_backward_binned_workspace_bytes(N, M, Lq, P, H, W))
+        ws = torch.empty((nbytes,), dtype=torch.uint8, device=value.device)
+        slabs = torch.empty((int(lib.df3d_ms_deform_attn_backward_binned_slab_bytes(N, M, D, Lq, P, H, W)) // 4,),
+                            dtype=torch.float32, device=value.device)
+        rc = lib.df3d_ms_deform_attn_backward_binned(_ptr(value), _ptr(spatial_shapes), _ptr(level_start_index),
+                                                     _ptr(sampling_locations), _ptr(attention_weights), _ptr(grad_output), N, M,
+                                                     D, Lq, P, H, W, _ptr(gv), _ptr(gl), _ptr(ga), _ptr(ws), nbytes, _ptr(slabs),
+                                                     _stream())
+        _lib.check(rc, "df3d_ms_deform_attn_backward_binned")
+        return gv, gl, ga
+    if plan != "atomic":
+        # several levels / heads of 32 or 64 channels / the ordered sum: bins of (level, tile, head)
+        # (df3d_ms_deform_attn_backward_binned_ml)
+        ordered = int(plan == "sorted")
+        hw, keep_hw = _i64_arr([v for pair in level_hw for v in pair])
+        st, keep_st = _i64_arr(level_start)
+        nbytes = int(lib.df3d_ms_deform_attn_backward_binned_ml_workspace_bytes(N, M, Lq, L, P, hw, ordered))
+        ws = torch.empty((nbytes,), dtype=torch.uint8, device=value.device)
+        slabs = torch.empty((int(lib.df3d_ms_deform_attn_backward_binned_ml_slab_bytes(N, M, D, Lq, L, P, hw)) // 4,),
+                            dtype=torch.float32, device=value.device)
+        rc = lib.df3d_ms_deform_attn_backward_binned_ml(_ptr(value), _ptr(spatial_shapes), _ptr(level_start_index),
+                                                        _ptr(sampling_locations), _ptr(attention_weights), _ptr(grad_output), hw, st,
+                                                        N, M, D, Lq, L, P, ordered, _ptr(gv), _ptr(gl), _ptr(ga), _ptr(ws), nbytes,
+                                                        _ptr(slabs), _stream())
+        _lib.check(rc, "df3d_ms_deform_attn_backward_binned_ml")
+        return gv, gl, ga
     rc = lib.df3d_ms_deform_attn_backward(_ptr(value), _ptr(spatial_shapes), _ptr(level_start_index),
                                           _ptr(sampling_locations), _ptr(attention_weights), _ptr(grad_output), N, S, M,
                                           D, Lq, L, P, _ptr(gv), _ptr(gl), _ptr(ga), _stream())

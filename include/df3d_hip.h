@@ -604,6 +604,27 @@ int df3d_ms_deform_attn_backward_binned(const float *value, const int64_t *spati
                                         const float *sampling_loc, const float *attn_weight, const float *grad_output, int N,
                                         int M, int D, int Lq, int P, int H, int W, float *grad_value, float *grad_sampling_loc,
                                         float *grad_attn_weight, void *workspace, size_t workspace_bytes, float *slabs, void *stream);
+/* ... and for L >= 1 levels and heads of 16 / 32 / 64 channels (csrc/msda.hip msda_binml_*): bins are (level, tile, head), a head
+ * of D channels is D / 16 column slices of the same matrix product (one set of weights, D / 16 gradient rows), slabs are
+ * [81][D].  level_hw [L][2] (H, W) and level_start [L] are HOST copies of spatial_shapes / level_start_index (the device
+ * tensors are still read by the location / weight half).  Served (df3d_ms_deform_attn_backward_plan): D in {16, 32, 64},
+ * L * P <= 16, M * sum_l ceil(H_l / 8) * ceil(W_l / 8) <= 7680, N <= 65535, and the levels tiling S = sum H_l * W_l without gaps
+ * (level_start[l] = the pixels of the levels before l): every element of grad_value is written exactly once.
+ * ordered != 0: the sampling points of every bin are put in ascending (query, level, point) order before they are summed
+ * (msda_bin_sort_kernel), work items are every 512 points of that order: grad_value depends on the inputs only, bit for bit,
+ * whatever the launch's atomics did (Lq <= 2^20).  No float atomics anywhere on this path.
+ * df3d_ms_deform_attn_backward_plan is the choice function, callable without a GPU: mode 0 = default, 1 = atomic, 2 = ordered
+ * -> 0 the atomic kernels (df3d_ms_deform_attn_backward), 1 binned, 2 binned + ordered, -1 ordered asked for and not served
+ * (df3d_last_error names the limit). */
+int df3d_ms_deform_attn_backward_plan(int N, int S, int M, int D, int Lq, int L, int P, const int64_t *level_hw,
+                                      const int64_t *level_start, int mode);
+size_t df3d_ms_deform_attn_backward_binned_ml_workspace_bytes(int N, int M, int Lq, int L, int P, const int64_t *level_hw, int ordered);
+size_t df3d_ms_deform_attn_backward_binned_ml_slab_bytes(int N, int M, int D, int Lq, int L, int P, const int64_t *level_hw);
+int df3d_ms_deform_attn_backward_binned_ml(const float *value, const int64_t *spatial_shapes, const int64_t *level_start_index,
+                                           const float *sampling_loc, const float *attn_weight, const float *grad_output,
+                                           const int64_t *level_hw, const int64_t *level_start, int N, int M, int D, int Lq, int L,
+                                           int P, int ordered, float *grad_value, float *grad_sampling_loc, float *grad_attn_weight,
+                                           void *workspace, size_t workspace_bytes, float *slabs, void *stream);
 
 /* Self-attention inside small token groups: nn.MultiheadAttention's scaled-dot-product core for the LocalTransformer of
  * ACTRv2 (VR/pcdet/models/backbones_3d/.../pointformer.py:10-44, 232-262): qkv [tokens*groups][3*heads*16] fp32 rows in
