@@ -78,6 +78,9 @@ SIGNATURES = {
     "df3d_ms_deform_attn_backward_binned_ml_workspace_bytes": (c_size_t, [c_int] * 5 + [c_void_p, c_int]),
     "df3d_ms_deform_attn_backward_binned_ml_slab_bytes": (c_size_t, [c_int] * 6 + [c_void_p]),
     "df3d_ms_deform_attn_backward_binned_ml": (c_int, [c_void_p] * 8 + [c_int] * 7 + [c_void_p] * 4 + [c_size_t, c_void_p, c_void_p]),
+    "df3d_ms_deform_attn_forward_f64": (c_int, [c_void_p] * 5 + [c_int] * 7 + [c_void_p, c_void_p]),
+    "df3d_ms_deform_attn_backward_f64_workspace_bytes": (c_size_t, [c_int] * 6),
+    "df3d_ms_deform_attn_backward_f64": (c_int, [c_void_p] * 6 + [c_int] * 7 + [c_void_p] * 4 + [c_size_t, c_void_p]),
     "df3d_furthest_point_sample": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "df3d_pe_gather_add": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_longlong, c_int, c_int,
                                    c_void_p, c_void_p]),

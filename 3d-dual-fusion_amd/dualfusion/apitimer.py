@@ -119,6 +119,21 @@ def _msda(a, value_bytes=4):
     return by, 10 * N * Lq * M * L * P * D, "hbm", "bilinear sampling + weighted sum of %d x %d queries, %d heads x %d points" % (N, Lq, M, L * P)
 
 
+def _msda_f64(a, at, backward=False):
+    """The float64 sampling entries (csrc/msda_f64.hip; value_bytes = 8): the forward moves what `_msda` counts at 8 bytes per
+    element; the backward reads that again plus the upstream rows, writes the three gradients and lists / sorts / walks one
+    4-byte id per corner (three times: fill, sort, gather)."""
+    N, S, M, D, Lq, L, P = a[at:at + 7]
+    value_bytes = 8
+    pts = N * Lq * M * L * P
+    by = min(N * S * M * D, pts * 4 * D) * value_bytes + pts * 3 * value_bytes + N * Lq * M * D * value_bytes
+    what = "bilinear sampling + weighted sum of %d x %d queries, %d heads x %d points, float64" % (N, Lq, M, L * P)
+    if not backward:
+        return by, 10 * pts * D, "hbm", what
+    by += N * Lq * M * D * value_bytes + N * S * M * D * value_bytes + pts * 3 * value_bytes + pts * 4 * 4 * 3 + N * S * M * 12
+    return by, 30 * pts * D, "hbm", "backward of " + what + " (ordered sums, no float atomics)"
+
+
 def _ffn(a, rows):
     d_model, d_ffn = a[2], a[3]
     if rows is None:
@@ -148,6 +163,8 @@ def _rows(elems_in, elems_out, what):
 MODELS = {
     "df3d_hard_voxelize": lambda a, x: (20 * a[1] + a[6] * 0, 0, "hbm", "hash + scan + gather of %d points (bytes completed by the caller with M * 36)" % a[1]),
     "df3d_hard_voxelize_batched": lambda a, x: (20 * a[1], 0, "hbm", "hash + scan + gather of %d points (bytes completed by the caller with M * 36)" % a[1]),
+    "df3d_ms_deform_attn_forward_f64": lambda a, x: _msda_f64(a, 5),
+    "df3d_ms_deform_attn_backward_f64": lambda a, x: _msda_f64(a, 6, backward=True),
     "df3d_ms_deform_attn_fused": lambda a, x: _msda(a, 4),
     "df3d_ms_deform_attn_fused_bf16": lambda a, x: _msda(a, 2),
     "df3d_ffn_fused_jobs": lambda a, x: _ffn(a, x),

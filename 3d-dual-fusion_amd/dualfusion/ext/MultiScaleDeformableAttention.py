@@ -1,5 +1,6 @@
 """`MultiScaleDeformableAttention` (CP/det3d/models/model_utils/ops/src/vision.cpp:13-16, ms_deform_attn.h:21-62), as
-`MSDeformAttnFunction` calls it (ops/functions/ms_deform_attn_func.py:21-38)."""
+`MSDeformAttnFunction` calls it (ops/functions/ms_deform_attn_func.py:21-38).  Float and double tensors, as the reference's
+dispatch (cuda/ms_deform_attn_cuda.cu:64, :129): the results have the operands' dtype."""
 import torch
 
 from .. import ops as _ops
@@ -28,7 +29,8 @@ def ms_deform_attn_forward(value, spatial_shapes, level_start_index, sampling_lo
 @runtime_errors
 def ms_deform_attn_backward(value, spatial_shapes, level_start_index, sampling_loc, attn_weight, grad_output, im2col_step):
     """-> [grad_value, grad_sampling_loc, grad_attn_weight].  The kernels are `ops.msda_backward_plan`'s choice (DF3D_MSDA_BWD =
-    binned | atomic | sorted; "sorted", the bit-reproducible value gradient, also under torch.use_deterministic_algorithms)."""
+    binned | atomic | sorted; "sorted", the bit-reproducible value gradient, also under torch.use_deterministic_algorithms) for
+    float tensors; double tensors have one path, always bit-reproducible."""
     _check(value, spatial_shapes, level_start_index, sampling_loc, attn_weight)
     need_cuda_contiguous(grad_output, "grad_output")
     return list(_ops.ms_deform_attn_backward(value, spatial_shapes, level_start_index, sampling_loc, attn_weight, grad_output))

@@ -20,7 +20,12 @@ class MSDeformAttnFunction(Function):
     im2col_step) -> [N, Lq, M*D].  im2col_step is accepted for signature parity; the HIP kernels
     need no batch chunking.  backward -> (grad_value, None, None, grad_sampling_loc, grad_attn_weight, None) like
     ms_deform_attn_func.py:31-38 (csrc/msda.hip; which kernels: ops.msda_backward_plan, DF3D_MSDA_BWD = binned | atomic |
-    sorted, "sorted" also under torch.use_deterministic_algorithms)."""
+    sorted, "sorted" also under torch.use_deterministic_algorithms).
+
+    The operands may be float32 or float64 -- the two types of the reference's dispatch; the four floating tensors share one.
+    Float64 (csrc/msda_f64.hip: what torch.autograd.gradcheck and the reference's ops/test.py run) is one path for any shape: all
+    arithmetic fp64, the backward without floating-point atomics and bit-reproducible.  DF3D_MSDA_BWD and
+    torch.use_deterministic_algorithms are not consulted for it, and it never raises "not served"."""
 
     @staticmethod
     def forward(ctx, value, value_spatial_shapes, value_level_start_index, sampling_locations, attention_weights,

@@ -1804,8 +1804,40 @@ def cross_attention_train(q, k, v, heads, scale, p=0.0, seed=None):
     return _CrossAttention.apply(q, k, v, int(heads), float(scale), float(p), int(seed))
 
 
+def _msda_dtype(operands):
+    """The one dtype -- float32 or float64, the two types of the reference's dispatch (ms_deform_attn_cuda.cu:64, :129) -- that
+    the floating operands [(tensor, name)] of the sampling operator share, `value` first; half and bfloat16 are refused as
+    there.  Where a tensor lives and how it is laid out is checked before what it holds."""
+    for t, name in operands:
+        if not t.is_cuda:
+            raise _lib.Df3dError("%s must live on the GPU (got %s); the MI355X path has no CPU fallback" % (name, t.device))
+        if not t.is_contiguous():
+            raise _lib.Df3dError("%s must be contiguous" % name)
+    dtype = operands[0][0].dtype
+    if dtype not in (torch.float32, torch.float64):
+        raise _lib.Df3dError("%s must be torch.float32 or torch.float64 (got %s)" % (operands[0][1], dtype))
+    for t, name in operands[1:]:
+        if t.dtype != dtype:
+            raise _lib.Df3dError("%s is %s but %s is %s: the floating operands of ms_deform_attn share one dtype"
+                                 % (name, t.dtype, operands[0][1], dtype))
+    return dtype
+
+
 def ms_deform_attn_forward(value, spatial_shapes, level_start_index, sampling_locations, attention_weights):
+    """-> [N, Lq, M*D] in the operands' dtype: float32 (csrc/msda.hip) or float64 (csrc/msda_f64.hip, all arithmetic fp64)."""
     lib = _lib.load()
+    if _msda_dtype(((value, "value"), (sampling_locations, "sampling_locations"),
+                    (attention_weights, "attention_weights"))) == torch.float64:
+        _chk(spatial_shapes, torch.int64, "spatial_shapes")
+        _chk(level_start_index, torch.int64, "level_start_index")
+        N, S, M, D = value.shape
+        _, Lq, _, L, P, _ = sampling_locations.shape
+        out = torch.empty((N, Lq, M * D), dtype=torch.float64, device=value.device)
+        rc = lib.df3d_ms_deform_attn_forward_f64(_ptr(value), _ptr(spatial_shapes), _ptr(level_start_index),
+                                                 _ptr(sampling_locations), _ptr(attention_weights), N, S, M, D, Lq, L, P,
+                                                 _ptr(out), _stream())
+        _lib.check(rc, "df3d_ms_deform_attn_forward_f64")
+        return out
     _chk(value, torch.float32, "value")
     _chk(spatial_shapes, torch.int64, "spatial_shapes")
     _chk(level_start_index, torch.int64, "level_start_index")
@@ -1904,8 +1936,31 @@ def msda_backward_plan(N, S, M, D, Lq, L, P, level_hw, level_start, mode=None):
 
 def ms_deform_attn_backward(value, spatial_shapes, level_start_index, sampling_locations, attention_weights, grad_output):
     """-> (grad_value [N,S,M,D], grad_sampling_loc [N,Lq,M,L,P,2], grad_attn_weight [N,Lq,M,L,P]).  Which kernels run:
-    `msda_backward_plan` (DF3D_MSDA_BWD = binned | atomic | sorted)."""
+    `msda_backward_plan` (DF3D_MSDA_BWD = binned | atomic | sorted) for float32 operands.  Float64 operands have one path
+    (df3d_ms_deform_attn_backward_f64: no floating-point atomics, bit-reproducible, any shape), for which neither DF3D_MSDA_BWD
+    nor torch.use_deterministic_algorithms is consulted."""
     lib = _lib.load()
+    if _msda_dtype(((value, "value"), (sampling_locations, "sampling_locations"), (attention_weights, "attention_weights"),
+                    (grad_output, "grad_output"))) == torch.float64:
+        _chk(spatial_shapes, torch.int64, "spatial_shapes")
+        _chk(level_start_index, torch.int64, "level_start_index")
+        N, S, M, D = value.shape
+        _, Lq, _, L, P, _ = sampling_locations.shape
+        if tuple(grad_output.shape) != (N, Lq, M * D):
+            raise ValueError("grad_output must be [N, Lq, M*D]")
+        nbytes = int(lib.df3d_ms_deform_attn_backward_f64_workspace_bytes(N, S, M, Lq, L, P))
+        if nbytes == 0:
+            why = lib.df3d_last_error()
+            raise _lib.Df3dError(why.decode() if why else "ms_deform_attn_backward_f64: shape not served")
+        gv = torch.empty_like(value)
+        gl = torch.empty_like(sampling_locations)
+        ga = torch.empty_like(attention_weights)
+        ws = torch.empty((nbytes,), dtype=torch.uint8, device=value.device)
+        rc = lib.df3d_ms_deform_attn_backward_f64(_ptr(value), _ptr(spatial_shapes), _ptr(level_start_index),
+                                                  _ptr(sampling_locations), _ptr(attention_weights), _ptr(grad_output), N, S, M,
+                                                  D, Lq, L, P, _ptr(gv), _ptr(gl), _ptr(ga), _ptr(ws), nbytes, _stream())
+        _lib.check(rc, "df3d_ms_deform_attn_backward_f64")
+        return gv, gl, ga
     for t, name in ((value, "value"), (sampling_locations, "sampling_locations"), (attention_weights, "attention_weights"),
                     (grad_output, "grad_output")):
         _chk(t, torch.float32, name)

@@ -626,6 +626,24 @@ int df3d_ms_deform_attn_backward_binned_ml(const float *value, const int64_t *sp
                                            int P, int ordered, float *grad_value, float *grad_sampling_loc, float *grad_attn_weight,
                                            void *workspace, size_t workspace_bytes, float *slabs, void *stream);
 
+/* The same operator in float64 (csrc/msda_f64.hip): the second type of the reference's dispatch (AT_DISPATCH_FLOATING_TYPES,
+ * cuda/ms_deform_attn_cuda.cu:64 forward, :129 backward), which its acceptance script ops/test.py runs (allclose against the
+ * torch core in double, torch.autograd.gradcheck).  Contracts of df3d_ms_deform_attn_forward / _backward with every floating
+ * operand a double; any D, L, P >= 1; all arithmetic fp64.  The backward has no floating-point atomics and is a function of its
+ * inputs bit for bit: the contributions to a value row (n, s, m) are listed (integer counters), put in ascending
+ * (query, level, point, corner) order and summed in that order, every element of grad_value stored once (no zero fill); the
+ * channel sums of grad_sampling_loc / grad_attn_weight follow one fixed tree per D.  Workspace of ..._workspace_bytes(N, S, M,
+ * Lq, L, P) bytes (host only; 0 with df3d_last_error naming the limit when the shape is not served: N * S * M <= 2^31 - 2 value
+ * rows, N * Lq * M * L * P * 4 <= 2^31 - 1 contributions -- what the uint32 segment offsets and ids hold). */
+int df3d_ms_deform_attn_forward_f64(const double *value, const int64_t *spatial_shapes, const int64_t *level_start_index,
+                                    const double *sampling_loc, const double *attn_weight, int N, int S, int M, int D, int Lq,
+                                    int L, int P, double *out, void *stream);
+size_t df3d_ms_deform_attn_backward_f64_workspace_bytes(int N, int S, int M, int Lq, int L, int P);
+int df3d_ms_deform_attn_backward_f64(const double *value, const int64_t *spatial_shapes, const int64_t *level_start_index,
+                                     const double *sampling_loc, const double *attn_weight, const double *grad_output, int N,
+                                     int S, int M, int D, int Lq, int L, int P, double *grad_value, double *grad_sampling_loc,
+                                     double *grad_attn_weight, void *workspace, size_t workspace_bytes, void *stream);
+
 /* Self-attention inside small token groups: nn.MultiheadAttention's scaled-dot-product core for the LocalTransformer of
  * ACTRv2 (VR/pcdet/models/backbones_3d/.../pointformer.py:10-44, 232-262): qkv [tokens*groups][3*heads*16] fp32 rows in
  * sequence-first order (row = token * groups + group; the in-projection's q | k | v blocks) -> out [tokens*groups][heads*16];
