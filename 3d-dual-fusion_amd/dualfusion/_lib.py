@@ -233,6 +233,12 @@ SIGNATURES = {
     "df3d_sparse_maxpool": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p]),
     "df3d_sparse_maxpool_backward": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p]),
     "df3d_dynamic_voxelize": (c_int, [c_void_p, c_longlong, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "df3d_dynamic_scatter_plan_workspace_bytes": (c_size_t, [c_longlong, c_void_p]),
+    "df3d_dynamic_scatter_plan": (c_int, [c_void_p, c_longlong, c_int] + [c_void_p] * 7 + [c_size_t, c_void_p]),
+    "df3d_dynamic_scatter_reduce": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
+    "df3d_voxel_to_point": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_longlong, c_void_p, c_void_p]),
+    "df3d_dynamic_scatter_max_backward": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_longlong, c_int, c_int, c_void_p,
+                                                  c_void_p, c_void_p, c_void_p]),
     "df3d_topk_keys_workspace_bytes": (c_size_t, [c_int, c_longlong, c_int]),
     "df3d_topk_keys": (c_int, [c_void_p, c_int, c_longlong, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "df3d_cross_attention_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),

@@ -33,10 +33,24 @@ def dynamic_voxelize(points, coors, voxel_size, coors_range, NDim=3):
     _ops.dynamic_voxelize(points, voxel_size, coors_range, out=coors)
 
 
-def dynamic_point_to_voxel_forward(*args, **kwargs):
-    raise RuntimeError("dynamic_point_to_voxel_forward (DynamicScatter) is not on the 3D-Dual-Fusion path: its configs "
-                       "use hard voxelisation + mean VFE")
+@runtime_errors
+def dynamic_point_to_voxel_forward(feats, coors, reduce_type):
+    """voxelization.h:96-109: -> [voxel_feats [M, C], voxel_coors [M, ndim], point2voxel_map [N], voxel_points_count [M]]
+    (the two index tensors are int32 here, as `coors` is)."""
+    need_cuda_contiguous(feats, "feats")
+    need_cuda_contiguous(coors, "coors")
+    plan = _ops.dynamic_scatter_plan(coors)
+    voxel_feats = _ops.dynamic_scatter_reduce(feats, plan, reduce_type)
+    return [voxel_feats, plan.voxel_coors, plan.point2voxel_map, plan.voxel_points_count]
 
 
-def dynamic_point_to_voxel_backward(*args, **kwargs):
-    raise RuntimeError("dynamic_point_to_voxel_backward (DynamicScatter) is not on the 3D-Dual-Fusion path")
+@runtime_errors
+def dynamic_point_to_voxel_backward(grad_feats, grad_voxel_feats, feats, voxel_feats, point2voxel_map, voxel_points_count,
+                                    reduce_type):
+    """voxelization.h:111-123: fills the caller's grad_feats [N, C]."""
+    for t, n in ((grad_feats, "grad_feats"), (grad_voxel_feats, "grad_voxel_feats"), (feats, "feats"),
+                 (voxel_feats, "voxel_feats"), (point2voxel_map, "point2voxel_map"),
+                 (voxel_points_count, "voxel_points_count")):
+        need_cuda_contiguous(t, n)
+    _ops.dynamic_scatter_backward(grad_voxel_feats, feats, voxel_feats, point2voxel_map, voxel_points_count, reduce_type,
+                                  out=grad_feats)

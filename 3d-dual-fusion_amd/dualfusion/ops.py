@@ -1710,6 +1710,204 @@ def dynamic_voxelize(points, voxel_size, coors_range, out=None):
     return coors
 
 
+# ------------------------------------------------------------------------- dynamic scatter
+_REDUCE_TYPES = {"sum": 0, "mean": 1, "max": 2}
+
+
+def _reduce_code(reduce):
+    if reduce not in _REDUCE_TYPES:
+        raise _lib.Df3dError("reduce type %r: must be one of 'sum', 'mean', 'max'" % (reduce,))
+    return _REDUCE_TYPES[reduce]
+
+
+def _chk_float(t, name):
+    if t.dtype not in (torch.float32, torch.float64):
+        raise _lib.Df3dError("%s must be float32 or float64 (got %s)" % (name, t.dtype))
+    return _chk(t, t.dtype, name)
+
+
+class DynamicScatterPlan(object):
+    """What `dynamic_scatter_plan` learned about one `coors` tensor; every reduce, gather and backward over those
+    coordinates reuses it.  voxel_coors [M, ndim], point2voxel_map [N] (-1: invalid point), voxel_points_count [M],
+    offsets [M + 1] / point_ids [*]: voxel v owns point_ids[offsets[v]:offsets[v + 1]], ascending.  The plan keeps the
+    full-capacity buffers (and the workspace they were built in) alive."""
+
+    __slots__ = ("coors", "num_points", "num_voxels", "voxel_coors", "point2voxel_map", "voxel_points_count", "offsets",
+                 "point_ids", "_buffers")
+
+    @property
+    def device(self):
+        return self.point2voxel_map.device
+
+
+def dynamic_scatter_plan(coors):
+    """df3d_dynamic_scatter_plan.  coors: int32 [N, ndim], ndim 1..4; rows with any negative entry are invalid.  Voxels
+    are the distinct valid rows in ascending lexicographic order.  One D2H read (the voxel count)."""
+    if not isinstance(coors, torch.Tensor) or coors.dim() != 2 or not 1 <= coors.shape[1] <= 4:
+        raise _lib.Df3dError("coors must be an int32 [N, ndim] tensor with ndim 1..4")
+    _chk(coors, torch.int32, "coors")
+    N, ndim = coors.shape
+    dev = coors.device
+    plan = DynamicScatterPlan()
+    plan.coors, plan.num_points = coors, N
+    if N == 0:
+        plan.num_voxels = 0
+        plan.voxel_coors = torch.empty((0, ndim), dtype=torch.int32, device=dev)
+        plan.point2voxel_map = torch.empty((0,), dtype=torch.int32, device=dev)
+        plan.voxel_points_count = torch.empty((0,), dtype=torch.int32, device=dev)
+        plan.offsets = torch.zeros((1,), dtype=torch.int32, device=dev)
+        plan.point_ids = torch.empty((0,), dtype=torch.int32, device=dev)
+        plan._buffers = ()
+        return plan
+    lib = _lib.load()
+    stream = _stream()
+    wsb = lib.df3d_dynamic_scatter_plan_workspace_bytes(N, stream)
+    if wsb == 0:
+        raise _lib.Df3dError("df3d_dynamic_scatter_plan: no workspace size for %d points: %s"
+                             % (N, (lib.df3d_last_error() or b"?").decode()))
+    ws = torch.empty((wsb,), dtype=torch.uint8, device=dev)
+    voxel_coors = torch.empty((N, ndim), dtype=torch.int32, device=dev)
+    p2v = torch.empty((N,), dtype=torch.int32, device=dev)
+    count = torch.empty((N,), dtype=torch.int32, device=dev)
+    offsets = torch.empty((N + 1,), dtype=torch.int32, device=dev)
+    ids = torch.empty((N,), dtype=torch.int32, device=dev)
+    status = torch.empty((2,), dtype=torch.int32, device=dev)
+    rc = lib.df3d_dynamic_scatter_plan(_ptr(coors), N, ndim, _ptr(voxel_coors), _ptr(p2v), _ptr(count), _ptr(offsets),
+                                       _ptr(ids), _ptr(status), _ptr(ws), wsb, stream)
+    _lib.check(rc, "df3d_dynamic_scatter_plan")
+    M, overflow = status.tolist()                                    # the one D2H read
+    if overflow:
+        raise _lib.Df3dError("dynamic_scatter_plan: the product of (max + 1) over the coordinate columns does not fit in "
+                             "63 bits; the voxel keys are 64-bit integers")
+    plan.num_voxels = M
+    plan.voxel_coors, plan.point2voxel_map, plan.voxel_points_count = voxel_coors[:M], p2v, count[:M]
+    plan.offsets, plan.point_ids = offsets[:M + 1], ids
+    plan._buffers = (ws, voxel_coors, count, offsets)
+    return plan
+
+
+def _as_plan(plan_or_coors):
+    return plan_or_coors if isinstance(plan_or_coors, DynamicScatterPlan) else dynamic_scatter_plan(plan_or_coors)
+
+
+def _rows_match_plan(rows, n, plan, name):
+    if rows.dim() != 2 or rows.shape[0] != n:
+        raise _lib.Df3dError("%s must be [%d, C] for this plan (got %s)" % (name, n, tuple(rows.shape)))
+    if rows.device != plan.device:
+        raise _lib.Df3dError("%s and the plan live on different devices" % name)
+
+
+def dynamic_scatter_reduce(feats, plan, reduce):
+    """df3d_dynamic_scatter_reduce: [M, C] sum / mean / max of the rows of feats [N, C] (float32 / float64) per voxel."""
+    code = _reduce_code(reduce)
+    _chk_float(feats, "feats")
+    _rows_match_plan(feats, plan.num_points, plan, "feats")
+    C, M = feats.shape[1], plan.num_voxels
+    out = torch.empty((M, C), dtype=feats.dtype, device=feats.device)
+    if M == 0 or C == 0:
+        return out
+    rc = _lib.load().df3d_dynamic_scatter_reduce(_ptr(feats), int(feats.dtype == torch.float64), C, _ptr(plan.point_ids),
+                                                 _ptr(plan.offsets), M, code, _ptr(out), _stream())
+    _lib.check(rc, "df3d_dynamic_scatter_reduce")
+    return out
+
+
+def _voxel_to_point(voxel_rows, plan, mean=False):
+    _chk_float(voxel_rows, "voxel_feats")
+    _rows_match_plan(voxel_rows, plan.num_voxels, plan, "voxel_feats")
+    N, C = plan.num_points, voxel_rows.shape[1]
+    out = torch.empty((N, C), dtype=voxel_rows.dtype, device=voxel_rows.device)
+    if N == 0 or C == 0:
+        return out
+    rc = _lib.load().df3d_voxel_to_point(_ptr(voxel_rows), int(voxel_rows.dtype == torch.float64), C,
+                                         _ptr(plan.point2voxel_map), _ptr(plan.voxel_points_count if mean else None), N,
+                                         _ptr(out), _stream())
+    _lib.check(rc, "df3d_voxel_to_point")
+    return out
+
+
+def dynamic_scatter_backward(grad_voxel_feats, feats, voxel_feats, point2voxel_map, voxel_points_count, reduce, out=None):
+    """Gradient of `dynamic_scatter_reduce` w.r.t. feats, from the tensors the reference's extension hands over."""
+    code = _reduce_code(reduce)
+    _chk_float(feats, "feats")
+    N, C = feats.shape
+    M = voxel_points_count.shape[0]
+    for t, nm in ((grad_voxel_feats, "grad_voxel_feats"), (voxel_feats, "voxel_feats")):
+        _chk(t, feats.dtype, nm)
+        if tuple(t.shape) != (M, C):
+            raise _lib.Df3dError("%s must be [%d, %d] (got %s)" % (nm, M, C, tuple(t.shape)))
+    _chk(point2voxel_map, torch.int32, "point2voxel_map")
+    _chk(voxel_points_count, torch.int32, "voxel_points_count")
+    if point2voxel_map.shape[0] != N:
+        raise _lib.Df3dError("point2voxel_map must have one entry per point")
+    grad = torch.empty_like(feats) if out is None else _chk(out, feats.dtype, "grad_feats")
+    if tuple(grad.shape) != (N, C):
+        raise _lib.Df3dError("grad_feats must be [%d, %d]" % (N, C))
+    if N == 0 or C == 0:
+        return grad
+    lib = _lib.load()
+    dbl = int(feats.dtype == torch.float64)
+    if code == 2:
+        arg = torch.empty((max(M * C, 1),), dtype=torch.int32, device=feats.device)
+        rc = lib.df3d_dynamic_scatter_max_backward(_ptr(feats), _ptr(voxel_feats), _ptr(grad_voxel_feats), dbl, N, M, C,
+                                                   _ptr(point2voxel_map), _ptr(arg), _ptr(grad), _stream())
+        _lib.check(rc, "df3d_dynamic_scatter_max_backward")
+    else:
+        rc = lib.df3d_voxel_to_point(_ptr(grad_voxel_feats), dbl, C, _ptr(point2voxel_map),
+                                     _ptr(voxel_points_count if code == 1 else None), N, _ptr(grad), _stream())
+        _lib.check(rc, "df3d_voxel_to_point")
+    return grad
+
+
+class _DynamicScatter(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, feats, plan, reduce):
+        out = dynamic_scatter_reduce(feats, plan, reduce)
+        ctx.plan, ctx.reduce = plan, reduce
+        ctx.save_for_backward(feats, out)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        feats, out = ctx.saved_tensors
+        plan = ctx.plan
+        return dynamic_scatter_backward(grad_out.contiguous(), feats, out, plan.point2voxel_map, plan.voxel_points_count,
+                                        ctx.reduce), None, None
+
+
+class _VoxelToPoint(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, voxel_feats, plan):
+        ctx.plan = plan
+        return _voxel_to_point(voxel_feats, plan)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        return dynamic_scatter_reduce(grad_out.contiguous(), ctx.plan, "sum"), None
+
+
+def dynamic_scatter(feats, plan_or_coors, reduce="max"):
+    """-> (voxel_feats [M, C], voxel_coors [M, ndim]): the rows of feats [N, C] that share a coordinate row reduced by
+    'sum', 'mean' or 'max' (TF/mmdet3d/ops/voxel/scatter_points.py:9-50); differentiable in feats.  Pass a
+    `dynamic_scatter_plan` to reuse the sort over several calls; `plan.point2voxel_map` / `.voxel_points_count` hold the
+    other two results of the reference's extension call."""
+    _reduce_code(reduce)
+    if not isinstance(feats, torch.Tensor) or not feats.is_cuda:
+        raise _lib.Df3dError("feats must live on the GPU; the MI355X path has no CPU fallback")
+    plan = _as_plan(plan_or_coors)
+    return _DynamicScatter.apply(feats.contiguous(), plan, reduce), plan.voxel_coors
+
+
+def voxel_to_point(voxel_feats, plan):
+    """out [N, C] = voxel_feats[plan.point2voxel_map], zero rows for invalid points (the reference's
+    DynamicVFE.map_voxel_center_to_point without its dense canvas); differentiable: the backward is the ordered segment sum."""
+    if not isinstance(plan, DynamicScatterPlan):
+        raise _lib.Df3dError("voxel_to_point needs a dynamic_scatter_plan")
+    if not isinstance(voxel_feats, torch.Tensor) or not voxel_feats.is_cuda:
+        raise _lib.Df3dError("voxel_feats must live on the GPU; the MI355X path has no CPU fallback")
+    return _VoxelToPoint.apply(voxel_feats.contiguous(), plan)
+
+
 def topk_keys(keys, k):
     """df3d_topk_keys.  keys: int64 [segments, n] (the 64-bit keys reinterpreted; they compare as UNSIGNED).  Returns
     (out int64 [segments, k] ascending as unsigned, count int32 [segments] of keys below the all-ones key)."""

@@ -1309,6 +1309,36 @@ int df3d_voxel_image_sample(const int32_t *indices, int n, int batch, float voxe
                             int Hin, int Win, int img_h, int img_w, float scale_y, float scale_x, const float *add,
                             const long long *out_rows, float *out, float *uv, float *grid, void *stream);
 
+/* ------------------------------------------------------------------------------------
+ * Dynamic scatter (csrc/dynscatter.hip).  Replaces voxel_layer.dynamic_point_to_voxel_forward / _backward
+ * (TF/mmdet3d/ops/voxel/src/voxelization.h:96-123, scatter_points_cuda.cu) and the canvas look-up of
+ * DynamicVFE.map_voxel_center_to_point.
+ *
+ * Plan over coors [N, ndim] int32 (ndim 1..4; a row with ANY negative entry is invalid): voxels = the distinct valid rows
+ * in ascending lexicographic order (first column most significant).  Outputs, all int32 with room for N voxels:
+ * voxel_coors [N, ndim], point2voxel_map [N] (-1 for invalid points), voxel_points_count [N], offsets [N + 1] and
+ * point_ids [N]: voxel v owns point_ids[offsets[v] .. offsets[v + 1]), ascending.  status [2] (device): {M, overflow};
+ * overflow = 1 when the product of (max + 1) over the columns does not fit in 63 bits (then M = 0 and the caller must
+ * report it).  The workspace size depends on the device of `stream` (0 when it cannot be determined).
+ *
+ * Reduce: out [M, C] = sum (0) / mean (1) / max (2) of feats [N, C] rows per voxel, float32 or float64 (is_double);
+ * the order of each sum is a function of the voxel's point count and C alone (bit-reproducible, no float atomics).
+ * voxel_to_point: out [N, C] = voxel_rows[map[p]] (divided by divide_by_count[map[p]] when that pointer is given), zero
+ * rows where map[p] < 0: the gather back to points and the sum / mean backward.
+ * max backward: grad_feats [N, C] = 0 except, per (voxel, channel), grad_voxel_feats at the LOWEST point index whose
+ * feature equals the maximum; arg_workspace: M * C int32. */
+size_t df3d_dynamic_scatter_plan_workspace_bytes(long long num_points, void *stream);
+int df3d_dynamic_scatter_plan(const int32_t *coors, long long num_points, int ndim, int32_t *voxel_coors,
+                              int32_t *point2voxel_map, int32_t *voxel_points_count, int32_t *offsets, int32_t *point_ids,
+                              int32_t *status, void *workspace, size_t workspace_bytes, void *stream);
+int df3d_dynamic_scatter_reduce(const void *feats, int is_double, int channels, const int32_t *point_ids,
+                                const int32_t *offsets, int num_voxels, int reduce, void *out, void *stream);
+int df3d_voxel_to_point(const void *voxel_rows, int is_double, int channels, const int32_t *point2voxel_map,
+                        const int32_t *divide_by_count, long long num_points, void *out, void *stream);
+int df3d_dynamic_scatter_max_backward(const void *feats, const void *voxel_feats, const void *grad_voxel_feats, int is_double,
+                                      long long num_points, int num_voxels, int channels, const int32_t *point2voxel_map,
+                                      int32_t *arg_workspace, void *grad_feats, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
