@@ -254,7 +254,9 @@ __global__ __launch_bounds__(256) void msda_bwd_vec4_kernel(MsdaBwdArgs a) {
 }
 
 // ---------------------------------------------------------------------------------------------------------
-// Value gradient WITHOUT global atomics (round 6; heads of 16 channels, one single-level map).  The col2im above issues 16 scalar
+// Value gradient WITHOUT global atomics (msda_bin_*): L >= 1 levels with L * P <= 16, heads of 16 / 32 / 64 channels.  Round 6
+// wrote it for one single-level map with 16-channel heads, DESIGN 7.7 widened it; both shapes run the ONE set of kernels below
+// (df3d_ms_deform_attn_backward_binned is df3d_ms_deform_attn_backward_binned_ml with L = 1).  The col2im above issues 16 scalar
 // fp32 atomics per lane and sampling point: 0.5 G atomics per call at the TransFusion training shape (24 maps x ~10 k queries x 8
 // heads x 4 points x 4 corners x 16 channels), and the L2's atomic units retire ~80 G of them per second whatever their scope or
 // spread (tools/debug/msda_bwd_probe.py: 5.0 ms with uniformly spread queries, 5.3 ms with a third of them on one pixel) -- 3 ms
@@ -263,48 +265,78 @@ __global__ __launch_bounds__(256) void msda_bwd_vec4_kernel(MsdaBwdArgs a) {
 // The col2im of a tile IS a matrix product:  footprint[81 px][16 ch] = Wt[81 px][points] . G[points][16 ch],  Wt = the
 // bilinear weights (four non-zeros per column), G = attention weight x upstream gradient -- dense in the accumulator, so a
 // pile-up on one pixel costs nothing.  Hence:
-//   1. the sampling points are counting-sorted by (map, 8 x 8 pixel tile of their top-left corner, head): LDS histograms per
-//      workgroup, one range reservation per workgroup and bin (msda_bin_kernel, msda_bin_scan_kernel);
+//   1. the sampling points are counting-sorted by (map, level, 8 x 8 pixel tile of their top-left corner, head): LDS histograms
+//      per workgroup, one range reservation per workgroup and bin (msda_bin_kernel, msda_bin_scan_kernel);
 //   2. a WAVE per <= 512 points of a bin runs the product on v_mfma_f32_16x16x4_f32 (exact fp32 products): six 16-pixel row
 //      tiles of the 9 x 9 footprint (tile + one-pixel halo: the four corners of a point stay inside), A operand = the weights
 //      formed in registers from (footprint index, lh, lw), B operand = the gradient row, and stores its footprint as a slab;
 //   3. a gather kernel adds the slabs of a tile and the halo row / column / corner of its three neighbours into grad_value:
 //      every element written exactly once -- no atomics, no zero fill.
+// A bin is a (level, tile, head): the levels' tiles are numbered one level after the other (tbase), every level has its own map
+// size, tile row length and first pixel, and grad_value [N][S][M][D] is written exactly once because the levels tile S without
+// gaps (checked on the host: df3d_ms_deform_attn_backward_plan).  A head of D = 16 * NS channels is NS column slices of the same
+// product: the A operand (the bilinear weights) is formed once per point and row tile and multiplies NS gradient rows, the
+// slab is [81][D].
+//
+// ORDERED (df3d_ms_deform_attn_backward_binned_ml(..., ordered = 1)): the scatter of msda_bin_kernel leaves the points of a bin
+// in the order in which lanes and workgroups won LDS / global integer atomics, and the fp32 sums of the accumulate kernel follow
+// that order.  msda_bin_sort_kernel puts every bin's packed ids (q << 4 | lp, unique within a bin) in ascending order first; the
+// work items are then every MB_CHUNK ids of that sequence, so grad_value is a function of the inputs alone.  A workgroup per
+// bin: <= 64 ids are ranked by counting inside one wave, <= 1024 go through a bitonic network in LDS, and a larger bin (the
+// pile-up on the unseen voxels' reference point: thousands to tens of thousands of ids) is written out from a bit directory --
+// one bit per possible id in 256 Ki-id windows, set with LDS integer atomics, read back in order with a popcount scan: linear
+// in the ids (the network's log^2 passes over 8192 ids cost more than the rest of the backward at the training shape).
 constexpr int MB_T = 8, MB_FOOT = (MB_T + 1) * (MB_T + 1), MB_CHUNK = 512, MB_D = 16;
+constexpr int MB_LMAX = 16, MS_WORDS = 8192, MS_WINDOW = MS_WORDS * 32, MS_NETWORK = 1024;
+#define MS_PHYS(i) ((i) + ((i) >> 5))                         // (a thread walks 32 consecutive words: one pad word per 32)
 
 // Everything below is per MAP n (blockIdx.y): bins, point ranges, work items and slabs are numbered within the map, so no
 // prefix sum crosses maps (nbm = tiles * M bins, ppm = Lq * M * LP point slots, mw = nbm + ppm / MB_CHUNK + 1 work items).
-struct MsdaBinArgs {
+struct MsdaMlArgs {
   const float *loc, *aw, *gout;
   const unsigned char *nz;
   float *gvalue;
-  int N, S, M, D, Lq, LP, H, W, tx, ty, tiles;
-  unsigned *count, *cursor, *offset;   // [N][nbm]: points of a bin; scatter cursor; first point slot
-  unsigned *binw;                      // [N][nbm + 1]: first work item of a bin
-  unsigned *nwork;                     // [N]
-  unsigned *work;                      // [N][mw][3]: (bin, first, last)
-  unsigned *items;                     // [N][ppm]: packed (q << 4 | lp), bin after bin
-  int mw;
-  float *slabs;                        // [N][mw][MB_FOOT][16]: the work items' footprints
+  int N, S, M, D, Lq, L, P, LP, nbm, mw;
+  int H[MB_LMAX], W[MB_LMAX], tx[MB_LMAX], start[MB_LMAX], tbase[MB_LMAX + 1];   // per level; tbase: first tile of the level
+  unsigned *count, *cursor, *offset;                          // [N][nbm]: points of a bin; scatter cursor; first point slot
+  unsigned *binw;                                             // [N][nbm + 1]: first work item of a bin
+  unsigned *nwork;                                            // [N]
+  unsigned *work;                                             // [N][mw][3]: (bin, first, last)
+  const unsigned *items;                                      // what the accumulate kernel reads (the ordered copy if there is one)
+  unsigned *scattered, *sorted;                               // [N][ppm] each: the scatter's output; the ordered copy
+  float *slabs;                                               // [N][mw][MB_FOOT][D]: the work items' footprints
+};
+// what the scan kernel reads and writes of the above
+struct MsdaScanArgs {
+  unsigned *count, *offset, *binw, *nwork, *work;
+  int nbm, mw;
 };
 
-__device__ __forceinline__ bool mb_point(const MsdaBinArgs &a, float lx, float ly, int &hl, int &wl, float &lh, float &lw) {
-  const float h_im = ly * (float)a.H - 0.5f, w_im = lx * (float)a.W - 0.5f;
-  const bool in = h_im > -1.f && w_im > -1.f && h_im < (float)a.H && w_im < (float)a.W;
+__device__ __forceinline__ bool mb_point_hw(int H, int W, float lx, float ly, int &hl, int &wl, float &lh, float &lw) {
+  const float h_im = ly * (float)H - 0.5f, w_im = lx * (float)W - 0.5f;
+  const bool in = h_im > -1.f && w_im > -1.f && h_im < (float)H && w_im < (float)W;
   hl = (int)floorf(h_im), wl = (int)floorf(w_im);
   lh = h_im - (float)hl, lw = w_im - (float)wl;
   return in;
 }
-__device__ __forceinline__ int mb_tile(const MsdaBinArgs &a, int hl, int wl) {
-  return (max(hl, 0) / MB_T) * a.tx + max(wl, 0) / MB_T;
+// ONE_LEVEL (a compile-time copy of L == 1) folds the level of a point or tile and the index into the per-level arrays to
+// constants in the bin, accumulate and reduce kernels: found at run time they cost the single-level training shape 15 us per call,
+// 12 of them in the accumulate kernel
+template <bool ONE_LEVEL>
+__device__ __forceinline__ int mb_level_of_tile(const MsdaMlArgs &a, int tile) {
+  if (ONE_LEVEL) return 0;
+  int l = 0;
+  while (l + 1 < a.L && tile >= a.tbase[l + 1]) ++l;
+  return l;
 }
 
-// pass 1 (SCATTER = false): points per (tile, head) of map blockIdx.y; pass 2 (SCATTER = true): the points' packed ids into
-// their bin's range.  A thread owns one (q, m) group and walks its L * P points.
-template <bool SCATTER>
-__global__ __launch_bounds__(256) void msda_bin_kernel(MsdaBinArgs a) {
+// pass 1 (SCATTER = false): points per (level, tile, head) of map blockIdx.y; pass 2 (SCATTER = true): the points' packed ids
+// into their bin's range.  A thread owns one (q, m) group and walks its L * P points; the level of a point decides map size
+// and tile numbering.
+template <bool SCATTER, bool ONE_LEVEL>
+__global__ __launch_bounds__(256) void msda_bin_kernel(MsdaMlArgs a) {
   extern __shared__ unsigned mb_hist[];                      // [nbm] counts, then (scatter) [nbm] bases
-  const int n = blockIdx.y, tid = threadIdx.x, nbm = a.tiles * a.M;
+  const int n = blockIdx.y, tid = threadIdx.x, nbm = a.nbm;
   for (int t = tid; t < nbm; t += 256) mb_hist[t] = 0u;
   __syncthreads();
   const long long g = (long long)blockIdx.x * 256 + tid;     // (q, m) of this map
@@ -317,10 +349,11 @@ __global__ __launch_bounds__(256) void msda_bin_kernel(MsdaBinArgs a) {
   for (int lp = 0; lp < a.LP; ++lp) {
     bin[lp & 15] = -1;
     if (!live) continue;
+    const int l = ONE_LEVEL ? 0 : lp / a.P;
     int hl, wl;
     float lh, lw;
-    if (!mb_point(a, loc[lp * 2], loc[lp * 2 + 1], hl, wl, lh, lw)) continue;
-    const int t = mb_tile(a, hl, wl) * a.M + m;
+    if (!mb_point_hw(a.H[l], a.W[l], loc[lp * 2], loc[lp * 2 + 1], hl, wl, lh, lw)) continue;
+    const int t = (a.tbase[l] + (max(hl, 0) / MB_T) * a.tx[l] + max(wl, 0) / MB_T) * a.M + m;
     bin[lp & 15] = t;
     rank[lp & 15] = atomicAdd(&mb_hist[t], 1u);
   }
@@ -336,16 +369,16 @@ __global__ __launch_bounds__(256) void msda_bin_kernel(MsdaBinArgs a) {
   __syncthreads();
   if (!live) return;
   const unsigned q = (unsigned)(g / a.M);
-  unsigned *items = a.items + (size_t)n * a.Lq * a.M * a.LP;
+  unsigned *items = a.scattered + (size_t)n * a.Lq * a.M * a.LP;
   for (int lp = 0; lp < a.LP; ++lp)
     if (bin[lp & 15] >= 0) items[base[bin[lp & 15]] + rank[lp & 15]] = (q << 4) | (unsigned)lp;
 }
 
 // exclusive scan of one map's bin counts + its work list: a bin with c points becomes ceil(c / MB_CHUNK) work items.  1024
 // threads, <= 8 consecutive bins per thread (nbm <= 7680), the (points, work items) pair scanned through wave shuffles.
-__global__ __launch_bounds__(1024) void msda_bin_scan_kernel(MsdaBinArgs a) {
+__global__ __launch_bounds__(1024) void msda_bin_scan_kernel(MsdaScanArgs a) {
   __shared__ unsigned long long s_wave[16];
-  const int n = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nbm = a.tiles * a.M;
+  const int n = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nbm = a.nbm;
   const int per = (nbm + 1023) / 1024, b0 = min(tid * per, nbm), b1 = min(b0 + per, nbm);
   const unsigned *count = a.count + (size_t)n * nbm;
   unsigned c[8];
@@ -374,190 +407,6 @@ __global__ __launch_bounds__(1024) void msda_bin_scan_kernel(MsdaBinArgs a) {
     run += c[k];
   }
   if (tid == 1023) binw[nbm] = wrun, a.nwork[n] = wrun;
-}
-
-// a wave = one work item: <= MB_CHUNK points of one (map, tile, head).  MFMA operand layout (v_mfma_f32_16x16x4_f32): lane
-// (i = lane & 15, k = lane >> 4) holds A[i][k] and B[k][i]; the accumulator of row tile rt holds footprint pixels
-// rt * 16 + 4 * (lane >> 4) + r of channel lane & 15.  Four points per matrix instruction, sixteen per loop pass; the ids of
-// pass k + 2 and the locations / weights / gradient rows of pass k + 1 are in flight while pass k multiplies.
-struct MbPoints {
-  float lx[4], ly[4], aw[4], g[4];
-};
-__global__ __launch_bounds__(256) void msda_bin_accumulate_kernel(MsdaBinArgs a) {
-  const int n = blockIdx.y, lane = threadIdx.x & 63, wid = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (wid >= (int)a.nwork[n]) return;
-  const unsigned *work = a.work + ((size_t)n * a.mw + wid) * 3;
-  const unsigned bin = work[0], first = work[1], last = work[2];
-  const int t = bin / a.M, m = bin - t * a.M;
-  const int y0 = (t / a.tx) * MB_T, x0 = (t % a.tx) * MB_T;
-  const int i16 = lane & 15, kg = lane >> 4;
-  const unsigned *items = a.items + (size_t)n * a.Lq * a.M * a.LP;
-  auto load_ids = [&](unsigned i0, unsigned(&id)[4]) {
-#pragma unroll
-    for (int u = 0; u < 4; ++u) id[u] = items[min(i0 + 4 * u + kg, last - 1)];
-  };
-  auto load_points = [&](const unsigned(&id)[4], MbPoints &v) {
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const size_t qm = ((size_t)n * a.Lq + (id[u] >> 4)) * a.M + m, lp = id[u] & 15u;
-      const float2 l = *(const float2 *)(a.loc + (qm * a.LP + lp) * 2);
-      v.lx[u] = l.x, v.ly[u] = l.y;
-      v.aw[u] = a.aw[qm * a.LP + lp];
-      v.g[u] = a.gout[qm * MB_D + i16];
-    }
-  };
-  f32x4 acc[6];
-#pragma unroll
-  for (int rt = 0; rt < 6; ++rt) acc[rt] = (f32x4){0.f, 0.f, 0.f, 0.f};
-  int prow[6], pcol[6];                                        // footprint row / column of this lane's pixel in row tile rt
-#pragma unroll
-  for (int rt = 0; rt < 6; ++rt) prow[rt] = (rt * 16 + i16) / (MB_T + 1), pcol[rt] = (rt * 16 + i16) % (MB_T + 1);
-  unsigned id[4];
-  MbPoints cur, nxt;
-  load_ids(first, id);
-  load_points(id, cur);
-  load_ids(first + 16, id);
-  for (unsigned i0 = first; i0 < last; i0 += 16) {
-    load_points(id, nxt);
-    load_ids(i0 + 32, id);
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      int hl, wl;
-      float lh, lw;
-      mb_point(a, cur.lx[u], cur.ly[u], hl, wl, lh, lw);      // (in bounds: it was binned)
-      const float b = i0 + 4 * u + kg < last ? cur.g[u] * cur.aw[u] : 0.f;
-      // the four corner weights are separable: (row weight) x (column weight), a corner outside the map = a zero factor
-      const int ry = hl - y0, rx = wl - x0, ry1 = ry + 1, rx1 = rx + 1;      // footprint row / column of the top-left corner
-      const float wt = hl >= 0 ? 1.f - lh : 0.f, wb = hl + 1 <= a.H - 1 ? lh : 0.f;
-      const float wl_ = wl >= 0 ? 1.f - lw : 0.f, wr = wl + 1 <= a.W - 1 ? lw : 0.f;
-#pragma unroll
-      for (int rt = 0; rt < 6; ++rt) {
-        float wy = prow[rt] == ry ? wt : 0.f, wx = pcol[rt] == rx ? wl_ : 0.f;
-        wy = prow[rt] == ry1 ? wb : wy;
-        wx = pcol[rt] == rx1 ? wr : wx;
-        acc[rt] = __builtin_amdgcn_mfma_f32_16x16x4f32(wy * wx, b, acc[rt], 0, 0, 0);
-      }
-    }
-    cur = nxt;
-  }
-  float *slab = a.slabs + ((size_t)n * a.mw + wid) * MB_FOOT * MB_D;
-#pragma unroll
-  for (int rt = 0; rt < 6; ++rt)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int px = rt * 16 + 4 * kg + r;
-      if (px < MB_FOOT) slab[px * MB_D + i16] = acc[rt][r];
-    }
-}
-
-// grad_value of one (map, tile): every pixel of the tile's 8 x 8 interior = the sum of that pixel over the tile's own work
-// items + the halo row / column / corner of the tiles above, to the left and above-left, head by head.  A pure gather.
-__global__ __launch_bounds__(256) void msda_bin_reduce_kernel(MsdaBinArgs a) {
-  const int n = blockIdx.y, t = blockIdx.x, tyi = t / a.tx, txi = t - tyi * a.tx, y0 = tyi * MB_T, x0 = txi * MB_T;
-  const int C = a.M * MB_D, C4 = C / 4, nbm = a.tiles * a.M;
-  const unsigned *binw = a.binw + (size_t)n * (nbm + 1);
-  const float *slabs = a.slabs + (size_t)n * a.mw * MB_FOOT * MB_D;
-  for (int i = threadIdx.x; i < MB_T * MB_T * C4; i += 256) {
-    const int px = i / C4, c = (i - px * C4) * 4, ly = px / MB_T, lx = px - ly * MB_T, m = c / MB_D, cc = c - m * MB_D;
-    if (y0 + ly >= a.H || x0 + lx >= a.W) continue;
-    f32x4 acc = (f32x4){0.f, 0.f, 0.f, 0.f};
-    auto add = [&](int b, int fy, int fx) {
-      const unsigned w0 = binw[b], w1 = binw[b + 1];
-      for (unsigned w = w0; w < w1; ++w)
-        acc += *(const f32x4 *)(slabs + ((size_t)w * MB_FOOT + fy * (MB_T + 1) + fx) * MB_D + cc);
-    };
-    add(t * a.M + m, ly, lx);
-    if (ly == 0 && tyi > 0) add((t - a.tx) * a.M + m, MB_T, lx);
-    if (lx == 0 && txi > 0) add((t - 1) * a.M + m, ly, MB_T);
-    if (ly == 0 && lx == 0 && tyi > 0 && txi > 0) add((t - a.tx - 1) * a.M + m, MB_T, MB_T);
-    *(f32x4 *)(a.gvalue + ((size_t)n * a.S + (size_t)(y0 + ly) * a.W + x0 + lx) * C + c) = acc;
-  }
-}
-
-// ---------------------------------------------------------------------------------------------------------
-// The same without global atomics for L >= 1 levels (L * P <= 16) and heads of 16 / 32 / 64 channels (msda_binml_*).  A bin is
-// a (level, tile, head): the levels' tiles are numbered one level after the other (tbase), every level has its own map size,
-// tile row length and first pixel, and grad_value [N][S][M][D] is still written exactly once because the levels tile S without
-// gaps (checked on the host: df3d_ms_deform_attn_backward_plan).  A head of D = 16 * NS channels is NS column slices of the same
-// product: the A operand (the bilinear weights) is formed once per point and row tile and multiplies NS gradient rows, the
-// slab is [81][D].  The scan kernel above is shared (its bins are just numbered 0 .. nbm - 1).
-//
-// ORDERED (df3d_ms_deform_attn_backward_binned_ml(..., ordered = 1)): the scatter of msda_bin*_kernel leaves the points of a bin
-// in the order in which lanes and workgroups won LDS / global integer atomics, and the fp32 sums of the accumulate kernel follow
-// that order.  msda_bin_sort_kernel puts every bin's packed ids (q << 4 | lp, unique within a bin) in ascending order first; the
-// work items are then every MB_CHUNK ids of that sequence, so grad_value is a function of the inputs alone.  A workgroup per
-// bin: <= 64 ids are ranked by counting inside one wave, <= 1024 go through a bitonic network in LDS, and a larger bin (the
-// pile-up on the unseen voxels' reference point: thousands to tens of thousands of ids) is written out from a bit directory --
-// one bit per possible id in 256 Ki-id windows, set with LDS integer atomics, read back in order with a popcount scan: linear
-// in the ids (the network's log^2 passes over 8192 ids cost more than the rest of the backward at the training shape).
-constexpr int MB_LMAX = 16, MS_WORDS = 8192, MS_WINDOW = MS_WORDS * 32, MS_NETWORK = 1024;
-#define MS_PHYS(i) ((i) + ((i) >> 5))                         // (a thread walks 32 consecutive words: one pad word per 32)
-
-struct MsdaMlArgs {
-  const float *loc, *aw, *gout;
-  const unsigned char *nz;
-  float *gvalue;
-  int N, S, M, D, Lq, L, P, LP, nbm, mw;
-  int H[MB_LMAX], W[MB_LMAX], tx[MB_LMAX], start[MB_LMAX], tbase[MB_LMAX + 1];   // per level; tbase: first tile of the level
-  unsigned *count, *cursor, *offset, *binw, *nwork, *work;   // as in MsdaBinArgs
-  const unsigned *items;                                      // what the accumulate kernel reads (the ordered copy if there is one)
-  unsigned *scattered, *sorted;                               // [N][ppm] each: the scatter's output; the ordered copy
-  float *slabs;                                               // [N][mw][MB_FOOT][D]
-};
-
-__device__ __forceinline__ bool mb_point_hw(int H, int W, float lx, float ly, int &hl, int &wl, float &lh, float &lw) {
-  const float h_im = ly * (float)H - 0.5f, w_im = lx * (float)W - 0.5f;
-  const bool in = h_im > -1.f && w_im > -1.f && h_im < (float)H && w_im < (float)W;
-  hl = (int)floorf(h_im), wl = (int)floorf(w_im);
-  lh = h_im - (float)hl, lw = w_im - (float)wl;
-  return in;
-}
-__device__ __forceinline__ int mb_level_of_tile(const MsdaMlArgs &a, int tile) {
-  int l = 0;
-  while (l + 1 < a.L && tile >= a.tbase[l + 1]) ++l;
-  return l;
-}
-
-// msda_bin_kernel with the level of a point deciding map size and tile numbering
-template <bool SCATTER>
-__global__ __launch_bounds__(256) void msda_binml_kernel(MsdaMlArgs a) {
-  extern __shared__ unsigned mb_hist[];                      // [nbm] counts, then (scatter) [nbm] bases
-  const int n = blockIdx.y, tid = threadIdx.x, nbm = a.nbm;
-  for (int t = tid; t < nbm; t += 256) mb_hist[t] = 0u;
-  __syncthreads();
-  const long long g = (long long)blockIdx.x * 256 + tid;     // (q, m) of this map
-  const bool live = g < (long long)a.Lq * a.M && a.nz[(size_t)n * a.Lq * a.M + g];
-  const int m = (int)(g % a.M);
-  const float *loc = a.loc + ((size_t)n * a.Lq * a.M + (size_t)(live ? g : 0)) * a.LP * 2;
-  unsigned rank[16];
-  int bin[16];
-#pragma unroll 1
-  for (int lp = 0; lp < a.LP; ++lp) {
-    bin[lp & 15] = -1;
-    if (!live) continue;
-    const int l = lp / a.P;
-    int hl, wl;
-    float lh, lw;
-    if (!mb_point_hw(a.H[l], a.W[l], loc[lp * 2], loc[lp * 2 + 1], hl, wl, lh, lw)) continue;
-    const int t = (a.tbase[l] + (max(hl, 0) / MB_T) * a.tx[l] + max(wl, 0) / MB_T) * a.M + m;
-    bin[lp & 15] = t;
-    rank[lp & 15] = atomicAdd(&mb_hist[t], 1u);
-  }
-  __syncthreads();
-  if (!SCATTER) {
-    for (int t = tid; t < nbm; t += 256)
-      if (mb_hist[t]) atomicAdd(&a.count[(size_t)n * nbm + t], mb_hist[t]);
-    return;
-  }
-  unsigned *base = mb_hist + nbm;
-  for (int t = tid; t < nbm; t += 256)
-    base[t] = mb_hist[t] ? a.offset[(size_t)n * nbm + t] + atomicAdd(&a.cursor[(size_t)n * nbm + t], mb_hist[t]) : 0u;
-  __syncthreads();
-  if (!live) return;
-  const unsigned q = (unsigned)(g / a.M);
-  unsigned *items = a.scattered + (size_t)n * a.Lq * a.M * a.LP;
-  for (int lp = 0; lp < a.LP; ++lp)
-    if (bin[lp & 15] >= 0) items[base[bin[lp & 15]] + rank[lp & 15]] = (q << 4) | (unsigned)lp;
 }
 
 // a workgroup = one bin of map blockIdx.y: its ids from `scattered` to `sorted`, ascending (see ORDERED above).  Two launches
@@ -636,19 +485,23 @@ __global__ __launch_bounds__(256) void msda_bin_sort_kernel(MsdaMlArgs a) {
   }
 }
 
-// msda_bin_accumulate_kernel for a (level, tile, head) bin and NS slices of 16 channels
+// a wave = one work item: <= MB_CHUNK points of one (map, level, tile, head), NS slices of 16 channels.  MFMA operand layout
+// (v_mfma_f32_16x16x4_f32): lane (i = lane & 15, k = lane >> 4) holds A[i][k] and B[k][i]; the accumulator of row tile rt holds
+// footprint pixels rt * 16 + 4 * (lane >> 4) + r of channel lane & 15 of the slice.  Four points per matrix instruction, sixteen
+// per loop pass; the ids of pass k + 2 and the locations / weights / gradient rows of pass k + 1 are in flight while pass k
+// multiplies.
 template <int NS>
-struct MbPointsMl {
+struct MbPoints {
   float lx[4], ly[4], aw[4], g[4][NS];
 };
-template <int NS>
-__global__ __launch_bounds__(256) void msda_binml_accumulate_kernel(MsdaMlArgs a) {
+template <int NS, bool ONE_LEVEL>
+__global__ __launch_bounds__(256) void msda_bin_accumulate_kernel(MsdaMlArgs a) {
   constexpr int D = NS * 16;
   const int n = blockIdx.y, lane = threadIdx.x & 63, wid = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (wid >= (int)a.nwork[n]) return;
   const unsigned *work = a.work + ((size_t)n * a.mw + wid) * 3;
   const unsigned bin = work[0], first = work[1], last = work[2];
-  const int tg = bin / a.M, m = bin - tg * a.M, lv = mb_level_of_tile(a, tg), t = tg - a.tbase[lv];
+  const int tg = bin / a.M, m = bin - tg * a.M, lv = mb_level_of_tile<ONE_LEVEL>(a, tg), t = tg - a.tbase[lv];
   const int H = a.H[lv], W = a.W[lv], tx = a.tx[lv];
   const int y0 = (t / tx) * MB_T, x0 = (t % tx) * MB_T;
   const int i16 = lane & 15, kg = lane >> 4;
@@ -657,7 +510,7 @@ __global__ __launch_bounds__(256) void msda_binml_accumulate_kernel(MsdaMlArgs a
 #pragma unroll
     for (int u = 0; u < 4; ++u) id[u] = items[min(i0 + 4 * u + kg, last - 1)];
   };
-  auto load_points = [&](const unsigned(&id)[4], MbPointsMl<NS> &v) {
+  auto load_points = [&](const unsigned(&id)[4], MbPoints<NS> &v) {
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
       const size_t qm = ((size_t)n * a.Lq + (id[u] >> 4)) * a.M + m, lp = id[u] & 15u;
@@ -677,7 +530,7 @@ __global__ __launch_bounds__(256) void msda_binml_accumulate_kernel(MsdaMlArgs a
 #pragma unroll
   for (int rt = 0; rt < 6; ++rt) prow[rt] = (rt * 16 + i16) / (MB_T + 1), pcol[rt] = (rt * 16 + i16) % (MB_T + 1);
   unsigned id[4];
-  MbPointsMl<NS> cur, nxt;
+  MbPoints<NS> cur, nxt;
   load_ids(first, id);
   load_points(id, cur);
   load_ids(first + 16, id);
@@ -718,9 +571,12 @@ __global__ __launch_bounds__(256) void msda_binml_accumulate_kernel(MsdaMlArgs a
       }
 }
 
-// msda_bin_reduce_kernel for a tile of any level: M * D channels per pixel, the level's pixels start at a.start[level]
-__global__ __launch_bounds__(256) void msda_binml_reduce_kernel(MsdaMlArgs a) {
-  const int n = blockIdx.y, tg = blockIdx.x, lv = mb_level_of_tile(a, tg), t = tg - a.tbase[lv];
+// grad_value of one (map, level, tile): every pixel of the tile's 8 x 8 interior = the sum of that pixel over the tile's own
+// work items + the halo row / column / corner of the tiles above, to the left and above-left, head by head.  A pure gather:
+// M * D channels per pixel, the level's pixels start at a.start[level].
+template <bool ONE_LEVEL>
+__global__ __launch_bounds__(256) void msda_bin_reduce_kernel(MsdaMlArgs a) {
+  const int n = blockIdx.y, tg = blockIdx.x, lv = mb_level_of_tile<ONE_LEVEL>(a, tg), t = tg - a.tbase[lv];
   const int H = a.H[lv], W = a.W[lv], tx = a.tx[lv];
   const int tyi = t / tx, txi = t - tyi * tx, y0 = tyi * MB_T, x0 = txi * MB_T;
   const int D = a.D, C = a.M * D, C4 = C / 4;
@@ -866,81 +722,7 @@ extern "C" int df3d_ms_deform_attn_backward(const float *value, const int64_t *s
   DF3D_LAUNCH_CHECK();
   return DF3D_OK;
 }
-
-// ---- binned backward (single-level maps, 16-channel heads): see msda_bin_* above ----------------------------------------------
-static size_t mb_align(size_t v) { return (v + 255) & ~(size_t)255; }
-static size_t mb_nbm(int M, int H, int W) { return (size_t)cdiv(H, MB_T) * cdiv(W, MB_T) * M; }
-static size_t mb_mw(int M, int Lq, int LP, int H, int W) { return mb_nbm(M, H, W) + (size_t)Lq * M * LP / MB_CHUNK + 1; }
-
-extern "C" size_t df3d_ms_deform_attn_backward_binned_workspace_bytes(int N, int M, int Lq, int LP, int H, int W) {
-  const size_t nbm = mb_nbm(M, H, W), n = (size_t)N;
-  return mb_align(n * Lq * M) + mb_align(n * nbm * 4) * 3 + mb_align(n * (nbm + 1) * 4) + mb_align(n * 4) +
-         mb_align(n * mb_mw(M, Lq, LP, H, W) * 12) + mb_align(n * Lq * M * LP * 4);
-}
-/* + the work items' footprints: N * mw * 81 * 16 floats, mw = tiles * M + Lq * M * P / 512 + 1 work items per map */
-extern "C" size_t df3d_ms_deform_attn_backward_binned_slab_bytes(int N, int M, int D, int Lq, int LP, int H, int W) {
-  (void)D;
-  return (size_t)N * mb_mw(M, Lq, LP, H, W) * MB_FOOT * MB_D * 4;
-}
-
-extern "C" int df3d_ms_deform_attn_backward_binned(const float *value, const int64_t *spatial_shapes, const int64_t *level_start_index,
-                                                   const float *sampling_loc, const float *attn_weight, const float *grad_output,
-                                                   int N, int M, int D, int Lq, int P, int H, int W, float *grad_value,
-                                                   float *grad_sampling_loc, float *grad_attn_weight, void *workspace,
-                                                   size_t workspace_bytes, float *slabs, void *stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  DF3D_CHECK_ARG(N >= 0 && M > 0 && D > 0 && Lq >= 0 && P > 0 && H > 0 && W > 0, "ms_deform_attn_backward_binned: bad sizes");
-  DF3D_CHECK_ARG(D == MB_D && P <= 16 && Lq < (1 << 28), "ms_deform_attn_backward_binned: head width %d / %d points not served", D, P);
-  const int S = H * W, C = M * D, tx = cdiv(W, MB_T), ty = cdiv(H, MB_T), tiles = tx * ty;
-  DF3D_CHECK_ARG((size_t)tiles * M <= 7680, "ms_deform_attn_backward_binned: %d tiles x %d heads exceed the LDS budget", tiles, M);
-  DF3D_CHECK_ARG(N <= 65535 && (long long)Lq * M * P < (1LL << 31), "ms_deform_attn_backward_binned: %d maps x %d queries", N, Lq);
-  if (N == 0) return DF3D_OK;
-  DF3D_CHECK_ARG(value && spatial_shapes && level_start_index && grad_value, "ms_deform_attn_backward_binned: null argument");
-  if (Lq == 0) {
-    DF3D_HIP(hipMemsetAsync(grad_value, 0, (size_t)N * S * C * sizeof(float), stream));
-    return DF3D_OK;
-  }
-  DF3D_CHECK_ARG(sampling_loc && attn_weight && grad_output && grad_sampling_loc && grad_attn_weight && workspace && slabs,
-                 "ms_deform_attn_backward_binned: null argument");
-  DF3D_CHECK_ARG(workspace_bytes >= df3d_ms_deform_attn_backward_binned_workspace_bytes(N, M, Lq, P, H, W),
-                 "ms_deform_attn_backward_binned: workspace too small");
-  const size_t nbm = mb_nbm(M, H, W), n = (size_t)N;
-  const int mw = (int)mb_mw(M, Lq, P, H, W);
-  char *w = (char *)workspace;
-  unsigned char *nz = (unsigned char *)w;
-  w += mb_align(n * Lq * M);
-  unsigned *count = (unsigned *)w;
-  w += mb_align(n * nbm * 4);
-  unsigned *cursor = (unsigned *)w;                            // (adjacent to `count`: one memset clears both)
-  w += mb_align(n * nbm * 4);
-  unsigned *offset = (unsigned *)w;
-  w += mb_align(n * nbm * 4);
-  unsigned *binw = (unsigned *)w;
-  w += mb_align(n * (nbm + 1) * 4);
-  unsigned *nwork = (unsigned *)w;
-  w += mb_align(n * 4);
-  unsigned *work = (unsigned *)w;
-  w += mb_align(n * mw * 12);
-  unsigned *items = (unsigned *)w;
-  DF3D_HIP(hipMemsetAsync(count, 0, mb_align(n * nbm * 4) * 2, stream));
-  // location / weight gradients + the groups that carry a gradient (the gather half of the col2im)
-  MsdaBwdArgs g = {value, spatial_shapes, level_start_index, sampling_loc, attn_weight, grad_output,
-                   grad_value, grad_sampling_loc, grad_attn_weight, N, S, M, D, Lq, 1, P, nz};
-  const long long total = (long long)N * Lq * M * (D / 4);
-  hipLaunchKernelGGL((msda_bwd_vec4_kernel<MB_D / 4, true>), dim3(cdiv(total, 256)), dim3(256), 0, stream, g);
-  MsdaBinArgs b = {sampling_loc, attn_weight, grad_output, nz, grad_value, N, S, M, D, Lq, P, H, W, tx, ty, tiles,
-                   count, cursor, offset, binw, nwork, work, items, mw, slabs};
-  const dim3 bgrid(cdiv((long long)Lq * M, 256), N);
-  hipLaunchKernelGGL(msda_bin_kernel<false>, bgrid, dim3(256), nbm * 4, stream, b);
-  hipLaunchKernelGGL(msda_bin_scan_kernel, dim3(N), dim3(1024), 0, stream, b);
-  hipLaunchKernelGGL(msda_bin_kernel<true>, bgrid, dim3(256), nbm * 8, stream, b);
-  hipLaunchKernelGGL(msda_bin_accumulate_kernel, dim3(cdiv(mw, 4), N), dim3(256), 0, stream, b);
-  hipLaunchKernelGGL(msda_bin_reduce_kernel, dim3(tiles, N), dim3(256), 0, stream, b);
-  DF3D_LAUNCH_CHECK();
-  return DF3D_OK;
-}
-
-// ---- binned backward, any number of levels / heads of 16, 32, 64 channels / ordered: see msda_binml_* above -------------------
+// ---- binned backward, any number of levels / heads of 16, 32, 64 channels / ordered: see msda_bin_* above ---------------------
 // What serves a shape.  Host only (no HIP call).  mode: 0 = default, 1 = atomic, 2 = ordered ("sorted").  -> 0 atomic kernels,
 // 1 binned, 2 binned + ordered, -1 ordered asked for and not served (df3d_last_error names the limit that failed).
 static const char *mb_limit(int N, int S, int M, int D, int Lq, int L, int P, const int64_t *hw, const int64_t *start, bool ordered,
@@ -983,24 +765,107 @@ extern "C" int df3d_ms_deform_attn_backward_plan(int N, int S, int M, int D, int
   return -1;
 }
 
-static size_t mb_nbm_ml(int M, int L, const int64_t *hw) {
+// The workspace of a call, carved in this order; `bytes` is what the ..._workspace_bytes functions return.
+struct MbLayout {
+  size_t nbm, ppm, mw;                                         // per map: bins, point slots, work items (upper bound)
+  size_t nz, count, cursor, offset, binw, nwork, work, scattered, sorted, bytes;   // byte offsets of the pieces; the total
+};
+static MbLayout mb_layout(int N, int M, int Lq, int L, int P, const int64_t *hw, bool ordered) {
+  MbLayout w = {};
   size_t tiles = 0;
   for (int l = 0; l < L; ++l) tiles += (size_t)cdiv((int)hw[l * 2], MB_T) * cdiv((int)hw[l * 2 + 1], MB_T);
-  return tiles * M;
+  w.nbm = tiles * M, w.ppm = (size_t)Lq * M * L * P, w.mw = w.nbm + w.ppm / MB_CHUNK + 1;
+  const size_t n = (size_t)N;
+  auto take = [&w](size_t bytes) { return (w.bytes = arena_need(w.bytes, bytes)) - bytes; };
+  w.nz = take(n * Lq * M);
+  w.count = take(n * w.nbm * 4);
+  w.cursor = take(n * w.nbm * 4);                              // (adjacent to `count`: one memset up to `offset` clears both)
+  w.offset = take(n * w.nbm * 4);
+  w.binw = take(n * (w.nbm + 1) * 4);
+  w.nwork = take(n * 4);
+  w.work = take(n * w.mw * 12);
+  w.scattered = take(n * w.ppm * 4);
+  if (ordered) w.sorted = take(n * w.ppm * 4);
+  w.bytes = align_up(w.bytes, 256);
+  return w;
 }
-static size_t mb_mw_ml(int M, int Lq, int L, int P, const int64_t *hw) { return mb_nbm_ml(M, L, hw) + (size_t)Lq * M * L * P / MB_CHUNK + 1; }
+
+// The launches of a call: heads of DD channels, ONE_LEVEL = (L == 1).  One memset before them, six kernels (eight when ordered).
+template <int DD, bool ONE_LEVEL>
+static void mb_launch(const MsdaBwdArgs &g, const MsdaMlArgs &b, const MsdaScanArgs &sc, hipStream_t stream) {
+  const long long total = (long long)b.N * b.Lq * b.M * (DD / 4);
+  const dim3 bgrid(cdiv((long long)b.Lq * b.M, 256), b.N), wgrid(cdiv(b.mw, 4), b.N), sgrid(b.nbm, b.N);
+  // location / weight gradients + the groups that carry a gradient (the gather half of the col2im)
+  hipLaunchKernelGGL((msda_bwd_vec4_kernel<DD / 4, true>), dim3(cdiv(total, 256)), dim3(256), 0, stream, g);
+  hipLaunchKernelGGL((msda_bin_kernel<false, ONE_LEVEL>), bgrid, dim3(256), b.nbm * 4, stream, b);
+  hipLaunchKernelGGL(msda_bin_scan_kernel, dim3(b.N), dim3(1024), 0, stream, sc);
+  hipLaunchKernelGGL((msda_bin_kernel<true, ONE_LEVEL>), bgrid, dim3(256), b.nbm * 8, stream, b);
+  if (b.sorted) {
+    hipLaunchKernelGGL(msda_bin_sort_kernel<false>, sgrid, dim3(256), 0, stream, b);
+    hipLaunchKernelGGL(msda_bin_sort_kernel<true>, sgrid, dim3(256), 0, stream, b);
+  }
+  hipLaunchKernelGGL((msda_bin_accumulate_kernel<DD / 16, ONE_LEVEL>), wgrid, dim3(256), 0, stream, b);
+  hipLaunchKernelGGL(msda_bin_reduce_kernel<ONE_LEVEL>, dim3(b.tbase[MB_LMAX], b.N), dim3(256), 0, stream, b);   // (a workgroup per tile)
+}
+
+// Both entries from here on (`who` names the caller in the messages); the shape has passed the caller's own checks.
+static int mb_backward(const char *who, const float *value, const int64_t *spatial_shapes, const int64_t *level_start_index,
+                       const float *sampling_loc, const float *attn_weight, const float *grad_output, const int64_t *level_hw,
+                       const int64_t *level_start, int N, int S, int M, int D, int Lq, int L, int P, int ordered, float *grad_value,
+                       float *grad_sampling_loc, float *grad_attn_weight, void *workspace, size_t workspace_bytes, float *slabs,
+                       hipStream_t stream) {
+  if (N == 0) return DF3D_OK;
+  DF3D_CHECK_ARG(value && spatial_shapes && level_start_index && grad_value, "%s: null argument", who);
+  if (Lq == 0) {
+    DF3D_HIP(hipMemsetAsync(grad_value, 0, (size_t)N * S * M * D * sizeof(float), stream));
+    return DF3D_OK;
+  }
+  DF3D_CHECK_ARG(sampling_loc && attn_weight && grad_output && grad_sampling_loc && grad_attn_weight && workspace && slabs,
+                 "%s: null argument", who);
+  const MbLayout w = mb_layout(N, M, Lq, L, P, level_hw, ordered != 0);
+  DF3D_CHECK_ARG(workspace_bytes >= w.bytes, "%s: workspace too small", who);
+  char *ws = (char *)workspace;
+  DF3D_HIP(hipMemsetAsync(ws + w.count, 0, w.offset - w.count, stream));
+  MsdaBwdArgs g = {value, spatial_shapes, level_start_index, sampling_loc, attn_weight, grad_output,
+                   grad_value, grad_sampling_loc, grad_attn_weight, N, S, M, D, Lq, L, P, (unsigned char *)(ws + w.nz)};
+  MsdaMlArgs b = {};
+  b.loc = sampling_loc, b.aw = attn_weight, b.gout = grad_output, b.nz = g.nz, b.gvalue = grad_value;
+  b.N = N, b.S = S, b.M = M, b.D = D, b.Lq = Lq, b.L = L, b.P = P, b.LP = L * P, b.nbm = (int)w.nbm, b.mw = (int)w.mw;
+  int tiles = 0;
+  for (int l = 0; l < L; ++l) {
+    b.H[l] = (int)level_hw[l * 2], b.W[l] = (int)level_hw[l * 2 + 1], b.tx[l] = cdiv(b.W[l], MB_T), b.start[l] = (int)level_start[l];
+    b.tbase[l] = tiles;
+    tiles += b.tx[l] * cdiv(b.H[l], MB_T);
+  }
+  for (int l = L; l <= MB_LMAX; ++l) b.tbase[l] = tiles;
+  b.count = (unsigned *)(ws + w.count), b.cursor = (unsigned *)(ws + w.cursor), b.offset = (unsigned *)(ws + w.offset);
+  b.binw = (unsigned *)(ws + w.binw), b.nwork = (unsigned *)(ws + w.nwork), b.work = (unsigned *)(ws + w.work);
+  b.scattered = (unsigned *)(ws + w.scattered), b.sorted = ordered ? (unsigned *)(ws + w.sorted) : nullptr;
+  b.items = ordered ? b.sorted : b.scattered, b.slabs = slabs;
+  const MsdaScanArgs sc = {b.count, b.offset, b.binw, b.nwork, b.work, b.nbm, b.mw};
+  switch (D) {
+#define DF3D_MSDA_BIN_CASE(DD)                                                                 \
+  case DD:                                                                                     \
+    L == 1 ? mb_launch<DD, true>(g, b, sc, stream) : mb_launch<DD, false>(g, b, sc, stream);   \
+    break;
+    DF3D_MSDA_BIN_CASE(16)
+    DF3D_MSDA_BIN_CASE(32)
+    DF3D_MSDA_BIN_CASE(64)
+#undef DF3D_MSDA_BIN_CASE
+  }
+  DF3D_LAUNCH_CHECK();
+  return DF3D_OK;
+}
 
 extern "C" size_t df3d_ms_deform_attn_backward_binned_ml_workspace_bytes(int N, int M, int Lq, int L, int P, const int64_t *level_hw,
                                                                          int ordered) {
   if (!level_hw || N < 0 || M <= 0 || Lq < 0 || L <= 0 || P <= 0) return 0;
-  const size_t nbm = mb_nbm_ml(M, L, level_hw), n = (size_t)N;
-  return mb_align(n * Lq * M) + mb_align(n * nbm * 4) * 3 + mb_align(n * (nbm + 1) * 4) + mb_align(n * 4) +
-         mb_align(n * mb_mw_ml(M, Lq, L, P, level_hw) * 12) + mb_align(n * Lq * M * L * P * 4) * (ordered ? 2 : 1);
+  return mb_layout(N, M, Lq, L, P, level_hw, ordered != 0).bytes;
 }
-/* + the work items' footprints: N * mw * 81 * D floats */
+/* + the work items' footprints: N * mw * 81 * D floats, mw = tiles * M + Lq * M * L * P / 512 + 1 work items per map */
 extern "C" size_t df3d_ms_deform_attn_backward_binned_ml_slab_bytes(int N, int M, int D, int Lq, int L, int P, const int64_t *level_hw) {
   if (!level_hw || N < 0 || M <= 0 || D <= 0 || Lq < 0 || L <= 0 || P <= 0) return 0;
-  return (size_t)N * mb_mw_ml(M, Lq, L, P, level_hw) * MB_FOOT * D * 4;
+  return (size_t)N * mb_layout(N, M, Lq, L, P, level_hw, false).mw * MB_FOOT * D * 4;
 }
 
 extern "C" int df3d_ms_deform_attn_backward_binned_ml(const float *value, const int64_t *spatial_shapes, const int64_t *level_start_index,
@@ -1008,8 +873,7 @@ extern "C" int df3d_ms_deform_attn_backward_binned_ml(const float *value, const 
                                                       const int64_t *level_hw, const int64_t *level_start, int N, int M, int D, int Lq,
                                                       int L, int P, int ordered, float *grad_value, float *grad_sampling_loc,
                                                       float *grad_attn_weight, void *workspace, size_t workspace_bytes, float *slabs,
-                                                      void *stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
+                                                      void *stream) {
   DF3D_CHECK_ARG(N >= 0 && M > 0 && D > 0 && Lq >= 0 && L > 0 && P > 0 && level_hw && level_start,
                  "ms_deform_attn_backward_binned_ml: bad sizes / null level arrays");
   long long S = 0;
@@ -1018,76 +882,34 @@ extern "C" int df3d_ms_deform_attn_backward_binned_ml(const float *value, const 
   const char *why = S > 0 && S < (1LL << 31) ? mb_limit(N, (int)S, M, D, Lq, L, P, level_hw, level_start, ordered != 0, buf, sizeof buf)
                                               : "bad level sizes";
   DF3D_CHECK_ARG(!why, "ms_deform_attn_backward_binned_ml: not served: %s", why);
-  if (N == 0) return DF3D_OK;
-  DF3D_CHECK_ARG(value && spatial_shapes && level_start_index && grad_value, "ms_deform_attn_backward_binned_ml: null argument");
-  const int C = M * D;
-  if (Lq == 0) {
-    DF3D_HIP(hipMemsetAsync(grad_value, 0, (size_t)N * S * C * sizeof(float), stream));
-    return DF3D_OK;
-  }
-  DF3D_CHECK_ARG(sampling_loc && attn_weight && grad_output && grad_sampling_loc && grad_attn_weight && workspace && slabs,
-                 "ms_deform_attn_backward_binned_ml: null argument");
-  DF3D_CHECK_ARG(workspace_bytes >= df3d_ms_deform_attn_backward_binned_ml_workspace_bytes(N, M, Lq, L, P, level_hw, ordered),
-                 "ms_deform_attn_backward_binned_ml: workspace too small");
-  const size_t nbm = mb_nbm_ml(M, L, level_hw), n = (size_t)N, ppm = (size_t)Lq * M * L * P;
-  const int mw = (int)mb_mw_ml(M, Lq, L, P, level_hw);
-  char *w = (char *)workspace;
-  unsigned char *nz = (unsigned char *)w;
-  w += mb_align(n * Lq * M);
-  unsigned *count = (unsigned *)w;
-  w += mb_align(n * nbm * 4);
-  unsigned *cursor = (unsigned *)w;                            // (adjacent to `count`: one memset clears both)
-  w += mb_align(n * nbm * 4);
-  unsigned *offset = (unsigned *)w;
-  w += mb_align(n * nbm * 4);
-  unsigned *binw = (unsigned *)w;
-  w += mb_align(n * (nbm + 1) * 4);
-  unsigned *nwork = (unsigned *)w;
-  w += mb_align(n * 4);
-  unsigned *work = (unsigned *)w;
-  w += mb_align(n * mw * 12);
-  unsigned *scattered = (unsigned *)w;
-  w += mb_align(n * ppm * 4);
-  unsigned *sorted = ordered ? (unsigned *)w : nullptr;
-  DF3D_HIP(hipMemsetAsync(count, 0, mb_align(n * nbm * 4) * 2, stream));
-  MsdaBwdArgs g = {value, spatial_shapes, level_start_index, sampling_loc, attn_weight, grad_output,
-                   grad_value, grad_sampling_loc, grad_attn_weight, N, (int)S, M, D, Lq, L, P, nz};
-  const long long total = (long long)N * Lq * M * (D / 4);
-  MsdaMlArgs b = {};
-  b.loc = sampling_loc, b.aw = attn_weight, b.gout = grad_output, b.nz = nz, b.gvalue = grad_value;
-  b.N = N, b.S = (int)S, b.M = M, b.D = D, b.Lq = Lq, b.L = L, b.P = P, b.LP = L * P, b.nbm = (int)nbm, b.mw = mw;
-  int tiles = 0;
-  for (int l = 0; l < L; ++l) {
-    b.H[l] = (int)level_hw[l * 2], b.W[l] = (int)level_hw[l * 2 + 1], b.tx[l] = cdiv(b.W[l], MB_T), b.start[l] = (int)level_start[l];
-    b.tbase[l] = tiles;
-    tiles += b.tx[l] * cdiv(b.H[l], MB_T);
-  }
-  for (int l = L; l <= MB_LMAX; ++l) b.tbase[l] = tiles;
-  b.count = count, b.cursor = cursor, b.offset = offset, b.binw = binw, b.nwork = nwork, b.work = work;
-  b.scattered = scattered, b.sorted = sorted, b.items = ordered ? sorted : scattered, b.slabs = slabs;
-  MsdaBinArgs sc = {};                                         // the scan kernel's view: nbm = tiles * M bins, numbered through
-  sc.M = M, sc.tiles = tiles, sc.count = count, sc.offset = offset, sc.binw = binw, sc.nwork = nwork, sc.work = work, sc.mw = mw;
-  const dim3 bgrid(cdiv((long long)Lq * M, 256), N), wgrid(cdiv(mw, 4), N);
-  // location / weight gradients + the groups that carry a gradient (the gather half of the col2im)
-  switch (D) {
-#define DF3D_MSDA_ML_CASE(DD)                                                                                              \
-  case DD:                                                                                                                 \
-    hipLaunchKernelGGL((msda_bwd_vec4_kernel<DD / 4, true>), dim3(cdiv(total, 256)), dim3(256), 0, stream, g);             \
-    hipLaunchKernelGGL(msda_binml_kernel<false>, bgrid, dim3(256), nbm * 4, stream, b);                                    \
-    hipLaunchKernelGGL(msda_bin_scan_kernel, dim3(N), dim3(1024), 0, stream, sc);                                          \
-    hipLaunchKernelGGL(msda_binml_kernel<true>, bgrid, dim3(256), nbm * 8, stream, b);                                     \
-    if (ordered) {                                                                                                         \
-      hipLaunchKernelGGL(msda_bin_sort_kernel<false>, dim3(nbm, N), dim3(256), 0, stream, b);                              \
-      hipLaunchKernelGGL(msda_bin_sort_kernel<true>, dim3(nbm, N), dim3(256), 0, stream, b);                               \
-    }                                                                                                                      \
-    hipLaunchKernelGGL(msda_binml_accumulate_kernel<DD / 16>, wgrid, dim3(256), 0, stream, b);                             \
-    break;
-    DF3D_MSDA_ML_CASE(16)
-    DF3D_MSDA_ML_CASE(32)
-    DF3D_MSDA_ML_CASE(64)
-#undef DF3D_MSDA_ML_CASE
-  }
-  hipLaunchKernelGGL(msda_binml_reduce_kernel, dim3(tiles, N), dim3(256), 0, stream, b);
-  DF3D_LAUNCH_CHECK();
-  return DF3D_OK;
+  return mb_backward("ms_deform_attn_backward_binned_ml", value, spatial_shapes, level_start_index, sampling_loc, attn_weight, grad_output,
+                     level_hw, level_start, N, (int)S, M, D, Lq, L, P, ordered, grad_value, grad_sampling_loc, grad_attn_weight, workspace,
+                     workspace_bytes, slabs, (hipStream_t)stream);
+}
+
+// ---- the single-level entry (one map [N, H * W, M, 16]; round 6): its own argument checks, then the above with L = 1 ----------
+extern "C" size_t df3d_ms_deform_attn_backward_binned_workspace_bytes(int N, int M, int Lq, int LP, int H, int W) {
+  const int64_t level_hw[2] = {H, W};
+  return mb_layout(N, M, Lq, 1, LP, level_hw, false).bytes;
+}
+extern "C" size_t df3d_ms_deform_attn_backward_binned_slab_bytes(int N, int M, int D, int Lq, int LP, int H, int W) {
+  (void)D;
+  const int64_t level_hw[2] = {H, W};
+  return (size_t)N * mb_layout(N, M, Lq, 1, LP, level_hw, false).mw * MB_FOOT * MB_D * 4;
+}
+
+extern "C" int df3d_ms_deform_attn_backward_binned(const float *value, const int64_t *spatial_shapes, const int64_t *level_start_index,
+                                                   const float *sampling_loc, const float *attn_weight, const float *grad_output,
+                                                   int N, int M, int D, int Lq, int P, int H, int W, float *grad_value,
+                                                   float *grad_sampling_loc, float *grad_attn_weight, void *workspace,
+                                                   size_t workspace_bytes, float *slabs, void *stream) {
+  DF3D_CHECK_ARG(N >= 0 && M > 0 && D > 0 && Lq >= 0 && P > 0 && H > 0 && W > 0, "ms_deform_attn_backward_binned: bad sizes");
+  DF3D_CHECK_ARG(D == MB_D && P <= 16 && Lq < (1 << 28), "ms_deform_attn_backward_binned: head width %d / %d points not served", D, P);
+  const int tiles = cdiv(W, MB_T) * cdiv(H, MB_T);
+  DF3D_CHECK_ARG((size_t)tiles * M <= 7680, "ms_deform_attn_backward_binned: %d tiles x %d heads exceed the LDS budget", tiles, M);
+  DF3D_CHECK_ARG(N <= 65535 && (long long)Lq * M * P < (1LL << 31), "ms_deform_attn_backward_binned: %d maps x %d queries", N, Lq);
+  const int64_t level_hw[2] = {H, W}, level_start[1] = {0};
+  return mb_backward("ms_deform_attn_backward_binned", value, spatial_shapes, level_start_index, sampling_loc, attn_weight, grad_output,
+                     level_hw, level_start, N, H * W, M, D, Lq, 1, P, 0, grad_value, grad_sampling_loc, grad_attn_weight, workspace,
+                     workspace_bytes, slabs, (hipStream_t)stream);
 }

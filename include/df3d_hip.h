@@ -590,8 +590,10 @@ int df3d_ms_deform_attn_backward(const float *value, const int64_t *spatial_shap
                                  const float *sampling_loc, const float *attn_weight, const float *grad_output, int N,
                                  int S, int M, int D, int Lq, int L, int P, float *grad_value,
                                  float *grad_sampling_loc, float *grad_attn_weight, void *stream);
-/* round 6 -- the same gradients for ONE single-level map [N, H * W, M, 16] WITHOUT global atomics (csrc/msda.hip msda_bin_*): the
- * sampling points are counting-sorted by (map, 8 x 8 pixel tile, head); a wave per <= 512 points of a bin evaluates the col2im of
+/* round 6 -- the same gradients for ONE single-level map [N, H * W, M, 16] WITHOUT global atomics (csrc/msda.hip msda_bin_*).  This
+ * entry is a forwarder: after its own argument checks it runs the implementation of df3d_ms_deform_attn_backward_binned_ml below with
+ * level_hw = {H, W}, level_start = {0}, L = 1, ordered = 0 -- one set of kernels serves both -- and its two size functions return
+ * what the _ml ones return for that shape.  The sampling points are counting-sorted by (map, 8 x 8 pixel tile, head); a wave per <= 512 points of a bin evaluates the col2im of
  * its 9 x 9 pixel footprint as a matrix product on v_mfma_f32_16x16x4_f32 (bilinear weights x gradient rows, exact fp32 products)
  * and stores it as a slab; a gather kernel adds the slabs and the neighbours' halos up -- every element of grad_value is written
  * once (no zero fill).  Same contract as df3d_ms_deform_attn_backward (which the reference's
@@ -604,7 +606,7 @@ int df3d_ms_deform_attn_backward_binned(const float *value, const int64_t *spati
                                         const float *sampling_loc, const float *attn_weight, const float *grad_output, int N,
                                         int M, int D, int Lq, int P, int H, int W, float *grad_value, float *grad_sampling_loc,
                                         float *grad_attn_weight, void *workspace, size_t workspace_bytes, float *slabs, void *stream);
-/* ... and for L >= 1 levels and heads of 16 / 32 / 64 channels (csrc/msda.hip msda_binml_*): bins are (level, tile, head), a head
+/* ... and for L >= 1 levels and heads of 16 / 32 / 64 channels (the same kernels, csrc/msda.hip msda_bin_*): bins are (level, tile, head), a head
  * of D channels is D / 16 column slices of the same matrix product (one set of weights, D / 16 gradient rows), slabs are
  * [81][D].  level_hw [L][2] (H, W) and level_start [L] are HOST copies of spatial_shapes / level_start_index (the device
  * tensors are still read by the location / weight half).  Served (df3d_ms_deform_attn_backward_plan): D in {16, 32, 64},

@@ -209,3 +209,53 @@ def test_module_path_reaches_the_binned_kernels(dev):
         assert torch.equal(leaf.grad.cpu(), ref), name
     _assert_close([t.grad.cpu() for t in leaves], atomic, want)
     _assert_no_overflow()
+
+
+# (N, Lq, M, P, H, W), D = 16: a map of one tile row, a map smaller than a tile with 16 points, and two tile rows x three tile
+# columns whose last tile is one pixel wide and one pixel high
+FORWARDED = [(2, 64, 2, 2, 5, 19), (1, 40, 1, 16, 3, 2), (2, 300, 4, 4, 9, 17)]
+
+
+@pytest.mark.parametrize("N,Lq,M,P,H,W", FORWARDED, ids=["5x19", "3x2_P16", "9x17"])
+def test_single_level_entry_is_the_general_entry_with_one_level(dev, N, Lq, M, P, H, W):
+    """df3d_ms_deform_attn_backward_binned forwards to the implementation of ..._binned_ml with level_hw = {H, W}, level_start = {0},
+    L = 1, ordered = 0.  Both entries through ctypes on the same operands: the same workspace and slab sizes, the location / weight
+    gradients bit for bit (the same kernel), grad_value within the bound of a changed summation order, against both modes of the
+    general entry.  A forwarder that swaps H and W, mis-sets level_start or hands over a wrong point count fails here."""
+    from dualfusion import _lib, ops
+    lib, D = _lib.load(), 16
+    value, loc, aw, go, starts, S = _inputs(N, Lq, M, D, P, [(H, W)])
+    value, loc, aw, go = [t.to(dev) for t in (value, loc, aw, go)]
+    shp = torch.tensor([(H, W)], dtype=torch.long, device=dev)
+    ls = torch.zeros((1,), dtype=torch.long, device=dev)
+    hw, keep_hw = ops._i64_arr([H, W])
+    st, keep_st = ops._i64_arr([0])
+    nslab = int(lib.df3d_ms_deform_attn_backward_binned_slab_bytes(N, M, D, Lq, P, H, W))
+    assert nslab == int(lib.df3d_ms_deform_attn_backward_binned_ml_slab_bytes(N, M, D, Lq, 1, P, hw))
+    nws = int(lib.df3d_ms_deform_attn_backward_binned_workspace_bytes(N, M, Lq, P, H, W))
+    assert nws == int(lib.df3d_ms_deform_attn_backward_binned_ml_workspace_bytes(N, M, Lq, 1, P, hw, 0))
+
+    def call(entry, ordered):
+        nbytes = nws if not ordered else int(lib.df3d_ms_deform_attn_backward_binned_ml_workspace_bytes(N, M, Lq, 1, P, hw, 1))
+        ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+        slabs = torch.empty((nslab // 4,), dtype=torch.float32, device=dev)
+        gv, gl, ga = torch.empty_like(value), torch.empty_like(loc), torch.empty_like(aw)
+        head = [ops._ptr(t) for t in (value, shp, ls, loc, aw, go)]
+        tail = [ops._ptr(gv), ops._ptr(gl), ops._ptr(ga), ops._ptr(ws), nbytes, ops._ptr(slabs), ops._stream()]
+        if entry == "df3d_ms_deform_attn_backward_binned":
+            rc = lib.df3d_ms_deform_attn_backward_binned(*(head + [N, M, D, Lq, P, H, W] + tail))
+        else:
+            rc = lib.df3d_ms_deform_attn_backward_binned_ml(*(head + [hw, st, N, M, D, Lq, 1, P, ordered] + tail))
+        _lib.check(rc, entry)
+        return [t.cpu() for t in (gv, gl, ga)]
+
+    single = call("df3d_ms_deform_attn_backward_binned", 0)
+    for ordered in (0, 1):
+        general = call("df3d_ms_deform_attn_backward_binned_ml", ordered)
+        bound = 2e-5 * max(1.0, float(general[0].abs().max()))
+        diff = float((single[0] - general[0]).abs().max())
+        print("ordered = %d: |single - general| of grad_value %.3e (bound %.3e)" % (ordered, diff, bound))
+        assert diff <= bound, ordered                                              # (summation order of a bin's points)
+        assert torch.equal(single[1], general[1]) and torch.equal(single[2], general[2]), ordered
+    assert float(single[0].abs().max()) > 0.0
+    _assert_no_overflow()

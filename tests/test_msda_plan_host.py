@@ -115,6 +115,45 @@ def test_workspace_and_slab_bytes_are_positive_and_monotone():
         int(lib.df3d_ms_deform_attn_backward_binned_slab_bytes(3, 8, 16, 700, 4, 37, 61))
 
 
+# (N, M, Lq, P, H, W): an odd map, a one-tile map, a map smaller than a tile with 16 points, the TransFusion training shape
+SINGLE_LEVEL = [(3, 8, 700, 4, 37, 61), (2, 4, 300, 4, 8, 8), (1, 1, 40, 16, 3, 2), (24, 8, 10000, 4, 112, 200)]
+
+
+@pytest.mark.parametrize("N,M,Lq,P,H,W", SINGLE_LEVEL)
+def test_single_level_entry_asks_for_the_bytes_of_the_general_one(N, M, Lq, P, H, W):
+    """df3d_ms_deform_attn_backward_binned forwards to the implementation behind ..._binned_ml with L = 1, ordered = 0: its two
+    size functions return what the general ones return for that shape."""
+    lib = _lib()
+    one = ctypes.cast(_i64([H, W]), ctypes.c_void_p)
+    ws = int(lib.df3d_ms_deform_attn_backward_binned_workspace_bytes(N, M, Lq, P, H, W))
+    slab = int(lib.df3d_ms_deform_attn_backward_binned_slab_bytes(N, M, 16, Lq, P, H, W))
+    assert ws > 0 and ws == int(lib.df3d_ms_deform_attn_backward_binned_ml_workspace_bytes(N, M, Lq, 1, P, one, 0))
+    assert slab > 0 and slab == int(lib.df3d_ms_deform_attn_backward_binned_ml_slab_bytes(N, M, 16, Lq, 1, P, one))
+
+
+def _single_level_call(N=2, M=8, D=16, Lq=300, P=4, H=37, W=61):
+    """df3d_ms_deform_attn_backward_binned with null tensors: only what it decides before it touches the device."""
+    lib = _lib()
+    rc = int(lib.df3d_ms_deform_attn_backward_binned(*([None] * 6 + [N, M, D, Lq, P, H, W] + [None] * 4 + [0, None, None])))
+    return rc, lib.df3d_last_error().decode()
+
+
+@pytest.mark.parametrize("change,text", [
+    (dict(D=32), "ms_deform_attn_backward_binned: head width 32 / 4 points not served"),
+    (dict(P=17), "ms_deform_attn_backward_binned: head width 16 / 17 points not served"),
+    (dict(H=248, W=248), "ms_deform_attn_backward_binned: 961 tiles x 8 heads exceed the LDS budget"),   # 7688 bins > 7680
+    (dict(N=65536), "ms_deform_attn_backward_binned: 65536 maps x 300 queries"),
+    (dict(), "ms_deform_attn_backward_binned: null argument"),
+], ids=["D32", "P17", "bins7688", "N65536", "null"])
+def test_single_level_entry_keeps_its_own_refusals(change, text):
+    rc, err = _single_level_call(**change)
+    assert rc != 0 and err == text, (rc, err)
+
+
+def test_single_level_entry_returns_ok_for_no_maps():
+    assert _single_level_call(N=0)[0] == 0                                         # DF3D_OK, before any argument is read
+
+
 def test_python_plan_agrees_with_the_library_under_the_switch():
     import torch
     from dualfusion import _lib as L, ops
