@@ -31,6 +31,7 @@ struct LossArgs {
   float code_weights[DF3D_LOSS_MAX_CODES];
   int ntasks, batch, hw, max_objs, box_dim, ncodes, chunks;
   float weight;
+  int reg_by_slot;          // the box-code pointers of `task` hold one row per object SLOT (df3d_centerhead_loss_slots), not per pixel
 };
 
 __device__ __forceinline__ float clamped_sigmoid(float x) {
@@ -136,7 +137,7 @@ __global__ __launch_bounds__(256) void loss_finish_kernel(LossArgs a, const doub
       continue;                                        // same normaliser as the gradient kernels' task_positives()
     }
     const int b = s / a.max_objs;
-    const long long r = (long long)b * a.hw + ind;
+    long long r = (long long)b * a.hw + ind;
     const long long c = g.cat[s];
     if (m != 0.f && c >= 0 && c < k.num_classes) {
       float dpdx = 0.f;
@@ -148,6 +149,7 @@ __global__ __launch_bounds__(256) void loss_finish_kernel(LossArgs a, const doub
         unsafeAtomicAdd(const_cast<float *>(gk.hm) + r * gk.ld_hm + c, -inv_pos * ((q * q) / p - 2.f * q * lp) * dpdx);
     }
     npos += m;
+    if (!GRAD && a.reg_by_slot) r = s;                 // the heat map was read at the pixel; the box codes live at the slot
     // codes in the reference's concatenation order: reg(2) height(1) dim(3) [vel(2)] rot(2); without vel the
     // target keeps columns [0..5, -2, -1] of anno_box (center_head.py:229)
     float pred[DF3D_LOSS_MAX_CODES];
@@ -215,7 +217,8 @@ size_t df3d_centerhead_loss_workspace_bytes(int ntasks, int batch, int H, int W)
 
 static int centerhead_loss_impl(const df3d_head_task *tasks, const df3d_head_task *grad_tasks, const df3d_head_targets *targets,
                                 int ntasks, int batch, int H, int W, int max_objs, int box_dim, const float *code_weights,
-                                int ncodes, float weight, float *out, void *workspace, size_t workspace_bytes, void *stream) {
+                                int ncodes, float weight, float *out, void *workspace, size_t workspace_bytes, void *stream,
+                                bool reg_by_slot = false) {
   DF3D_CHECK_ARG(tasks && targets && out, "df3d_centerhead_loss: null argument");
   DF3D_CHECK_ARG(ntasks >= 1 && ntasks <= DF3D_MAX_HEAD_TASKS, "df3d_centerhead_loss: 1..%d tasks", DF3D_MAX_HEAD_TASKS);
   DF3D_CHECK_ARG(batch >= 1 && H >= 1 && W >= 1 && max_objs >= 0, "df3d_centerhead_loss: bad sizes");
@@ -246,6 +249,7 @@ static int centerhead_loss_impl(const df3d_head_task *tasks, const df3d_head_tas
   a.ntasks = ntasks, a.batch = batch, a.hw = H * W, a.max_objs = max_objs, a.box_dim = box_dim, a.ncodes = ncodes;
   a.chunks = cdiv((long long)batch * H * W, LOSS_CHUNK);
   a.weight = weight;
+  a.reg_by_slot = reg_by_slot && !grad_tasks;
   DF3D_CHECK_ARG(workspace && workspace_bytes >= df3d_centerhead_loss_workspace_bytes(ntasks, batch, H, W),
                  "df3d_centerhead_loss: workspace too small");
   double *partial = (double *)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
@@ -266,6 +270,13 @@ int df3d_centerhead_loss(const df3d_head_task *tasks, const df3d_head_targets *t
                          void *workspace, size_t workspace_bytes, void *stream) {
   return centerhead_loss_impl(tasks, nullptr, targets, ntasks, batch, H, W, max_objs, box_dim, code_weights, ncodes, weight, out,
                               workspace, workspace_bytes, stream);
+}
+
+int df3d_centerhead_loss_slots(const df3d_head_task *tasks, const df3d_head_targets *targets, int ntasks, int batch, int H,
+                               int W, int max_objs, int box_dim, const float *code_weights, int ncodes, float weight,
+                               float *out, void *workspace, size_t workspace_bytes, void *stream) {
+  return centerhead_loss_impl(tasks, nullptr, targets, ntasks, batch, H, W, max_objs, box_dim, code_weights, ncodes, weight, out,
+                              workspace, workspace_bytes, stream, true);
 }
 
 int df3d_centerhead_loss_grad(const df3d_head_task *tasks, const df3d_head_task *grad_tasks, const df3d_head_targets *targets,

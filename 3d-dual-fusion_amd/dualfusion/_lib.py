@@ -197,7 +197,13 @@ SIGNATURES = {
                                      c_void_p, c_void_p, c_size_t, c_void_p]),
     "df3d_centerhead_loss_grad": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_float,
                                      c_void_p, c_void_p, c_size_t, c_void_p]),
-    "df3d_heatmap_proposals_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "df3d_centerhead_loss_slots": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_float,
+                                           c_void_p, c_void_p, c_size_t, c_void_p]),
+    "df3d_head_regress_packed_bytes": (c_size_t, [c_int]),
+    "df3d_head_regress_pack": (c_int, [c_void_p, c_int, c_void_p, c_void_p]),
+    "df3d_head_regress_at": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                                     c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "df3d_heatmap_proposals_workspace_bytes":(c_size_t, [c_int, c_int, c_int, c_int]),
     "df3d_heatmap_proposals": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_uint, c_int, c_void_p, c_int,
                                        c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                        c_void_p, c_size_t, c_void_p]),

@@ -85,6 +85,12 @@ class ApiTimer(object):
                 extra = sum(int(arr[i].rows) for i in range(int(_ival(args[1]))))
             except Exception:                                   # noqa: BLE001
                 extra = None
+        elif name == "df3d_centerhead_loss_slots":              # heat-map classes live in the task structs
+            try:
+                arr = getattr(args[0], "_obj", args[0])
+                extra = sum(int(arr[i].num_classes) for i in range(int(_ival(args[2]))))
+            except Exception:                                   # noqa: BLE001
+                extra = None
         e0, e1 = self._event(), self._event()
         self.hip.hipEventRecord(e0, stream)
         rc = fn(*args)
@@ -160,7 +166,27 @@ def _rows(elems_in, elems_out, what):
     return (elems_in + elems_out) * 4, 0, "hbm", what
 
 
+def _regress_at(a):
+    """Bytes: one pass over the filter banks (147 KB of hi/lo fp16 + 9 KB of fp32 per bank), the slot lists and the output.
+    No flops: they scale with the LIVE slots (2 * (9 * 576 * 64 + 576 * 4) per slot and branch), which are device data -- a frame
+    has a few dozen per task, the cap of one object per slot would overstate them ~15x."""
+    B, H, W, T, M, NB = a[1], a[2], a[3], a[5], a[6], a[7]
+    banks = T * NB
+    by = banks * (147456 + 9 * 64 * 4 * 4) + T * B * M * (9 + 40)
+    return by, 0, "hbm", "regression branches at the live ones of %d object slots, %d tasks x %d branches (latency-bound)" % (B * M, T, NB)
+
+
+def _loss_slots(a, classes):
+    n, B, H, W, M, D = a[2:8]
+    if classes is None:
+        return None, None, "hbm", "detection losses"
+    return B * H * W * classes * 8 + n * B * M * (17 + D * 4 + 40), 20 * B * H * W * classes, "hbm", \
+        "focal loss over %d heat-map classes x %d pixels + L1 codes of %d slots" % (classes, B * H * W, n * B * M)
+
+
 MODELS = {
+    "df3d_head_regress_at": lambda a, x: _regress_at(a),
+    "df3d_centerhead_loss_slots": lambda a, x: _loss_slots(a, x),
     "df3d_hard_voxelize": lambda a, x: (20 * a[1] + a[6] * 0, 0, "hbm", "hash + scan + gather of %d points (bytes completed by the caller with M * 36)" % a[1]),
     "df3d_hard_voxelize_batched": lambda a, x: (20 * a[1], 0, "hbm", "hash + scan + gather of %d points (bytes completed by the caller with M * 36)" % a[1]),
     "df3d_ms_deform_attn_forward_f64": lambda a, x: _msda_f64(a, 5),

@@ -406,6 +406,139 @@ class CenterHead(nn.Module):
             rets[t][head] = v
         return rets
 
+    # ------------------------------------------------------------------ loss-only path: heat maps densely, box codes at the object centres
+    _SITE_CODES = (("reg", 2), ("height", 1), ("dim", 3), ("vel", 2), ("rot", 2))      # the loss kernel's code order
+
+    def _sites_plan(self, plan):
+        """Operands of the loss-only path, kept in (and dropped with) the row plan: the heat-map branches as a dense subset
+        (first convs 64 -> 64 per task as 128-column blocks, final convs into a packed [n, width] buffer) and the regression
+        branches as banks of `ops.head_regress_at`.  None when the head is not reg / height / dim / rot (/ vel) + hm."""
+        if "sites" in plan:
+            return plan["sites"]
+        plan["sites"] = None
+        names = [n for n, _ in self._SITE_CODES]
+        vel = all("vel" in task.heads for task in self.tasks)
+        want = {n: k for n, k in self._SITE_CODES if vel or n != "vel"}
+        for task in self.tasks:
+            if set(task.heads) != set(want) | {"hm"} or any(getattr(task, n)[3].out_channels != k for n, k in want.items()) \
+                    or any(getattr(task, n)[0].bias is None or getattr(task, n)[3].bias is None for n in task.heads):
+                return None
+        dev = self.shared_conv[0].weight.device
+        pad4 = lambda fc: torch.cat([fc[3].bias.detach().float(), torch.zeros(4 - fc[3].out_channels, device=dev)])
+        # heat maps: the dense subset
+        hms = [task.hm for task in self.tasks]
+        pair = 2 if len(hms) % 2 == 0 else 1
+        f1 = [self._filters(fc[0]) for fc in hms]
+        folds = [self._fold(fc[1]) for fc in hms]
+        cols, c0 = [], 0
+        for fc in hms:
+            cols.append((c0, fc[3].out_channels))
+            c0 += fc[3].out_channels
+        w4 = torch.stack([self._filters(fc[3], 4) for fc in hms]).contiguous()
+        sites = dict(hm_mid=torch.cat([_ops.conv_pack_weights(torch.cat(f1[i:i + pair], dim=2).contiguous())
+                                       for i in range(0, len(f1), pair)]), hm_pair=pair,
+                     hm_bias=torch.cat([fc[0].bias.detach().float() for fc in hms]).contiguous(),
+                     hm_scale=torch.cat([a for a, _ in folds]).contiguous(), hm_shift=torch.cat([b for _, b in folds]).contiguous(),
+                     hm_w4=w4, hm_b4=torch.stack([pad4(fc) for fc in hms]).contiguous(),
+                     hm_pk=_ops.head_final_pack(w4) if os.environ.get("DF3D_HEADFINAL", "mfma")[:1] != "v" else None,
+                     hm_cols=cols, hm_cols_dev=torch.tensor(cols, dtype=torch.int32, device=dev).contiguous(),
+                     hm_width=(c0 + 7) // 8 * 8, vel=vel, ncodes=10 if vel else 8)
+        # regression branches: banks (task, branch) in the loss kernel's code order
+        banks, rcols = [], []
+        for task in self.tasks:
+            c = 0
+            for n in names:
+                if n in want:
+                    banks.append(getattr(task, n))
+                    rcols.append((c, want[n]))
+                    c += want[n]
+        rfolds = [self._fold(fc[1]) for fc in banks]
+        sites.update(w1=_ops.head_regress_pack(torch.stack([self._filters(fc[0]) for fc in banks]).contiguous()),
+                     bias1=torch.stack([fc[0].bias.detach().float() for fc in banks]).contiguous(),
+                     scale1=torch.stack([a for a, _ in rfolds]).contiguous(), shift1=torch.stack([b for _, b in rfolds]).contiguous(),
+                     w2=torch.stack([self._filters(fc[3], 4) for fc in banks]).contiguous(),
+                     b2=torch.stack([pad4(fc) for fc in banks]).contiguous(),
+                     cols=torch.tensor(rcols, dtype=torch.int32, device=dev).contiguous())
+        plan["sites"] = sites
+        return sites
+
+    def loss_sites_wanted(self, example):
+        """The switch of the loss-only path (DF3D_HEAD_LOSS_SITES, default on; read per call) and what it needs of `example`:
+        device tensors hm / ind / mask / cat / anno_box for every task."""
+        if os.environ.get("DF3D_HEAD_LOSS_SITES", "1") == "0" or self.dataset not in ('waymo', 'nuscenes'):
+            return False
+        if not isinstance(example, dict):
+            return False
+        T = len(self.tasks)
+        for k in ("hm", "ind", "mask", "cat", "anno_box"):
+            v = example.get(k)
+            if not isinstance(v, (list, tuple)) or len(v) < T or not all(torch.is_tensor(a) and a.is_cuda for a in v[:T]):
+                return False
+        return True
+
+    def loss_sites_fit(self, x):
+        """True in the state in which `forward(x)` would run `forward_rows` with its `head_final_conv` branch (eval, no grad,
+        CUDA fp32 input, row kernels, two-part split rows) for a head whose branches the loss-only operands describe."""
+        if (self.training or torch.is_grad_enabled() or not x.is_cuda or x.dtype != torch.float32 or not self._row_kernels_fit(x)
+                or _ops.CONV_PRECISION in ("fp32", "split3") or os.environ.get("DF3D_HEAD_FINAL", "valu") != "valu"):
+            return False
+        plan = self._plan()
+        if plan["fin_w4"] is None:
+            return False
+        sites = self._sites_plan(plan)
+        return sites is not None and len(self.code_weights) == sites["ncodes"]
+
+    @torch.no_grad()
+    def forward_loss_dense(self, x):
+        """Dense part of the loss-only path (fixed shapes: library launches, allocations and views only): the shared conv as
+        in `forward_rows`, then ONLY the heat-map branches -- their first convs as one grouped launch, their final convs
+        through `head_final_conv`.  -> (heat maps [B*H*W, width] fp32 packed, split rows of the shared conv, (B, H, W))."""
+        from .necks import _rows_of
+        self.__dict__.pop("_packed_train", None)
+        plan = self._plan()
+        sites = self._sites_plan(plan)
+        B, _, H, W = x.shape
+        rows, split = _rows_of(x)
+        if (split is None or split.dtype != torch.uint8 or split.shape[1] != _ops.split_width(rows.shape[1])):
+            split = _ops.split_rows(rows.contiguous())
+        if (B, H, W) not in plan["nbr"]:
+            plan["nbr"][(B, H, W)] = _ops.conv2d_neighbors(B, H, W, 3, 3, 1, 1, False, x.device)[0]
+        nbr = plan["nbr"][(B, H, W)]
+        n = B * H * W
+        T = len(self.tasks)
+        _, s1 = _ops.conv_rows_split(split, 512, 0, plan["shared"], 64, 1, nbr, n, plan["s_bias"], plan["s_scale"],
+                                     plan["s_shift"], relu=True, want_out=False, want_split=True)
+        _, s2 = _ops.conv_rows_split(s1, 64, 0, sites["hm_mid"], 64 * sites["hm_pair"], T // sites["hm_pair"], nbr, n,
+                                     sites["hm_bias"], sites["hm_scale"], sites["hm_shift"], relu=True, want_out=False,
+                                     want_split=True)
+        out = _ops.head_final_conv(s2, B, H, W, sites["hm_w4"], sites["hm_b4"], sites["hm_cols_dev"], sites["hm_width"],
+                                   packed=sites["hm_pk"])
+        return out, s1, (B, H, W)
+
+    @torch.no_grad()
+    def loss_sites(self, example, dense):
+        """Sparse part of the loss-only path: the regression branches at the object centres (ONE launch, csrc/headloss.hip)
+        and the loss over the dense heat maps and those slot rows.  Same dict as `loss_device`."""
+        out_hm, s1, (B, H, W) = dense
+        sites = self._sites_plan(self._plan())
+        T = len(self.tasks)
+        pred = _ops.head_regress_at(s1, B, H, W, [example['ind'][t] for t in range(T)], [example['mask'][t] for t in range(T)],
+                                    sites["w1"], sites["bias1"], sites["scale1"], sites["shift1"], sites["w2"], sites["b2"],
+                                    sites["cols"])
+        ncodes = sites["ncodes"]
+        tasks = []
+        for t, (c0, k) in enumerate(sites["hm_cols"]):
+            p = pred[t]
+            d = dict(hm=out_hm[:, c0:c0 + k], reg=p[:, 0:2], height=p[:, 2:3], dim=p[:, 3:6], rot=p[:, ncodes - 2:ncodes])
+            if sites["vel"]:
+                d['vel'] = p[:, 6:8]
+            tasks.append(d)
+        targets = [dict(hm=example['hm'][t], ind=example['ind'][t], mask=example['mask'][t], cat=example['cat'][t],
+                        anno_box=example['anno_box'][t]) for t in range(T)]
+        out = _ops.centerhead_loss(tasks, targets, B, H, W, self.code_weights, self.weight, reg_by_slot=True)
+        return {'loss': out[:, 0], 'hm_loss': out[:, 1], 'loc_loss': out[:, 2], 'num_positive': out[:, 3],
+                'loc_loss_elem': out[:, 4:4 + ncodes]}
+
     def _final_pack(self, branches, dev):
         """Index tensors that gather the [G, 9, 64, 4] / [G, 4] operands of the final-conv kernel out of the concatenated
         (flattened) conv weights / biases of the branches (last element of the concatenation = 0 for the padding maps)."""

@@ -993,6 +993,66 @@ def head_final_conv(in_split, batch, H, W, weights, bias, out_cols, out_channels
     return out
 
 
+def head_regress_pack(filters):
+    """filters [banks, 9, 64, 64] fp32 (tap, cin, cout: the first convs of the head's regression branches) -> their
+    matrix-core operands for `head_regress_at` (csrc/headloss.hip)."""
+    lib = _lib.load()
+    _chk(filters, torch.float32, "filters")
+    if filters.dim() != 4 or tuple(filters.shape[1:]) != (9, 64, 64):
+        raise _lib.Df3dError("head_regress_pack: filters [banks,9,64,64] expected")
+    banks = filters.shape[0]
+    packed = torch.empty(int(lib.df3d_head_regress_packed_bytes(banks)), dtype=torch.uint8, device=filters.device)
+    _lib.check(lib.df3d_head_regress_pack(_ptr(filters), banks, _ptr(packed), _stream()), "df3d_head_regress_pack")
+    return packed
+
+
+def _ind_mask(ind, mask, batch):
+    """The (ind int64 [B, M], mask uint8 [B, M]) pair of one task as contiguous device tensors."""
+    if mask.dtype == torch.bool:
+        mask = mask.view(torch.uint8)
+    if ind.dtype != torch.int64 or mask.dtype != torch.uint8 or ind.dim() != 2 or ind.shape[0] != batch or mask.shape != ind.shape:
+        raise ValueError("targets ind (int64) / mask (uint8 or bool) must be [%d, max_objs]" % batch)
+    if not (ind.is_cuda and mask.is_cuda):
+        raise _lib.Df3dError("head_regress_at: targets must live on the GPU (no CPU fallback)")
+    return ind.contiguous(), mask.contiguous()
+
+
+def head_regress_at(s1_split, batch, H, W, inds, masks, packed, bias1, scale1, shift1, w2, b2, cols):
+    """The regression branches of a CenterPoint-style head at the object centres only (df3d_head_regress_at).
+    s1_split [B*H*W, 256] uint8: two-part split rows of the shared conv's 64 channels; inds / masks: per task [B, M] int64 /
+    uint8; per (task, branch) bank: packed (`head_regress_pack`), bias1 / scale1 / shift1 [banks, 64], w2 [banks, 9, 64, 4],
+    b2 [banks, 4], cols [banks, 2] int32 (first code column, codes).  -> pred [T, B*M, 10] fp32, zeros at dead slots."""
+    lib = _lib.load()
+    T = len(inds)
+    banks = w2.shape[0]
+    _chk(s1_split, torch.uint8, "s1_split")
+    _chk(packed, torch.uint8, "packed")
+    _chk(cols, torch.int32, "cols")
+    for t_, nm in ((bias1, "bias1"), (scale1, "scale1"), (shift1, "shift1"), (w2, "w2"), (b2, "b2")):
+        _chk(t_, torch.float32, nm)
+    n = int(batch) * int(H) * int(W)
+    if tuple(s1_split.shape) != (n, 256):
+        raise _lib.Df3dError("head_regress_at: split rows [%d, 256] expected for a %dx%dx%d map of 64 channels" % (n, batch, H, W))
+    if T < 1 or banks % T or packed.numel() != lib.df3d_head_regress_packed_bytes(banks) or tuple(w2.shape[1:]) != (9, 64, 4) \
+            or tuple(b2.shape) != (banks, 4) or tuple(cols.shape) != (banks, 2) \
+            or any(tuple(v.shape) != (banks, 64) for v in (bias1, scale1, shift1)):
+        raise _lib.Df3dError("head_regress_at: operands do not describe %d banks over %d tasks" % (banks, T))
+    tg = (_HeadTargets * T)()
+    keep = []
+    M = int(inds[0].shape[1])
+    for i in range(T):
+        ind, mask = _ind_mask(inds[i], masks[i], batch)
+        if ind.shape[1] != M:
+            raise ValueError("head_regress_at: tasks disagree about max_objs")
+        keep.append((ind, mask))
+        tg[i].ind, tg[i].mask = ind.data_ptr(), mask.data_ptr()
+    pred = torch.empty((T, int(batch) * M, LOSS_MAX_CODES), dtype=torch.float32, device=s1_split.device)
+    rc = lib.df3d_head_regress_at(_ptr(s1_split), int(batch), int(H), int(W), ctypes.byref(tg), T, M, banks // T, _ptr(packed),
+                                  _ptr(bias1), _ptr(scale1), _ptr(shift1), _ptr(w2), _ptr(b2), _ptr(cols), _ptr(pred), _stream())
+    _lib.check(rc, "df3d_head_regress_at")
+    return pred
+
+
 def sparse_to_dense(features, indices, batch, shape):
     lib = _lib.load()
     _chk(features, torch.float32, "features")
@@ -1159,9 +1219,11 @@ class _HeadTargets(ctypes.Structure):
 
 
 LOSS_FIELDS = 14        # DF3D_LOSS_FIELDS: loss, hm_loss, loc_loss, num_positive, loc_loss_elem[10]
+LOSS_MAX_CODES = 10     # DF3D_LOSS_MAX_CODES
 
 
-def _fill_head_tasks(arr, tasks, rows):
+def _fill_head_tasks(arr, tasks, rows, code_rows=None):
+    """code_rows: rows of the box-code maps where they differ from the heat map's (one row per object slot)."""
     for i, t in enumerate(tasks):
         for k in ("hm", "reg", "height", "dim", "rot", "vel"):
             v = t.get(k)
@@ -1169,26 +1231,31 @@ def _fill_head_tasks(arr, tasks, rows):
                 setattr(arr[i], k, None)
                 setattr(arr[i], "ld_" + k, 0)
                 continue
-            if v.dtype != torch.float32 or not v.is_cuda or v.dim() != 2 or (v.shape[1] > 1 and v.stride(1) != 1) or v.shape[0] != rows:
-                raise ValueError("head map '%s' must be a CUDA fp32 [B*H*W, C] view with unit column stride" % k)
+            want = rows if (k == "hm" or code_rows is None) else code_rows
+            if v.dtype != torch.float32 or not v.is_cuda or v.dim() != 2 or (v.shape[1] > 1 and v.stride(1) != 1) or v.shape[0] != want:
+                raise ValueError("head map '%s' must be a CUDA fp32 [%d, C] view with unit column stride" % (k, want))
             setattr(arr[i], k, v.data_ptr())
             setattr(arr[i], "ld_" + k, int(v.stride(0)))
         arr[i].num_classes = int(t["hm"].shape[1])
         arr[i].label_base = int(t.get("label_base", 0))
 
 
-def centerhead_loss(tasks, targets, batch, H, W, code_weights, weight, grad_tasks=None):
+def centerhead_loss(tasks, targets, batch, H, W, code_weights, weight, grad_tasks=None, reg_by_slot=False):
     """Detection losses of all tasks in two launches (csrc/loss.hip); with `grad_tasks` (zero-filled maps in the layout of
     `tasks`) also the gradient of the summed task losses with respect to every head map.  tasks: as for centerhead_predict; targets: list of
     dicts {'hm' [B, C, H, W] f32, 'ind' [B, M] i64, 'mask' [B, M] u8, 'cat' [B, M] i64, 'anno_box' [B, M, D] f32} on
-    the device.  Returns [T, LOSS_FIELDS] f32 on the device: loss, hm_loss, loc_loss, num_positive, loc_loss_elem[10]."""
+    the device.  Returns [T, LOSS_FIELDS] f32 on the device: loss, hm_loss, loc_loss, num_positive, loc_loss_elem[10].
+    reg_by_slot: the box-code maps ('reg', 'height', 'dim', 'rot', 'vel') are [B*M, C] views with one row per object slot
+    (what `head_regress_at` writes) instead of pixel rows (df3d_centerhead_loss_slots; values only)."""
     lib = _lib.load()
     n = len(tasks)
     dev = tasks[0]["hm"].device
     arr = (_HeadTask * n)()
-    _fill_head_tasks(arr, tasks, batch * H * W)
-    tg = (_HeadTargets * n)()
     M = int(targets[0]["ind"].shape[1])
+    if reg_by_slot and grad_tasks is not None:
+        raise ValueError("centerhead_loss: reg_by_slot serves the values only")
+    _fill_head_tasks(arr, tasks, batch * H * W, code_rows=batch * M if reg_by_slot else None)
+    tg = (_HeadTargets * n)()
     D = int(targets[0]["anno_box"].shape[2])
     keep = []
     for i, t in enumerate(targets):
@@ -1221,10 +1288,11 @@ def centerhead_loss(tasks, targets, batch, H, W, code_weights, weight, grad_task
                                            _ptr(out), _ptr(ws), nbytes, _stream())
         _lib.check(rc, "df3d_centerhead_loss_grad")
         return out
-    rc = lib.df3d_centerhead_loss(ctypes.byref(arr), ctypes.byref(tg), n, int(batch), int(H), int(W), M, D,
-                                  ctypes.cast(cw, ctypes.c_void_p), len(code_weights), float(weight), _ptr(out), _ptr(ws),
-                                  nbytes, _stream())
-    _lib.check(rc, "df3d_centerhead_loss")
+    entry = "df3d_centerhead_loss_slots" if reg_by_slot else "df3d_centerhead_loss"
+    rc = getattr(lib, entry)(ctypes.byref(arr), ctypes.byref(tg), n, int(batch), int(H), int(W), M, D,
+                             ctypes.cast(cw, ctypes.c_void_p), len(code_weights), float(weight), _ptr(out), _ptr(ws),
+                             nbytes, _stream())
+    _lib.check(rc, entry)
     return out
 
 

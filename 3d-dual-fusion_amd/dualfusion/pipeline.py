@@ -281,7 +281,21 @@ class CenterPointDetector(nn.Module):
         rows, (nb, _, h, w) = bev
         return self.bbox_head(self.hot_path.neck.forward_rows(rows, nb, h, w))
 
-    def _taped_tail(self, bev):
+    def _head_for_loss(self, x):
+        """The head's share of a loss-only step: ("sites", dense part of the loss-only path) where the head serves it
+        (`CenterHead.loss_sites_fit`), else ("maps", all head maps)."""
+        head = self.bbox_head
+        if head.loss_sites_fit(x):
+            return "sites", head.forward_loss_dense(x)
+        return "maps", head(x)
+
+    def _neck_head_for_loss(self, bev):
+        rows, (nb, _, h, w) = bev
+        return self._head_for_loss(self.hot_path.neck.forward_rows(rows, nb, h, w))
+
+    def _taped_tail(self, bev, mode="maps"):
+        """mode "maps": neck + head -> all head maps; "loss": neck + `_head_for_loss` (the sparse part of the loss-only path
+        reads the frame's target addresses and stays outside the tape).  ONE taped section serves both, the mode is in its key."""
         from . import ops as _ops
         from .necks import SplitRows
         from .tape import TapedSection
@@ -291,8 +305,9 @@ class CenterPointDetector(nn.Module):
         if tape is None:
             tape = self.__dict__["_tail_tape"] = TapedSection()
         key = (nb, c, h, w, tuple(inp.shape), inp.dtype, _ops.CONV_PRECISION, self._tail_versions(),
-               os.environ.get("DF3D_HEAD_FINAL"), os.environ.get("DF3D_HEADFINAL"))
-        return tape.run(key, lambda: self._neck_head(bev), [inp], _ops._stream())
+               os.environ.get("DF3D_HEAD_FINAL"), os.environ.get("DF3D_HEADFINAL"), mode, os.environ.get("DF3D_HEAD_LOSS_SITES"))
+        fn = (lambda: self._neck_head_for_loss(bev)) if mode == "loss" else (lambda: self._neck_head(bev))
+        return tape.run(key, fn, [inp], _ops._stream())
 
     @torch.no_grad()
     def simple_test(self, points_list, batch_dict=None, example=None):
@@ -329,6 +344,13 @@ class CenterPointDetector(nn.Module):
             x, _ = hp(points_list, batch_dict=batch_dict, example=example)
         finally:
             hp.defer_neck = False
+        head = self.bbox_head
+        if return_loss and hasattr(head, "loss_sites_wanted") and head.loss_sites_wanted(example):
+            # the loss reads the regression maps at the object centres only: heat maps densely, box codes at the centres
+            kind, val = self._taped_tail(x, "loss") if taped else self._head_for_loss(x)
+            if kind == "sites":
+                return head.loss_sites(example, val)
+            return head.loss_device(example, val)
         preds = self._taped_tail(x) if taped else self.bbox_head(x)
         if return_loss:
             return self.bbox_head.loss_device(example, preds)

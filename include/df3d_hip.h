@@ -464,6 +464,32 @@ int df3d_centerhead_loss(const df3d_head_task *tasks, const df3d_head_targets *t
 int df3d_centerhead_loss_grad(const df3d_head_task *tasks, const df3d_head_task *grad_tasks, const df3d_head_targets *targets,
                               int ntasks, int batch, int H, int W, int max_objs, int box_dim, const float *code_weights,
                               int ncodes, float weight, float *out, void *workspace, size_t workspace_bytes, void *stream);
+/* df3d_centerhead_loss whose box-code maps (reg / height / dim / rot / vel of every task) hold one row per object SLOT
+ * (row b * max_objs + m) instead of one per pixel: what df3d_head_regress_at writes.  The heat maps stay pixel rows and
+ * are read at ind as before; a slot whose ind lies outside the map is skipped as before.  Same values as
+ * df3d_centerhead_loss on full maps whose rows at ind equal the slot rows. */
+int df3d_centerhead_loss_slots(const df3d_head_task *tasks, const df3d_head_targets *targets, int ntasks, int batch, int H,
+                               int W, int max_objs, int box_dim, const float *code_weights, int ncodes, float weight,
+                               float *out, void *workspace, size_t workspace_bytes, void *stream);
+
+/* df3d_head_regress_at: the regression branches of a CenterPoint-style head (first conv 3x3 64 -> 64, folded BatchNorm,
+ * ReLU, final conv 3x3 64 -> k, zero padding in both) evaluated ONLY at the object centres the loss reads, in one launch
+ * (csrc/headloss.hip), instead of on every pixel.
+ *   s1_split: two-part split rows [batch*H*W, 64] of the shared conv's output (32 B per 8 channels: hi | lo);
+ *   targets[t].ind [batch, max_objs] i64 / .mask [batch, max_objs] u8 (the other members are not read);
+ *   per (task, branch) bank q = t * branches + b: w1_packed = df3d_head_regress_packed_bytes(tasks * branches) bytes
+ *   written by df3d_head_regress_pack from the first convs' filters [banks][9][64][64] fp32 (tap, cin, cout);
+ *   bias1 / scale1 / shift1 [banks][64] (mid = relu(scale * (bias + conv) + shift)); w2 [banks][9][64][4] fp32 and
+ *   b2 [banks][4] (tap-major, output maps padded to 4); cols [banks][2] i32 = (first code column, codes <= 4).
+ *   pred [tasks][batch*max_objs][DF3D_LOSS_MAX_CODES] f32: a live slot (mask != 0, 0 <= ind < H*W) receives the
+ *   branches' values at pixel ind of its sample in the columns `cols` names; every other slot, and every column no
+ *   branch of the task names, receives 0.  Fixed summation order, no atomics: two runs are bit-identical. */
+size_t df3d_head_regress_packed_bytes(int banks);
+int df3d_head_regress_pack(const float *w1, int banks, void *packed, void *stream);
+int df3d_head_regress_at(const void *s1_split, int batch, int H, int W, const df3d_head_targets *targets, int ntasks,
+                         int max_objs, int branches, const void *w1_packed, const float *bias1, const float *scale1,
+                         const float *shift1, const float *w2, const float *b2, const int32_t *cols, float *pred,
+                         void *stream);
 
 /* ------------------------------------------------------------------------------------
  * TransFusionHead (LiDAR-only branch), the index and decode steps.
