@@ -343,6 +343,25 @@ class VoxelWithPointProjection(nn.Module):
         return hit
 
     # ------------------------------------------------------------------ image-side projection
+    def _projection_weights(self):
+        """(w_ip, Wcat): the weight of input_proj's 1x1 conv [C, Cimg] and the matrix the image projection multiplies by --
+        with the image gate, w_ip + the gate's 1-channel image summary as an extra row (+ zero rows), kept in `_wcat`."""
+        w_full = self.pfat.input_proj[0][0].weight
+        w_ip = w_full[:, :, 0, 0]
+        if self.ifat_cfg is None:
+            return w_ip, w_ip
+        w3 = self.ifat.folded()[2]
+        # keyed on the parameters themselves: w3 is a view of the gate's reduced_dim3 weight (fp32), so its address survives
+        # an in-place update of that parameter and only the version counter tells
+        key = _ops.tensors_key((w_full, self.ifat.reduced_dim3.weight))
+        if self._wcat is None or self._wcat[0] != key:
+            # rows padded to a multiple of 16: hipBLASLt picks a 2x slower macro-tile for a 129-row operand
+            npad = (-(w_ip.shape[0] + 1)) % 16
+            # (`_wpack` below is keyed on THIS tensor's address and version: a rebuilt Wcat is allocated while the old one is
+            # still held by `_wcat`, so its address differs from the one `_wpack` remembers)
+            self._wcat = (key, torch.cat([w_ip, w3, w3.new_zeros((npad, w3.shape[1]))], 0))
+        return w_ip, self._wcat[1]
+
     def _image_projection(self, inp, img_conv_func=None, pixrow=None):
         """`both` [NI, C(+1+pad), H*W] = input_proj 1x1 conv of every camera map WITHOUT bias (+ the gate's 1-channel
         image summary as an extra row when the image gate is configured): one GEMM per map, written in place."""
@@ -351,18 +370,7 @@ class VoxelWithPointProjection(nn.Module):
             imgs = list(img_conv_func(torch.stack(imgs, 0)))
             inp['imgs'] = imgs
             inp['img_ptrs'] = self._pointer_table(imgs, imgs[0].device)
-        w_full = self.pfat.input_proj[0][0].weight
-        w_ip = w_full[:, :, 0, 0]
-        if self.ifat_cfg is not None:
-            w3 = self.ifat.folded()[2]
-            key = (w_full.data_ptr(), w_full._version, w3.data_ptr())
-            if self._wcat is None or self._wcat[0] != key:
-                # rows padded to a multiple of 16: hipBLASLt picks a 2x slower macro-tile for a 129-row operand
-                npad = (-(w_ip.shape[0] + 1)) % 16
-                self._wcat = (key, torch.cat([w_ip, w3, w3.new_zeros((npad, w3.shape[1]))], 0))
-            wcat = self._wcat[1]
-        else:
-            wcat = w_ip
+        w_ip, wcat = self._projection_weights()
         S_pix = inp['h'] * inp['w']
         if (img_conv_func is None and self.pfat.can_fold() and len(self.pfat.transformer.encoder.layers) == 2
                 and _ops.imgproj_supported(wcat.shape[0], imgs[0].shape[0], w_ip.shape[0])
@@ -499,17 +507,7 @@ class VoxelWithPointProjection(nn.Module):
         if not (self.pfat.can_fold() and len(self.pfat.transformer.encoder.layers) == 2
                 and os.environ.get("DF3D_IMGPROJ", "1") == "1"):
             return None
-        w_full = self.pfat.input_proj[0][0].weight
-        w_ip = w_full[:, :, 0, 0]
-        if self.ifat_cfg is not None:
-            w3 = self.ifat.folded()[2]
-            key = (w_full.data_ptr(), w_full._version, w3.data_ptr())
-            if self._wcat is None or self._wcat[0] != key:
-                npad = (-(w_ip.shape[0] + 1)) % 16
-                self._wcat = (key, torch.cat([w_ip, w3, w3.new_zeros((npad, w3.shape[1]))], 0))
-            wcat = self._wcat[1]
-        else:
-            wcat = w_ip
+        w_ip, wcat = self._projection_weights()
         if not _ops.imgproj_supported(wcat.shape[0], inp['imgs'][0].shape[0], w_ip.shape[0]):
             return None
         key = (wcat.data_ptr(), wcat._version)

@@ -218,12 +218,13 @@ class CenterHead(nn.Module):
         return super(CenterHead, self).train(mode)
 
     def _state_tensors(self):
-        """Every parameter and buffer of the head, collected ONCE (the module tree walk of `parameters()` cost ~1 ms of host
-        time per step); the objects stay valid across load_state_dict / optimizer steps, `train()` drops the list."""
-        ts = self.__dict__.get("_plan_tensors")
-        if ts is None:
-            ts = self.__dict__["_plan_tensors"] = list(self.parameters()) + list(self.buffers())
-        return ts
+        """Every parameter and buffer of the head.  Their (dict, name) slots are collected ONCE (the module tree walk of
+        `parameters()` cost ~1 ms of host time per step) and read per call: a list of the tensors themselves would go on
+        watching the old buffer objects after `.double().float()` replaced them.  `train()` drops the slots."""
+        slots = self.__dict__.get("_plan_tensors")
+        if slots is None:
+            slots = self.__dict__["_plan_tensors"] = _ops.state_slots(self)
+        return _ops.slot_tensors(slots)
 
     def _row_kernels_fit(self, x):
         hit = self.__dict__.get("_row_fit")
@@ -264,7 +265,7 @@ class CenterHead(nn.Module):
         return scale, bn.bias.float() - bn.running_mean.float() * scale
 
     def _plan(self):
-        key = tuple((p.data_ptr(), p._version) for p in self._state_tensors()) + (_ops.split_parts(),)
+        key = _ops.tensors_key(self._state_tensors()) + (_ops.split_parts(),)
         plan = self.__dict__.get("_row_plan")
         if plan is not None and plan["key"] == key:
             return plan
@@ -316,7 +317,7 @@ class CenterHead(nn.Module):
         channels; 64 -> 128 per group = two branches) into a [pixels, 64 * branches] buffer; the final convs as ONE grouped
         launch, each group reading its branch's 64 columns of that buffer in place (64 -> classes padded to 16)."""
         from .necks import _rows_of
-        key = tuple((p.data_ptr(), p._version) for p in self._state_tensors())
+        key = _ops.tensors_key(self._state_tensors())
         plan = self.__dict__.get("_row_plan_fp32")
         if plan is None or plan["key"] != key:
             sc, sbn = self.shared_conv[0], self.shared_conv[1]

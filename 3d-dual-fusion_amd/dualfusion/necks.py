@@ -90,8 +90,12 @@ class _Layer(object):
 
     def prepare(self, pad):
         c = self.conv
-        key = (c.weight.data_ptr(), c.weight._version, self.bn.running_var._version, self.bn.weight._version,
-               _ops.CONV_PRECISION)
+        bn = self.bn
+        # every tensor read below: the BatchNorm bias and the running mean are baked into `shift` (an edit of either alone
+        # must rebuild); the conv bias is kept as a view of an fp32 parameter and follows in-place edits by itself, but
+        # `.float()` copies for any other dtype, so it is part of the key as well
+        key = (_ops.tensors_key((c.weight, c.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var)),
+               _ops.CONV_PRECISION, bn.eps)
         if key == self._key:
             return
         w = c.weight.detach().float()

@@ -741,6 +741,25 @@ class ConvFilters(object):
         self.packed = _pack_filters(self.kind, filters) if self.kind != "fp32" else None
 
 
+def tensors_key(tensors):
+    """The cache key of something derived from `tensors` (None allowed): address, version counter, device and dtype of each.
+    Host-side only.  In-place updates under no_grad (optimizers, load_state_dict, `bn.bias.add_()`) move the version,
+    re-seated or converted storage moves the address; writes through `.data` move neither and are not tracked."""
+    return tuple(None if t is None else (t.data_ptr(), t._version, t.device, t.dtype) for t in tensors)
+
+
+def state_slots(module):
+    """[(dict, name)] of every parameter and buffer of the module tree, to be collected ONCE (the tree walk is host time per
+    step) and read with `slot_tensors` per call: the modules' own `_parameters` / `_buffers` dicts always hold the live
+    objects, also after `.double().float()` or an assignment replaced a buffer -- a list of the tensors themselves would go
+    on watching the dead ones."""
+    return [(d, k) for m in module.modules() for d in (m._parameters, m._buffers) for k in d]
+
+
+def slot_tensors(slots):
+    return [d.get(k) for d, k in slots]
+
+
 def conv_filters(owner, weight, kvol, cin, cout):
     """The ConvFilters of `weight` ([..., cin, cout] in any kernel shape) for the current mode, kept in `owner.__dict__` and
     rebuilt when the parameter (address, version, device) or the kind changes; one slot per kind."""

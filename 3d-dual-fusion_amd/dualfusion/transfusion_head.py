@@ -489,10 +489,11 @@ class TransFusionHead(nn.Module):
         return scale.contiguous(), (bn.bias.detach().float() - bn.running_mean.float() * scale).contiguous()
 
     def _plan(self):
-        params = self.__dict__.get("_plan_tensors")
-        if params is None:                            # collected once (train() drops it): parameters() walks the module tree
-            params = self.__dict__["_plan_tensors"] = [p for p in self.parameters()] + [b for b in self.buffers()]
-        key = tuple((p.data_ptr(), p._version) for p in params)
+        slots = self.__dict__.get("_plan_tensors")
+        if slots is None:                             # collected once (train() drops it): parameters() walks the module tree;
+            slots = self.__dict__["_plan_tensors"] = _ops.state_slots(self)   # slots, not tensors: buffers can be replaced
+        # the packed filters are those of the split format in force (two parts, three in the "split3" mode)
+        key = _ops.tensors_key(_ops.slot_tensors(slots)) + (_ops.split_parts(),)
         plan = self.__dict__.get("_row_plan")
         if plan is not None and plan["key"] == key:
             return plan
