@@ -304,6 +304,18 @@ SIGNATURES = {
                                     c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
     "df3d_fusion_writeback": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
                                       c_void_p, c_void_p]),
+    "df3d_voxel_query": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_longlong, c_void_p, c_void_p, c_longlong,
+                                 c_void_p, c_float, c_int, c_void_p, c_void_p]),
+    "df3d_voxel_query_dense": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_longlong, c_void_p, c_void_p, c_longlong,
+                                       c_void_p, c_float, c_int, c_void_p, c_void_p]),
+    "df3d_group_points_stack": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_longlong, c_int, c_int, c_longlong,
+                                        c_void_p, c_void_p]),
+    "df3d_group_points_stack_grad_workspace_bytes": (c_size_t, [c_longlong, c_int, c_void_p]),
+    "df3d_group_points_stack_grad": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_longlong, c_int, c_longlong,
+                                             c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "df3d_voxel_pool_fused": (c_int, [c_void_p, c_void_p, c_longlong, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
+                                      c_void_p, c_longlong, c_void_p, c_float, c_int, c_void_p, c_int, c_void_p, c_void_p,
+                                      c_void_p, c_void_p]),
 }
 
 _lib = None

@@ -9,6 +9,7 @@ names, argument order, caller-allocated outputs and error behaviour as the pybin
   group_points_ext              TF/mmdet3d/ops/group_points/src/group_points.cpp:59-62
   gather_points_ext             TF/mmdet3d/ops/gather_points/src/gather_points.cpp:54-59
   iou3d_cuda                    TF/mmdet3d/ops/iou3d/src/iou3d.cpp (boxes_overlap_bev_gpu / boxes_iou_bev_gpu / nms_gpu / nms_normal_gpu)
+  pointnet2_stack_cuda          VR/pcdet/ops/pointnet2/pointnet2_stack/src/pointnet2_api.cpp:14,19-20 (voxel query, stack grouping)
 
 `install()` puts them into `sys.modules` under the import paths the reference's Python wrappers use, so that
 `from . import sparse_conv_ext` (TF/mmdet3d/ops/spconv/ops.py:17), `from .voxel_layer import hard_voxelize`
@@ -20,6 +21,8 @@ import sys
 
 NAMES = ("sparse_conv_ext", "voxel_layer", "MultiScaleDeformableAttention", "furthest_point_sample_ext", "ball_query_ext",
          "group_points_ext", "gather_points_ext", "iou3d_cuda")
+# the shims of the pcdet tree (NAMES is the mmdet3d / Det3D set)
+PCDET_NAMES = ("pointnet2_stack_cuda",)
 
 # import paths of the reference's wrappers (module attribute of a package, or a top-level module)
 ALIASES = {
@@ -32,11 +35,12 @@ ALIASES = {
     "group_points_ext": ("mmdet3d.ops.group_points.group_points_ext", "det3d.ops.group_points.group_points_ext"),
     "gather_points_ext": ("mmdet3d.ops.gather_points.gather_points_ext", "det3d.ops.gather_points.gather_points_ext"),
     "iou3d_cuda": ("mmdet3d.ops.iou3d.iou3d_cuda",),
+    "pointnet2_stack_cuda": ("pcdet.ops.pointnet2.pointnet2_stack.pointnet2_stack_cuda",),
 }
 
 
 def load(name):
-    if name not in NAMES:
+    if name not in NAMES + PCDET_NAMES:
         raise KeyError(name)
     return importlib.import_module("." + name, __name__)
 

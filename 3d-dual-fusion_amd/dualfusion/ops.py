@@ -3193,3 +3193,166 @@ def linear_rows(x, lin, min_rows=16384):
     out, _ = sparse_conv_split(split_rows(x2), packed_linear(lin.weight), identity_table(rows, x.device), rows, cin, cout,
                                bias=lin.bias.detach() if lin.bias is not None else None, emit_split=False)
     return out.view(*x.shape[:-1], cout)
+
+
+# ------------------------------------------------------------------------- RoI grid pooling (csrc/roipool.hip)
+VOXEL_QUERY_MAX_XRANGE = 15          # csrc/roipool.hip: VQ_MAX_XRANGE
+VOXEL_POOL_MAX_NSAMPLE = 16          # VP_MAX_NSAMPLE
+_POOL_METHODS = {"max_pool": 0, "avg_pool": 1}
+
+
+def _query_args(xyz, new_xyz, new_coords, max_range):
+    _chk(xyz, torch.float32, "xyz")
+    _chk(new_xyz, torch.float32, "new_xyz")
+    _chk(new_coords, torch.int32, "new_coords")
+    if xyz.dim() != 2 or xyz.shape[1] != 3 or new_xyz.dim() != 2 or new_xyz.shape[1] != 3:
+        raise _lib.Df3dError("xyz and new_xyz must be [*, 3]")
+    if tuple(new_coords.shape) != (new_xyz.shape[0], 4):
+        raise _lib.Df3dError("new_coords must be [M, 4] (batch, z, y, x) with one row per row of new_xyz")
+    if len(max_range) != 3:
+        raise _lib.Df3dError("the query range is (z, y, x)")
+    return _lib.int3(max_range)
+
+
+def voxel_query(max_range, radius, nsample, xyz, new_xyz, new_coords, voxel2point):
+    """The raw voxel query (voxel_query_gpu.cu:10-89): idx int32 [M, nsample] of global rows of `xyz`, idx[m, 0] = -1
+    for an empty ball.  `voxel2point`: a GridDirectory over the voxels whose centres `xyz` holds (row i of the indices
+    it was built from = row i of xyz), or the reference's dense int32 [B, Z, Y, X] tensor.  max_range = (z, y, x)."""
+    rng_p, keep = _query_args(xyz, new_xyz, new_coords, max_range)
+    M = new_xyz.shape[0]
+    idx = torch.empty((M, int(nsample)), dtype=torch.int32, device=xyz.device)
+    lib = _lib.load()
+    if isinstance(voxel2point, GridDirectory):
+        g = voxel2point
+        shp_p, keep2 = _lib.int3(g.shape)
+        rc = lib.df3d_voxel_query(_ptr(g.blob), _ptr(g.perm), g.batch, shp_p, _ptr(xyz), xyz.shape[0], _ptr(new_xyz),
+                                  _ptr(new_coords), M, rng_p, float(radius), int(nsample), _ptr(idx), _stream())
+        _lib.check(rc, "df3d_voxel_query")
+    else:
+        _chk(voxel2point, torch.int32, "voxel2point_indices")
+        if voxel2point.dim() != 4:
+            raise _lib.Df3dError("voxel2point_indices must be [B, Z, Y, X]")
+        shp_p, keep2 = _lib.int3(voxel2point.shape[1:])
+        rc = lib.df3d_voxel_query_dense(_ptr(voxel2point), voxel2point.shape[0], shp_p, _ptr(xyz), xyz.shape[0],
+                                        _ptr(new_xyz), _ptr(new_coords), M, rng_p, float(radius), int(nsample), _ptr(idx),
+                                        _stream())
+        _lib.check(rc, "df3d_voxel_query_dense")
+    return idx
+
+
+def _stack_args(features, features_batch_cnt, idx, idx_batch_cnt):
+    _chk(features, torch.float32, "features")
+    _chk(idx, torch.int32, "idx")
+    _chk(features_batch_cnt, torch.int32, "features_batch_cnt")
+    _chk(idx_batch_cnt, torch.int32, "idx_batch_cnt")
+    if features.dim() != 2 or idx.dim() != 2:
+        raise _lib.Df3dError("features must be [N, C] and idx [M, nsample]")
+    if features_batch_cnt.dim() != 1 or features_batch_cnt.shape != idx_batch_cnt.shape or features_batch_cnt.shape[0] < 1:
+        raise _lib.Df3dError("features_batch_cnt and idx_batch_cnt must both be [B]")
+
+
+def _group_points_stack(features, features_batch_cnt, idx, idx_batch_cnt):
+    N, C = features.shape
+    M, nsample = idx.shape
+    out = torch.empty((M, C, nsample), dtype=torch.float32, device=features.device)
+    rc = _lib.load().df3d_group_points_stack(_ptr(features), _ptr(features_batch_cnt), _ptr(idx), _ptr(idx_batch_cnt),
+                                             features_batch_cnt.shape[0], M, C, nsample, N, _ptr(out), _stream())
+    _lib.check(rc, "df3d_group_points_stack")
+    return out
+
+
+def group_points_stack_backward(grad_out, idx, idx_batch_cnt, features_batch_cnt, N, out=None):
+    """grad_features [N, C] of the stack grouping: every row the ordered sum of its contributions (no float atomics, the
+    same bits on every run).  `out` (optional, [N, C]) is overwritten."""
+    grad_out = _chk(grad_out, torch.float32, "grad_out")
+    M, C, nsample = grad_out.shape
+    if tuple(idx.shape) != (M, nsample):
+        raise _lib.Df3dError("idx must be [M, nsample] like grad_out [M, C, nsample]")
+    if out is None:
+        out = torch.empty((N, C), dtype=torch.float32, device=grad_out.device)
+    elif tuple(out.shape) != (N, C):
+        raise _lib.Df3dError("grad_features must be [N, C]")
+    _chk(out, torch.float32, "grad_features")
+    lib = _lib.load()
+    stream = _stream()
+    ws, wsb = None, 0
+    if M * nsample > 0:
+        wsb = lib.df3d_group_points_stack_grad_workspace_bytes(M, nsample, stream)
+        if wsb == 0:
+            raise _lib.Df3dError("group_points_stack backward: no workspace size for M * nsample = %d (limit 2^31 - 1)"
+                                 % (M * nsample))
+        ws = torch.empty((wsb,), dtype=torch.uint8, device=grad_out.device)
+    rc = lib.df3d_group_points_stack_grad(_ptr(grad_out), _ptr(idx), _ptr(idx_batch_cnt), _ptr(features_batch_cnt),
+                                          features_batch_cnt.shape[0], M, C, N, nsample, _ptr(out), _ptr(ws), wsb, stream)
+    _lib.check(rc, "df3d_group_points_stack_grad")
+    return out
+
+
+class _GroupPointsStack(torch.autograd.Function):
+    """GroupingOperation of pointnet2_stack (pointnet2_utils.py): the gradient goes to `features` alone."""
+
+    @staticmethod
+    def forward(ctx, features, features_batch_cnt, idx, idx_batch_cnt):
+        ctx.save_for_backward(idx, idx_batch_cnt, features_batch_cnt)
+        ctx.n = features.shape[0]
+        return _group_points_stack(features, features_batch_cnt, idx, idx_batch_cnt)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad):
+        idx, idx_batch_cnt, features_batch_cnt = ctx.saved_tensors
+        return group_points_stack_backward(grad.contiguous(), idx, idx_batch_cnt, features_batch_cnt, ctx.n), None, None, None
+
+
+def group_points_stack(features, features_batch_cnt, idx, idx_batch_cnt):
+    """features [N1 + N2 .., C], idx int32 [M1 + M2 .., nsample] local to its frame, counts int32 [B] ->
+    [M, C, nsample] (group_points_gpu.cu:71-102); differentiable in `features`."""
+    _stack_args(features, features_batch_cnt, idx, idx_batch_cnt)
+    if torch.is_grad_enabled() and features.requires_grad:
+        return _GroupPointsStack.apply(features, features_batch_cnt, idx, idx_batch_cnt)
+    return _group_points_stack(features, features_batch_cnt, idx, idx_batch_cnt)
+
+
+def voxel_pool_fused_supported(channels, nsample, max_range, pool_method="max_pool", voxel2point=None):
+    """Shapes `voxel_pool_fused` serves; everything else takes the composed path (query + grouping + torch layers)."""
+    return (int(channels) in (16, 32, 64) and 1 <= int(nsample) <= VOXEL_POOL_MAX_NSAMPLE and len(max_range) == 3
+            and 0 <= int(max_range[2]) <= VOXEL_QUERY_MAX_XRANGE and 0 <= int(max_range[0]) <= 1024
+            and 0 <= int(max_range[1]) <= 1024 and pool_method in _POOL_METHODS
+            and (voxel2point is None or isinstance(voxel2point, GridDirectory)))
+
+
+def voxel_pool_fused(rows_in, xyz, grid, new_xyz, new_coords, max_range, radius, nsample, w_pos, pool_method="max_pool",
+                     want_idx=False):
+    """One level, one scale of NeighborVoxelSAModuleMSG in eval mode: query, gather, position term, ReLU and pool in one
+    kernel.  rows_in [N, C] = the features after mlps_in; w_pos [C, 4] = (conv weight * BN scale | BN shift) of mlps_pos.
+    Returns pooled [M, C] (before mlps_out), and with want_idx also (idx int32 [M, nsample], empty bool [M])."""
+    if pool_method not in _POOL_METHODS:
+        raise _lib.Df3dError("pool method %r: must be 'max_pool' or 'avg_pool'" % (pool_method,))
+    if not isinstance(grid, GridDirectory):
+        raise _lib.Df3dError("voxel_pool_fused needs the level's GridDirectory")
+    rng_p, keep = _query_args(xyz, new_xyz, new_coords, max_range)
+    _chk(rows_in, torch.float32, "rows_in")
+    _chk(w_pos, torch.float32, "w_pos")
+    if rows_in.dim() != 2 or rows_in.shape[0] != xyz.shape[0]:
+        raise _lib.Df3dError("rows_in must be [N, C] with one row per row of xyz")
+    C = rows_in.shape[1]
+    if tuple(w_pos.shape) != (C, 4):
+        raise _lib.Df3dError("w_pos must be [C, 4]")
+    if not voxel_pool_fused_supported(C, nsample, max_range, pool_method):
+        raise _lib.Df3dError("voxel_pool_fused does not serve C = %d, nsample = %d, range %s (C in 16/32/64, nsample <= %d, "
+                             "x range <= %d): use the composed path" % (C, nsample, list(max_range), VOXEL_POOL_MAX_NSAMPLE,
+                                                                        VOXEL_QUERY_MAX_XRANGE))
+    M = new_xyz.shape[0]
+    dev = xyz.device
+    pooled = torch.empty((M, C), dtype=torch.float32, device=dev)
+    idx = torch.empty((M, int(nsample)), dtype=torch.int32, device=dev) if want_idx else None
+    empty = torch.empty((M,), dtype=torch.uint8, device=dev) if want_idx else None
+    shp_p, keep2 = _lib.int3(grid.shape)
+    rc = _lib.load().df3d_voxel_pool_fused(_ptr(rows_in), _ptr(xyz), xyz.shape[0], C, _ptr(grid.blob), _ptr(grid.perm),
+                                           grid.batch, shp_p, _ptr(new_xyz), _ptr(new_coords), M, rng_p, float(radius),
+                                           int(nsample), _ptr(w_pos), _POOL_METHODS[pool_method], _ptr(pooled), _ptr(idx),
+                                           _ptr(empty), _stream())
+    _lib.check(rc, "df3d_voxel_pool_fused")
+    if want_idx:
+        return pooled, idx, empty.bool()
+    return pooled

@@ -82,13 +82,15 @@ MM_NECKS = Registry("mmdet neck")
 MM_HEADS = Registry("mmdet head")              # TransFusionHead (mmdet3d HEADS is mmdet's HEADS registry)
 MM_DETECTORS = Registry("mmdet detector")      # TransFusionDetector (mmdet3d registers detectors into mmdet's DETECTORS)
 BACKBONES_3D = Registry("pcdet backbone_3d")   # pcdet uses a plain dict `__all__`; same lookup by NAME
+ROI_HEADS = Registry("pcdet roi_head")         # pcdet.models.roi_heads.__all__ (VoxelRCNNHead)
 
 
 def late_register():
     """Register our classes into the real frameworks' registries when those are importable, so the
     reference configs resolve `type=` / `NAME:` strings to the MI355X modules unchanged."""
     import importlib
-    for m in ("spconv", "voxel", "backbones", "fusion", "fusion_tf", "necks", "heads", "transfusion_head", "transfusion"):
+    for m in ("spconv", "voxel", "backbones", "fusion", "fusion_tf", "necks", "heads", "transfusion_head", "transfusion",
+              "roi_heads"):
         importlib.import_module("." + m, __package__)          # every module that registers classes (some import lazily)
     done = []
     try:
@@ -133,6 +135,13 @@ def late_register():
         for k, v in BACKBONES_3D.module_dict.items():
             p3.__all__[k] = v
         done.append("pcdet")
+    except Exception:
+        pass
+    try:
+        import pcdet.models.roi_heads as pr
+        for k, v in ROI_HEADS.module_dict.items():
+            pr.__all__[k] = v
+        done.append("pcdet.roi_heads")
     except Exception:
         pass
     return done

@@ -1367,6 +1367,51 @@ int df3d_dynamic_scatter_max_backward(const void *feats, const void *voxel_feats
                                       long long num_points, int num_voxels, int channels, const int32_t *point2voxel_map,
                                       int32_t *arg_workspace, void *grad_feats, void *stream);
 
+/* ------------------------------------------------------------------------------------
+ * Voxel-RCNN RoI grid pooling (csrc/roipool.hip).  Replaces voxel_query_wrapper, group_points_wrapper and
+ * group_points_grad_wrapper of VR/pcdet/ops/pointnet2/pointnet2_stack (src/pointnet2_api.cpp) and, in eval mode, the
+ * per-scale body of NeighborVoxelSAModuleMSG.forward (voxel_pool_modules.py:84-122).
+ *
+ * Voxel query (src/voxel_query_gpu.cu:10-89): per centre m with voxel coordinate new_coords [M,4] (b,z,y,x) the cells
+ * (z+dz, y+dy, x+dx), |d| <= range (host int[3], z,y,x), are scanned dz outer, dy, dx inner; cells outside the grid are
+ * skipped one by one; a voxel is accepted when !(dist2 > radius^2), dist2 = ((dx*dx) + (dy*dy)) + (dz*dz) in float32 with
+ * every operation rounded separately.  idx [M,nsample] i32: the first min(count, nsample) hits in scan order, the
+ * remaining slots repeat the first hit; an empty ball gives idx[m,0] = -1 and zeros after it.  Indices are global rows
+ * of xyz [n_rows,3].  df3d_voxel_query looks the cells up in an occupancy directory (grid, perm as df3d_grid_build made
+ * them over [batch, shape]); df3d_voxel_query_dense in the reference's point_indices [B,Z,Y,X] i32 (-1 = empty).
+ * Limits (refused with an error): range x <= 15, range z, y <= 1024, nsample <= 4096.
+ *
+ * Stack grouping (src/group_points_gpu.cu:71-102 / :15-45): features [N,C], idx [M,nsample] i32 local to its frame,
+ * per-frame counts [B] i32 on the device; out [M,C,nsample].  An index outside its frame reads as 0 / receives nothing.
+ * The backward writes ALL of grad_features [N,C]: each row is the sum of its contributions in ascending (m, s) order
+ * (sorted by target row, no float atomics: the same bits on every run).  float32 only, M * nsample < 2^31.
+ *
+ * Fused pool, one level and one scale: rows_in [n_rows,C] (the level's features after mlps_in), w_pos [C,4] = the
+ * weight of mlps_pos' conv times its BatchNorm scale (x,y,z) and the BatchNorm shift; pooled [M,C] = max (pool_method 0)
+ * or mean (1) over the nsample slots of relu(rows_in[idx] + w_pos . (xyz[idx] - new_xyz, 1)), slots past the hit count
+ * repeating the first hit; an empty ball gives relu(shift).  idx [M,nsample] i32 and empty [M] u8 are optional outputs.
+ * C in {16, 32, 64}, nsample <= 16, query limits as above.  Nothing of size M * C * nsample is written.
+ * ---------------------------------------------------------------------------------- */
+int df3d_voxel_query(const void *grid, const int32_t *perm, int batch, const int *shape_host, const float *xyz,
+                     long long n_rows, const float *new_xyz, const int32_t *new_coords, long long M,
+                     const int *range_host, float radius, int nsample, int32_t *idx, void *stream);
+int df3d_voxel_query_dense(const int32_t *point_indices, int batch, const int *shape_host, const float *xyz,
+                           long long n_rows, const float *new_xyz, const int32_t *new_coords, long long M,
+                           const int *range_host, float radius, int nsample, int32_t *idx, void *stream);
+int df3d_group_points_stack(const float *features, const int32_t *features_batch_cnt, const int32_t *idx,
+                            const int32_t *idx_batch_cnt, int B, long long M, int C, int nsample, long long N,
+                            float *out, void *stream);
+size_t df3d_group_points_stack_grad_workspace_bytes(long long M, int nsample, void *stream);
+int df3d_group_points_stack_grad(const float *grad_out, const int32_t *idx, const int32_t *idx_batch_cnt,
+                                 const int32_t *features_batch_cnt, int B, long long M, int C, long long N,
+                                 int nsample, float *grad_features, void *workspace, size_t workspace_bytes,
+                                 void *stream);
+int df3d_voxel_pool_fused(const float *rows_in, const float *xyz, long long n_rows, int C, const void *grid,
+                          const int32_t *perm, int batch, const int *shape_host, const float *new_xyz,
+                          const int32_t *new_coords, long long M, const int *range_host, float radius, int nsample,
+                          const float *w_pos, int pool_method, float *pooled, int32_t *idx, uint8_t *empty,
+                          void *stream);
+
 #ifdef __cplusplus
 }
 #endif
