@@ -296,17 +296,17 @@ class DeformableTransformerFusionEncoderLayer(nn.Module):
         return (not self.training and self.q_method == 'sum' and list(self.q_rep_place) == ['weight']
                 and self.attn_layer == 'BiGateSum1D_2' and self.activation is F.relu and self.d_model % 4 == 0)
 
+    def _ffn_packed(self, lin_a, lin_b, slot):
+        from . import ops as _ops
+        return _ops.derived(self.__dict__, slot, (lin_a.weight, lin_b.weight), lambda: _ops.ffn_pack(
+            lin_a.weight.detach().contiguous(), lin_b.weight.detach().contiguous()))
+
     def _ffn(self, x, lin_a, lin_b, norm, slot):
         """norm(x + lin_b(relu(lin_a(x)))): one fused kernel (csrc/ffn.hip) when the sizes fit it."""
         from . import ops as _ops
         if not _ops.ffn_supported(lin_a.in_features, lin_a.out_features):
             return _ops.add_layernorm(x, lin_b(self._linear_relu(lin_a, x)), norm.weight, norm.bias, norm.eps)
-        key = (lin_a.weight.data_ptr(), lin_a.weight._version, lin_b.weight.data_ptr(), lin_b.weight._version)
-        hit = getattr(self, slot, None)
-        if hit is None or hit[0] != key:
-            hit = (key, _ops.ffn_pack(lin_a.weight.detach().contiguous(), lin_b.weight.detach().contiguous()))
-            object.__setattr__(self, slot, hit)
-        return _ops.ffn_fused(x, hit[1], lin_a.bias, lin_b.bias, lin_a.out_features, residual=x,
+        return _ops.ffn_fused(x, self._ffn_packed(lin_a, lin_b, slot), lin_a.bias, lin_b.bias, lin_a.out_features, residual=x,
                               ln_weight=norm.weight, ln_bias=norm.bias, eps=norm.eps)
 
     def _ffn_pair(self, qi, q):
@@ -319,13 +319,8 @@ class DeformableTransformerFusionEncoderLayer(nn.Module):
         jobs = []
         for x, la, lb, norm, slot in ((qi, self.linear1, self.linear2, self.norm2, "_ffn_i"),
                                       (q, self.linear3, self.linear4, self.norm3, "_ffn_p")):
-            key = (la.weight.data_ptr(), la.weight._version, lb.weight.data_ptr(), lb.weight._version)
-            hit = getattr(self, slot, None)
-            if hit is None or hit[0] != key:
-                hit = (key, _ops.ffn_pack(la.weight.detach().contiguous(), lb.weight.detach().contiguous()))
-                object.__setattr__(self, slot, hit)
-            jobs.append(dict(x=x.contiguous(), packed=hit[1], b1=la.bias, b2=lb.bias, residual=x.contiguous(),
-                             ln_weight=norm.weight, ln_bias=norm.bias, eps=norm.eps))
+            jobs.append(dict(x=x.contiguous(), packed=self._ffn_packed(la, lb, slot), b1=la.bias, b2=lb.bias,
+                             residual=x.contiguous(), ln_weight=norm.weight, ln_bias=norm.bias, eps=norm.eps))
         return tuple(_ops.ffn_fused_jobs(jobs, self.linear1.out_features))
 
     def _forward_fused(self, src, reference_points, spatial_shapes, level_start_index, q_pos, q_feat, q_i_feat,
@@ -347,12 +342,15 @@ class DeformableTransformerFusionEncoderLayer(nn.Module):
                 and _ops.rows_linear_supported(C, C) and sa.output_proj.out_features == C and C % 16 == 0):
             # the two query mixtures are formed on load and both linears run as one launch on the matrix cores; the
             # output projection carries its residual + LayerNorm (csrc/rowlinear.hip): 2 launches instead of 5
-            pk = _ops.rows_linear_pack([sa.sampling_offsets.weight, sa.attention_weights.weight],
-                                       [sa.sampling_offsets.bias, sa.attention_weights.bias])
+            ws = [sa.sampling_offsets.weight, sa.attention_weights.weight]
+            bs = [sa.sampling_offsets.bias, sa.attention_weights.bias]
+            pk = _ops.derived(sa.__dict__, "_offw_pack", ws + bs, lambda: _ops.rows_linear_pack(ws, bs))
             offsets, logits = _ops.rows_linear(q_feat, pk, x1=q_i_feat, x2=q_pos, csplit=n_off, n0=n_off, n1=n_w)
             out = _ops.ms_deform_attn_fused(value, spatial_shapes, level_start_index, ref_xy, offsets, logits, sa.n_levels,
                                             sa.n_points, pixel_scale, image_bias)
-            qi = _ops.rows_linear(out.contiguous(), _ops.rows_linear_pack(sa.output_proj.weight, sa.output_proj.bias),
+            po = sa.output_proj
+            qi = _ops.rows_linear(out.contiguous(), _ops.derived(po.__dict__, "_outproj_pack", (po.weight, po.bias),
+                                                                 lambda: _ops.rows_linear_pack(po.weight, po.bias)),
                                   ln=(q_i_feat, self.norm1))
         else:
             A, Bw = _ops.actr_prep(q_feat, q_i_feat, q_pos)
@@ -550,7 +548,8 @@ class ACTR(nn.Module):
         from . import ops as _ops
         if (v_i_feat.is_cuda and v_i_feat.dtype == torch.float32 and not torch.is_grad_enabled() and v_i_feat.shape[1] > 0
                 and _ops.CONV_PRECISION != "fp32" and _ops.rows_linear_supported(conv.in_channels, conv.out_channels)):
-            y = _ops.rows_linear(v_i_feat.contiguous(), _ops.rows_linear_pack(conv.weight, conv.bias))
+            y = _ops.rows_linear(v_i_feat.contiguous(), _ops.derived(conv.__dict__, "_iproj_pack", (conv.weight, conv.bias),
+                                                                     lambda: _ops.rows_linear_pack(conv.weight, conv.bias)))
         else:
             y = _linear(v_i_feat, conv.weight[:, :, 0], conv.bias)        # [N, Q, C]
         if y.is_cuda and y.dtype == torch.float32 and not torch.is_grad_enabled() \
@@ -589,15 +588,11 @@ class ACTR(nn.Module):
                         for l in layers))
 
     def _value_weights(self):
-        layers = self.transformer.encoder.layers
-        vkey = tuple((l.self_attn.value_proj.weight.data_ptr(), l.self_attn.value_proj.weight._version,
-                      l.self_attn.value_proj.bias._version) for l in layers)
-        hit = getattr(self, "_vcat", None)
-        if hit is None or hit[0] != vkey:
-            hit = (vkey, torch.cat([l.self_attn.value_proj.weight for l in layers], 0).contiguous(),
-                   torch.cat([l.self_attn.value_proj.bias for l in layers], 0).contiguous())
-            object.__setattr__(self, "_vcat", hit)
-        return hit[1], hit[2]
+        from . import ops as _ops
+        projs = [l.self_attn.value_proj for l in self.transformer.encoder.layers]
+        return _ops.derived(self.__dict__, "_vcat", [p.weight for p in projs] + [p.bias for p in projs],
+                            lambda: (torch.cat([p.weight for p in projs], 0).contiguous(),
+                                     torch.cat([p.bias for p in projs], 0).contiguous()))
 
     def start_values(self, u, gate):
         """The image side of forward_folded (moments of the gated projection, GroupNorm fold, value rows of every layer) queued

@@ -373,7 +373,7 @@ class BucketAdamW(object):
     Parameters without a gradient in a step see the zeros the reducer keeps for them (what DistributedDataParallel hands the
     optimizer for unused parameters): their moments decay and weight decay applies.
     The views keep their own version counters, which an in-place update of the flat buffer does not move; `step()` bumps them
-    (host side) so that every (data_ptr, _version)-keyed weight pack of the library sees the update.
+    (host side) so that every weight pack of the library (`derived.tensors_key`) sees the update.
     Re-seating happens once, here: move / cast the model BEFORE building the reducer and this optimizer."""
 
     def __init__(self, reducer, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2):

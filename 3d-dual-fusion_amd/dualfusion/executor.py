@@ -139,10 +139,8 @@ class BackbonePlan(object):
 
     # ---------------------------------------------------------------- layer specs -> C table
     def _signature(self):
-        """Change detector for the cached table: (storage address, version counter) of EVERY tensor the table is folded
-        from -- filters, conv biases, BatchNorm weight / bias / running_mean / running_var.  Version counters are bumped by
-        every in-place update (load_state_dict, optimizer steps, `bn.bias.add_()` under no_grad ...); addresses catch re-assigned
-        parameters."""
+        """Change detector for the cached table: `tensors_key` of EVERY tensor the table is folded from -- filters, conv
+        biases, BatchNorm weight / bias / running_mean / running_var."""
         slots = self.__dict__.get("_sig_slots")
         if slots is None:
             # (dict, key) of every tensor, looked up in the modules' own _parameters / _buffers dicts: this runs twice per frame
@@ -154,11 +152,7 @@ class BackbonePlan(object):
                     slots += [(s.bn._parameters, "weight"), (s.bn._parameters, "bias"),
                               (s.bn._buffers, "running_mean"), (s.bn._buffers, "running_var")]
             self.__dict__["_sig_slots"] = slots
-        sig = []
-        for d, k in slots:
-            t = d.get(k)
-            sig.append(None if t is None else (t.data_ptr(), t._version))
-        return (tuple(sig), _ops.CONV_PRECISION)
+        return (_ops.tensors_key(_ops.slot_tensors(slots)), _ops.CONV_PRECISION)
 
     def _build_table(self):
         n = len(self.specs)

@@ -82,16 +82,10 @@ class Basicgate_patch_iv_multivoxel(nn.Module):
         csrc/fusion.hip "Image-side gate without dense canvases"):
           T[idx] [9, C_idx+3]: tap responses of a voxel row of scale idx;  kg [19] = k_t, g_t, bias;
           w3 [1, Cimg], b3: the 1-channel image summary (reduced_dim3)."""
-        ps = self.__dict__.get("_param_list")
-        if ps is None:                                # collected once: the module-tree walk of parameters() is host time per step
-            ps = self.__dict__["_param_list"] = list(self.parameters())
-        key = tuple((p.data_ptr(), p._version) for p in ps)
-        hit = getattr(self, "_folded", None)
-        if hit is not None and hit[0] == key:
-            return hit[1]
-        out = self._fold()
-        object.__setattr__(self, "_folded", (key, out))
-        return out
+        slots = self.__dict__.get("_state_slots")
+        if slots is None:                             # collected once: the module-tree walk is host time per step
+            slots = self.__dict__["_state_slots"] = _ops.state_slots(self)
+        return _ops.derived(self.__dict__, "_folded", _ops.slot_tensors(slots), self._fold)
 
     def _fold(self):
         with torch.no_grad():
@@ -353,14 +347,20 @@ class VoxelWithPointProjection(nn.Module):
         w3 = self.ifat.folded()[2]
         # keyed on the parameters themselves: w3 is a view of the gate's reduced_dim3 weight (fp32), so its address survives
         # an in-place update of that parameter and only the version counter tells
-        key = _ops.tensors_key((w_full, self.ifat.reduced_dim3.weight))
-        if self._wcat is None or self._wcat[0] != key:
-            # rows padded to a multiple of 16: hipBLASLt picks a 2x slower macro-tile for a 129-row operand
-            npad = (-(w_ip.shape[0] + 1)) % 16
-            # (`_wpack` below is keyed on THIS tensor's address and version: a rebuilt Wcat is allocated while the old one is
-            # still held by `_wcat`, so its address differs from the one `_wpack` remembers)
-            self._wcat = (key, torch.cat([w_ip, w3, w3.new_zeros((npad, w3.shape[1]))], 0))
-        return w_ip, self._wcat[1]
+        # rows padded to a multiple of 16: hipBLASLt picks a 2x slower macro-tile for a 129-row operand
+        # (`_wpack` below is keyed on THIS tensor's address and version: a rebuilt Wcat is allocated while the old one is
+        # still held by `_wcat`, so its address differs from the one `_wpack` remembers)
+        return w_ip, _ops.derived(self.__dict__, "_wcat", (w_full, self.ifat.reduced_dim3.weight), lambda: torch.cat(
+            [w_ip, w3, w3.new_zeros(((-(w_ip.shape[0] + 1)) % 16, w3.shape[1]))], 0))
+
+    def _wcat_packed(self, wcat, sync=False):
+        """`Wcat` packed for the native projection kernel (csrc/imgproj.hip), kept in `_wpack`."""
+        def build():
+            packed = _ops.imgproj_pack(wcat.contiguous())
+            if sync:
+                torch.cuda.current_stream(wcat.device).synchronize()      # first use only: the worker's stream reads it
+            return packed
+        return _ops.derived(self.__dict__, "_wpack", (wcat,), build)
 
     def _image_projection(self, inp, img_conv_func=None, pixrow=None):
         """`both` [NI, C(+1+pad), H*W] = input_proj 1x1 conv of every camera map WITHOUT bias (+ the gate's 1-channel
@@ -377,18 +377,16 @@ class VoxelWithPointProjection(nn.Module):
                 and os.environ.get("DF3D_IMGPROJ", "1") == "1"):
             # native split-precision projection straight from the channel-first maps (csrc/imgproj.hip): returns
             # (pixel-major split rows of the 128 projection channels, fp32 gate row)
-            key = (wcat.data_ptr(), wcat._version)
-            if self._wpack is None or self._wpack[0] != key:
-                self._wpack = (key, _ops.imgproj_pack(wcat.contiguous()))
+            packed = self._wcat_packed(wcat)
             if pixrow is not None and os.environ.get("DF3D_ASSEMBLE_COMPACT", "1") == "1":
                 # (round 4) also the raw rows of the pixels the queries sample, pixel-major, for the query assembly.  With the
                 # LDS-staged projection and the wave-per-candidate assembly this was a loss (assembly 77 -> 63 us, projection
                 # 121 -> 155 us); with the direct projection (the lane holds its pixel's channels: two stores under a mark,
                 # 92 -> 103 us) and the by-slot assembly (78 -> 42 us) it is a gain of ~50 us per step: on by default,
                 # DF3D_ASSEMBLE_COMPACT=0 turns it off
-                return _ops.imgproj_split(inp['img_ptrs'], len(imgs), imgs[0].shape[0], S_pix, self._wpack[1],
+                return _ops.imgproj_split(inp['img_ptrs'], len(imgs), imgs[0].shape[0], S_pix, packed,
                                           pixrow=pixrow[0], pixrow_total=pixrow[1])
-            return _ops.imgproj_split(inp['img_ptrs'], len(imgs), imgs[0].shape[0], S_pix, self._wpack[1])
+            return _ops.imgproj_split(inp['img_ptrs'], len(imgs), imgs[0].shape[0], S_pix, packed)
         # The camera network runs the cameras as one batch, so the per-camera dict entries are normally views of one
         # tensor at a uniform stride: then the projection is a single batched GEMM over that storage (still no copy).
         # Unrelated buffers get one GEMM per map.
@@ -510,11 +508,7 @@ class VoxelWithPointProjection(nn.Module):
         w_ip, wcat = self._projection_weights()
         if not _ops.imgproj_supported(wcat.shape[0], inp['imgs'][0].shape[0], w_ip.shape[0]):
             return None
-        key = (wcat.data_ptr(), wcat._version)
-        if self._wpack is None or self._wpack[0] != key:
-            self._wpack = (key, _ops.imgproj_pack(wcat.contiguous()))
-            torch.cuda.current_stream(wcat.device).synchronize()      # first use only: the worker's stream reads it
-        return self._wpack[1]
+        return self._wcat_packed(wcat, sync=True)
 
     def use_prepared(self, batch_dict, layer_name, prepared):
         """Hand over a `prepare_geometry` result for the forward() of this batch_dict; its tensors must be complete on (and

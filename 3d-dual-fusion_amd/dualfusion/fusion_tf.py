@@ -264,14 +264,12 @@ class ACTRFusionLayer(nn.Module):
                 and os.environ.get("DF3D_IMGPROJ", "1") == "1"):
             NI, Ci, H, W = f0.shape
             w = actr.input_proj[0][0].weight
-            key = (w.data_ptr(), w._version)
-            if getattr(self, "_wpack", None) is None or self._wpack[0] != key:
-                self._wpack = (key, _ops.imgproj_pack(w[:, :, 0, 0].contiguous()))
+            packed = _ops.derived(self.__dict__, "_wpack", (w,), lambda: _ops.imgproj_pack(w[:, :, 0, 0].contiguous()))
             pkey = (f0.data_ptr(), NI, Ci * H * W)
             if getattr(self, "_ptrs", None) is None or self._ptrs[0] != pkey:
                 base, step = f0.data_ptr(), Ci * H * W * 4
                 self._ptrs = (pkey, torch.tensor([base + i * step for i in range(NI)], dtype=torch.int64, device=f0.device))
-            u, _ = _ops.imgproj_split(self._ptrs[1], NI, Ci, H * W, self._wpack[1])
+            u, _ = _ops.imgproj_split(self._ptrs[1], NI, Ci, H * W, packed)
             return actr.forward_folded(v_feat, grid, u, None, (H, W), v_i_feat, qpts, q_pos=q_pos)
         return actr(v_feat=v_feat, grid=grid, i_feats=img_feats, lidar_grid=qpts, v_i_feat=v_i_feat)
 

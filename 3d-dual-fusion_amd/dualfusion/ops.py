@@ -11,6 +11,7 @@ import os
 import torch
 
 from . import _lib
+from .derived import derived, slot_tensors, state_slots, tensors_key   # noqa: F401 (re-exported)
 
 
 _raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)
@@ -741,35 +742,12 @@ class ConvFilters(object):
         self.packed = _pack_filters(self.kind, filters) if self.kind != "fp32" else None
 
 
-def tensors_key(tensors):
-    """The cache key of something derived from `tensors` (None allowed): address, version counter, device and dtype of each.
-    Host-side only.  In-place updates under no_grad (optimizers, load_state_dict, `bn.bias.add_()`) move the version,
-    re-seated or converted storage moves the address; writes through `.data` move neither and are not tracked."""
-    return tuple(None if t is None else (t.data_ptr(), t._version, t.device, t.dtype) for t in tensors)
-
-
-def state_slots(module):
-    """[(dict, name)] of every parameter and buffer of the module tree, to be collected ONCE (the tree walk is host time per
-    step) and read with `slot_tensors` per call: the modules' own `_parameters` / `_buffers` dicts always hold the live
-    objects, also after `.double().float()` or an assignment replaced a buffer -- a list of the tensors themselves would go
-    on watching the dead ones."""
-    return [(d, k) for m in module.modules() for d in (m._parameters, m._buffers) for k in d]
-
-
-def slot_tensors(slots):
-    return [d.get(k) for d, k in slots]
-
-
 def conv_filters(owner, weight, kvol, cin, cout):
     """The ConvFilters of `weight` ([..., cin, cout] in any kernel shape) for the current mode, kept in `owner.__dict__` and
-    rebuilt when the parameter (address, version, device) or the kind changes; one slot per kind."""
+    rebuilt when the parameter changes; one slot per kind."""
     kind = conv_kind(kvol, cin, cout)
-    key = (weight.data_ptr(), weight._version, str(weight.device), kind)
-    cache = owner.__dict__.setdefault("_conv_filters", {})
-    hit = cache.get(kind)
-    if hit is None or hit[0] != key:
-        hit = cache[kind] = (key, ConvFilters(weight.detach().contiguous().float().view(kvol, cin, cout), kind))
-    return hit[1]
+    return derived(owner.__dict__.setdefault("_conv_filters", {}), kind, (weight,),
+                   lambda: ConvFilters(weight.detach().contiguous().float().view(kvol, cin, cout), kind))
 
 
 def is_operand(kind, rows, channels):
@@ -1344,9 +1322,6 @@ class CenterHeadLossFunction(torch.autograd.Function):
 
 
 # ------------------------------------------------------------------------- query-side dense layers (csrc/rowlinear.hip)
-_ROWLIN_CACHE = {}
-
-
 SPLIT_ACT_SCALE, SPLIT_W_SCALE = 32.0, 128.0        # csrc/common.h: DF3D_SA_SCALE, DF3D_SW_SCALE
 
 
@@ -1470,17 +1445,9 @@ def rows_linear_supported(cin, cout):
 
 def rows_linear_pack(weights, biases=None):
     """weights: one nn.Linear weight [cout, cin] or a list of them (concatenated along the outputs) -> (packed uint8,
-    bias fp32 [16 * tiles] or None, cout).  Cached per (storage, version) of the parameters."""
+    bias fp32 [16 * tiles] or None, cout).  Not cached: the caller keeps the pack with the module that owns the weights."""
     ws = list(weights) if isinstance(weights, (list, tuple)) else [weights]
     bs = list(biases) if isinstance(biases, (list, tuple)) else ([biases] if biases is not None else [None] * len(ws))
-    # keyed by (storage, version) AND validated by the identity of the parameter objects: the storage of a freed module's
-    # parameter is handed to the next module's, with the same version counter (a stale pack of another layer's weights --
-    # round 3: a test-order dependent failure)
-    ts = ws + [b for b in bs if b is not None]
-    key = tuple((w.data_ptr(), w._version) for w in ws) + tuple((b.data_ptr(), b._version) if b is not None else None for b in bs)
-    hit = _ROWLIN_CACHE.get(key)
-    if hit is not None and len(hit[0]) == len(ts) and all(r() is t for r, t in zip(hit[0], ts)):
-        return hit[1]
     W = torch.cat([w.detach().float().reshape(w.shape[0], -1) for w in ws], 0)
     cout, cin = W.shape
     if not rows_linear_supported(cin, cout):
@@ -1495,11 +1462,7 @@ def rows_linear_pack(weights, biases=None):
     if any(b is not None for b in bs):
         bias = W.new_zeros(CT * 16)
         bias[:cout] = torch.cat([b.detach().float() if b is not None else W.new_zeros(w.shape[0]) for w, b in zip(ws, bs)])
-    if len(_ROWLIN_CACHE) > 64:
-        _ROWLIN_CACHE.clear()
-    import weakref
-    _ROWLIN_CACHE[key] = (tuple(weakref.ref(t) for t in ts), (packed, bias, cout))
-    return _ROWLIN_CACHE[key][1]
+    return packed, bias, cout
 
 
 def rows_linear(x0, pack, x1=None, x2=None, csplit=None, n0=None, n1=0, ln=None):
@@ -3034,18 +2997,13 @@ def identity_table(n, device):
 def packed_linear(weight, group=None):
     """nn.Linear weight [cout, cin] -> packed split-precision operand of the conv kernels (kept with the weight): one bank
     [1, cin, cout], or with `group` columns per bank cout / group banks (wide outputs through `conv_rows_split`)."""
-    hit = getattr(weight, "_df3d_packed_linear", None)
-    key = (weight.data_ptr(), weight._version, group, CONV_PRECISION)
-    if hit is not None and hit[0] == key:
-        return hit[1]
-    w = weight.detach().float()
-    cout, cin = w.shape
-    if group is None:
-        packed = conv_pack_weights(w.t().contiguous().view(1, cin, cout))
-    else:
-        packed = conv_pack_weights_groups(w.view(cout // group, group, cin).transpose(1, 2).contiguous().view(cout // group, 1, cin, group))
-    weight._df3d_packed_linear = (key, packed)
-    return packed
+    def build():
+        w = weight.detach().float()
+        cout, cin = w.shape
+        if group is None:
+            return conv_pack_weights(w.t().contiguous().view(1, cin, cout))
+        return conv_pack_weights_groups(w.view(cout // group, group, cin).transpose(1, 2).contiguous().view(cout // group, 1, cin, group))
+    return derived(weight.__dict__, "_df3d_packed_linear", (weight,), build, (group, CONV_PRECISION))
 
 
 def pe_gather_add(feat, sel, xyz, w0, b0, w1, b1):

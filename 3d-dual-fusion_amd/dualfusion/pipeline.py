@@ -262,20 +262,17 @@ class CenterPointDetector(nn.Module):
         tape = self.__dict__.get("_tail_tape")
         if tape is not None:
             tape.reset()
-        self.__dict__.pop("_tape_tensors", None)
+        self.__dict__.pop("_tape_slots", None)
         return super(CenterPointDetector, self).train(mode)
 
-    def _tail_versions(self):
-        """Cheap change detector over every parameter / buffer of neck and head: the sum of the version counters (in-place
-        updates -- optimizer steps, load_state_dict -- bump them; train() / eval() drop the tapes)."""
-        ts = self.__dict__.get("_tape_tensors")
-        if ts is None:
-            mods = (self.hot_path.neck, self.bbox_head)
-            ts = self.__dict__["_tape_tensors"] = [t for m in mods for t in list(m.parameters()) + list(m.buffers())]
-        v = 0
-        for t in ts:
-            v += t._version
-        return v
+    def _tail_state(self):
+        """Change detector over every parameter / buffer of neck and head: their `tensors_key`, read through the modules' own
+        slots so that buffers replaced by `.double().float()` stay watched (train() / eval() drop the tapes)."""
+        from . import ops as _ops
+        slots = self.__dict__.get("_tape_slots")
+        if slots is None:
+            slots = self.__dict__["_tape_slots"] = _ops.state_slots(self.hot_path.neck) + _ops.state_slots(self.bbox_head)
+        return _ops.tensors_key(_ops.slot_tensors(slots))
 
     def _neck_head(self, bev):
         rows, (nb, _, h, w) = bev
@@ -304,7 +301,7 @@ class CenterPointDetector(nn.Module):
         tape = self.__dict__.get("_tail_tape")
         if tape is None:
             tape = self.__dict__["_tail_tape"] = TapedSection()
-        key = (nb, c, h, w, tuple(inp.shape), inp.dtype, _ops.CONV_PRECISION, self._tail_versions(),
+        key = (nb, c, h, w, tuple(inp.shape), inp.dtype, _ops.CONV_PRECISION, self._tail_state(),
                os.environ.get("DF3D_HEAD_FINAL"), os.environ.get("DF3D_HEADFINAL"), mode, os.environ.get("DF3D_HEAD_LOSS_SITES"))
         fn = (lambda: self._neck_head_for_loss(bev)) if mode == "loss" else (lambda: self._neck_head(bev))
         return tape.run(key, fn, [inp], _ops._stream())

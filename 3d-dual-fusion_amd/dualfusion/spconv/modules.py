@@ -7,6 +7,7 @@ from collections import OrderedDict
 import torch
 from torch import nn
 
+from ..derived import derived
 from .structure import SparseConvTensor
 
 
@@ -27,20 +28,15 @@ class SparseModule(nn.Module):
 def fold_batchnorm(bn):
     """(scale, shift) of an eval-mode BatchNorm1d: y = x * scale + shift.  The folded pair lives ON the module
     (so it dies with it and can never be handed to another module) and is rebuilt when any parameter / buffer
-    changes version, storage or device -- a steady-state forward launches nothing for it."""
-    tensors = (bn.weight, bn.bias, bn.running_mean, bn.running_var)
-    ver = tuple((-1, 0) if t is None else (t._version, t.data_ptr()) for t in tensors) + (bn.eps,)
-    hit = bn.__dict__.get("_df3d_fold")
-    if hit is not None and hit[0] == ver:
-        return hit[1], hit[2]
-    with torch.no_grad():
-        inv = torch.rsqrt(bn.running_var.float() + bn.eps)
-        w = bn.weight.float() if bn.weight is not None else torch.ones_like(inv)
-        b = bn.bias.float() if bn.bias is not None else torch.zeros_like(inv)
-        scale = (w * inv).contiguous()
-        shift = (b - bn.running_mean.float() * scale).contiguous()
-    bn.__dict__["_df3d_fold"] = (ver, scale, shift)
-    return scale, shift
+    changes (`derived`) -- a steady-state forward launches nothing for it."""
+    def build():
+        with torch.no_grad():
+            inv = torch.rsqrt(bn.running_var.float() + bn.eps)
+            w = bn.weight.float() if bn.weight is not None else torch.ones_like(inv)
+            b = bn.bias.float() if bn.bias is not None else torch.zeros_like(inv)
+            scale = (w * inv).contiguous()
+            return scale, (b - bn.running_mean.float() * scale).contiguous()
+    return derived(bn.__dict__, "_df3d_fold", (bn.weight, bn.bias, bn.running_mean, bn.running_var), build, (bn.eps,))
 
 
 def can_fold(bn):

@@ -1,7 +1,7 @@
 """Every cached weight pack follows the tensors it was built from.
 
 Almost every fast path keeps something derived from module state (packed filters, folded BatchNorm scale / shift,
-concatenated weights, executor tables) under a hand-written key of (data_ptr, _version) pairs.  A key that leaves one tensor
+concatenated weights, executor tables) under a key of its tensors (`dualfusion.derived`).  A key that leaves one tensor
 out makes the module compute with old weights after that tensor changes, and a suite that builds a module and runs it once
 cannot notice.  The invariant checked here, for a module instance `m` that has already run (caches warm):
 

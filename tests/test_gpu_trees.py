@@ -845,4 +845,16 @@ def test_launch_tape_over_neck_and_head_equals_plain_detector():
                     assert torch.equal(a, b), ("after an outside switch", rnd, j)
         assert st["replayed"] > before["replayed"], st
         del junk
+        # `.double().float()` replaces every buffer OBJECT (nn.Module._apply), then in-place edits of the new running
+        # statistics: the tape key reads the modules' own slots, so it follows the live buffers and records again
+        for m in (plain, taped):
+            m.double().float()
+            m.bbox_head.shared_conv[1].running_mean.add_(0.125)
+            m.hot_path.neck.blocks[0][2].running_var.mul_(1.5)
+        before = dict(st)
+        for rnd in range(2):
+            for j, (pts, ex) in enumerate(frames):
+                for a, b in zip(run(taped, pts, ex, True), run(plain, pts, ex, True)):
+                    assert torch.equal(a, b), ("converted", rnd, j)
+        assert st["recorded"] == before["recorded"] + 1, st
     torch.cuda.synchronize()

@@ -31,15 +31,15 @@ for mode in ("1", "0", "1"):
     print("DF3D_LT_FUSED=%s: %.1f us per layer (rows in + out %.0f MB -> %.2f TB/s)" % (mode, us, 2 * x.numel() * 4 / 1e6, 2 * x.numel() * 4 / us / 1e6))
 
 from dualfusion import ops  # noqa: E402
-hit = m.__dict__["_lt_packed"]
+pk, vc = m._packed_fused()
 xg = x.permute(1, 0, 2).contiguous()
 with torch.no_grad():
     for _ in range(3):
-        yg = ops.lt_layer(xg, hit[1], hit[2], 4, 128, 1e-5, 1e-5, group_major=True)
+        yg = ops.lt_layer(xg, pk, vc, 4, 128, 1e-5, 1e-5, group_major=True)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(20):
-        yg = ops.lt_layer(xg, hit[1], hit[2], 4, 128, 1e-5, 1e-5, group_major=True)
+        yg = ops.lt_layer(xg, pk, vc, 4, 128, 1e-5, 1e-5, group_major=True)
     torch.cuda.synchronize()
     print("group-major rows: %.1f us per layer" % ((time.perf_counter() - t0) / 20 * 1e6))
     os.environ["DF3D_LT_FUSED"] = "1"
