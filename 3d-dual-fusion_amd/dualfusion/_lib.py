@@ -316,6 +316,12 @@ SIGNATURES = {
     "df3d_voxel_pool_fused": (c_int, [c_void_p, c_void_p, c_longlong, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
                                       c_void_p, c_longlong, c_void_p, c_float, c_int, c_void_p, c_int, c_void_p, c_void_p,
                                       c_void_p, c_void_p]),
+    "df3d_anchor_proposals_workspace_bytes": (c_size_t, [c_void_p]),
+    "df3d_anchor_proposals": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                      c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "df3d_roi_decode_select_workspace_bytes": (c_size_t, [c_void_p]),
+    "df3d_roi_decode_select": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                       c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
 }
 
 _lib = None

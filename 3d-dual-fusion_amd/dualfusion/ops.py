@@ -1211,6 +1211,125 @@ def centerhead_predict(tasks, batch, H, W, out_size_factor, voxel_size, pc_range
     return boxes, scores, labels, counts
 
 
+MAX_ANCHORS = 32        # DF3D_MAX_ANCHORS
+TAIL_MAX_CANDIDATES = 4096      # cap of df3d_topk_keys and df3d_nms_bev
+
+
+class _AnchorCfg(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int) for n in ("batch", "H", "W", "num_anchors", "num_classes", "num_dir_bins", "num_sets")] + \
+               [("anchor_set", ctypes.c_int * MAX_ANCHORS), ("anchor", (ctypes.c_float * 5) * MAX_ANCHORS),
+                ("dir_offset", ctypes.c_float), ("dir_limit_offset", ctypes.c_float), ("nms_threshold", ctypes.c_float),
+                ("pre_max", ctypes.c_int), ("post_max", ctypes.c_int)]
+
+
+class _RoiDecodeCfg(ctypes.Structure):
+    _fields_ = [("batch", ctypes.c_int), ("num_rois", ctypes.c_int), ("num_classes", ctypes.c_int),
+                ("score_threshold", ctypes.c_float), ("nms_threshold", ctypes.c_float), ("pre_max", ctypes.c_int),
+                ("post_max", ctypes.c_int), ("output_raw_score", ctypes.c_int)]
+
+
+def _tail_rows(v, rows, cols, name):
+    if not v.is_cuda:
+        raise _lib.Df3dError("%s must live on the GPU (got %s); the MI355X path has no CPU fallback" % (name, v.device))
+    if v.dtype != torch.float32 or not v.is_cuda or v.dim() != 2 or (v.shape[1] > 1 and v.stride(1) != 1) or \
+            v.shape[0] != rows or v.shape[1] != cols:
+        raise ValueError("%s must be a CUDA fp32 [%d, %d] view with unit column stride" % (name, rows, cols))
+    return v
+
+
+def anchor_cfg(batch, H, W, num_classes, num_dir_bins, anchor_set, anchor_table, num_sets, dir_offset, dir_limit_offset,
+               nms_threshold, pre_max, post_max):
+    """The df3d_anchor_cfg of a call: anchor_set [A] ints, anchor_table [A][5] = (centre z, dx, dy, dz, rotation)."""
+    A = len(anchor_set)
+    if A > MAX_ANCHORS:
+        raise NotImplementedError("anchor proposals: at most %d anchors per location (got %d)" % (MAX_ANCHORS, A))
+    cfg = _AnchorCfg()
+    cfg.batch, cfg.H, cfg.W = int(batch), int(H), int(W)
+    cfg.num_anchors, cfg.num_classes, cfg.num_dir_bins, cfg.num_sets = A, int(num_classes), int(num_dir_bins), int(num_sets)
+    for a in range(A):
+        cfg.anchor_set[a] = int(anchor_set[a])
+        for e in range(5):
+            cfg.anchor[a][e] = float(anchor_table[a][e])
+    cfg.dir_offset, cfg.dir_limit_offset = float(dir_offset), float(dir_limit_offset)
+    cfg.nms_threshold, cfg.pre_max, cfg.post_max = float(nms_threshold), int(pre_max), int(post_max)
+    return cfg
+
+
+def anchor_proposals(cls_rows, box_rows, dir_rows, x_shifts, y_shifts, batch, H, W, num_classes, anchor_set, anchor_table,
+                     nms_threshold, pre_max, post_max, dir_offset=0.0, dir_limit_offset=0.0):
+    """Anchor head maps -> RoIs of all frames in one call, nothing read back (csrc/proposals.hip).  cls_rows [B*H*W, A*C],
+    box_rows [B*H*W, A*7], dir_rows [B*H*W, A*NB] or None: fp32 row views (any row stride); x_shifts [sets, W], y_shifts
+    [sets, H] fp32; anchor_set [A], anchor_table [A][5] host values.  -> rois [B, post_max, 7], roi_scores [B, post_max] (raw
+    logits), roi_labels [B, post_max] int64, num [B] int32."""
+    lib = _lib.load()
+    A, rows = len(anchor_set), int(batch) * int(H) * int(W)
+    _tail_rows(cls_rows, rows, A * int(num_classes), "cls_rows")
+    _tail_rows(box_rows, rows, A * 7, "box_rows")
+    nb = 0
+    if dir_rows is not None:
+        if dir_rows.dim() != 2 or dir_rows.shape[1] % A:
+            raise ValueError("dir_rows must be [B*H*W, A*NB]")
+        nb = dir_rows.shape[1] // A
+        _tail_rows(dir_rows, rows, A * nb, "dir_rows")
+    _chk(x_shifts, torch.float32, "x_shifts")
+    _chk(y_shifts, torch.float32, "y_shifts")
+    sets = int(x_shifts.shape[0])
+    if x_shifts.dim() != 2 or y_shifts.dim() != 2 or x_shifts.shape[1] != W or tuple(y_shifts.shape) != (sets, H):
+        raise ValueError("x_shifts must be [sets, W] and y_shifts [sets, H]")
+    cfg = anchor_cfg(batch, H, W, num_classes, nb, anchor_set, anchor_table, sets, dir_offset, dir_limit_offset, nms_threshold,
+                     pre_max, post_max)
+    dev = cls_rows.device
+    rois = torch.empty((cfg.batch, cfg.post_max, 7), dtype=torch.float32, device=dev)
+    scores = torch.empty((cfg.batch, cfg.post_max), dtype=torch.float32, device=dev)
+    labels = torch.empty((cfg.batch, cfg.post_max), dtype=torch.int64, device=dev)
+    num = torch.empty((cfg.batch,), dtype=torch.int32, device=dev)
+    nbytes = int(lib.df3d_anchor_proposals_workspace_bytes(ctypes.byref(cfg)))
+    ws = torch.empty((max(nbytes, 8),), dtype=torch.uint8, device=dev)
+    rc = lib.df3d_anchor_proposals(_ptr(cls_rows), int(cls_rows.stride(0)), _ptr(box_rows), int(box_rows.stride(0)),
+                                   _ptr(dir_rows), int(dir_rows.stride(0)) if dir_rows is not None else 0, _ptr(x_shifts),
+                                   _ptr(y_shifts), ctypes.byref(cfg), _ptr(rois), _ptr(scores), _ptr(labels), _ptr(num),
+                                   _ptr(ws), nbytes, _stream())
+    _lib.check(rc, "df3d_anchor_proposals")
+    return rois, scores, labels, num
+
+
+def roi_decode_select(rois, rcnn_cls, rcnn_reg, roi_labels, score_threshold, nms_threshold, pre_max, post_max,
+                      output_raw_score=False):
+    """RoIs [B, N, 7] + RCNN outputs (rcnn_cls [B*N, 1 or C], rcnn_reg [B*N, 7] fp32 row views) -> batch_box_preds [B, N, 7]
+    and the class-agnostic final selection of all frames: pred_boxes [B, post_max, 7], pred_scores [B, post_max],
+    pred_labels [B, post_max] int64 (roi_labels [B, N] int64 where given, else arg-max + 1), counts [B] int32."""
+    lib = _lib.load()
+    _chk(rois, torch.float32, "rois")
+    if rois.dim() != 3 or rois.shape[2] != 7:
+        raise ValueError("rois must be [B, N, 7]")
+    B, N = int(rois.shape[0]), int(rois.shape[1])
+    if rcnn_cls.dim() != 2:
+        raise ValueError("rcnn_cls must be [B*N, classes]")
+    _tail_rows(rcnn_cls, B * N, int(rcnn_cls.shape[1]), "rcnn_cls")
+    _tail_rows(rcnn_reg, B * N, 7, "rcnn_reg")
+    if roi_labels is not None:
+        _chk(roi_labels, torch.int64, "roi_labels")
+        if tuple(roi_labels.shape) != (B, N):
+            raise ValueError("roi_labels must be [B, N]")
+    cfg = _RoiDecodeCfg()
+    cfg.batch, cfg.num_rois, cfg.num_classes = B, N, int(rcnn_cls.shape[1])
+    cfg.score_threshold, cfg.nms_threshold = float(score_threshold), float(nms_threshold)
+    cfg.pre_max, cfg.post_max, cfg.output_raw_score = int(pre_max), int(post_max), int(bool(output_raw_score))
+    dev = rois.device
+    box_preds = torch.empty((B, N, 7), dtype=torch.float32, device=dev)
+    boxes = torch.empty((B, cfg.post_max, 7), dtype=torch.float32, device=dev)
+    scores = torch.empty((B, cfg.post_max), dtype=torch.float32, device=dev)
+    labels = torch.empty((B, cfg.post_max), dtype=torch.int64, device=dev)
+    counts = torch.empty((B,), dtype=torch.int32, device=dev)
+    nbytes = int(lib.df3d_roi_decode_select_workspace_bytes(ctypes.byref(cfg)))
+    ws = torch.empty((max(nbytes, 8),), dtype=torch.uint8, device=dev)
+    rc = lib.df3d_roi_decode_select(_ptr(rois), _ptr(rcnn_cls), int(rcnn_cls.stride(0)), _ptr(rcnn_reg), int(rcnn_reg.stride(0)),
+                                    _ptr(roi_labels), ctypes.byref(cfg), _ptr(box_preds), _ptr(boxes), _ptr(scores),
+                                    _ptr(labels), _ptr(counts), _ptr(ws), nbytes, _stream())
+    _lib.check(rc, "df3d_roi_decode_select")
+    return box_preds, boxes, scores, labels, counts
+
+
 class _HeadTargets(ctypes.Structure):
     _fields_ = [(n, ctypes.c_void_p) for n in ("hm", "ind", "mask", "cat", "box")]
 

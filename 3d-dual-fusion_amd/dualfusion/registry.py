@@ -83,6 +83,10 @@ MM_HEADS = Registry("mmdet head")              # TransFusionHead (mmdet3d HEADS 
 MM_DETECTORS = Registry("mmdet detector")      # TransFusionDetector (mmdet3d registers detectors into mmdet's DETECTORS)
 BACKBONES_3D = Registry("pcdet backbone_3d")   # pcdet uses a plain dict `__all__`; same lookup by NAME
 ROI_HEADS = Registry("pcdet roi_head")         # pcdet.models.roi_heads.__all__ (VoxelRCNNHead)
+DENSE_HEADS = Registry("pcdet dense_head")     # pcdet.models.dense_heads.__all__ (AnchorHeadSingle)
+BACKBONES_2D = Registry("pcdet backbone_2d")   # pcdet.models.backbones_2d.__all__ (BaseBEVBackbone)
+MAP_TO_BEV = Registry("pcdet map_to_bev")      # pcdet.models.backbones_2d.map_to_bev.__all__ (HeightCompression)
+DETECTORS_PCDET = Registry("pcdet detector")   # pcdet.models.detectors.__all__ (VoxelRCNN)
 
 
 def late_register():
@@ -90,7 +94,7 @@ def late_register():
     reference configs resolve `type=` / `NAME:` strings to the MI355X modules unchanged."""
     import importlib
     for m in ("spconv", "voxel", "backbones", "fusion", "fusion_tf", "necks", "heads", "transfusion_head", "transfusion",
-              "roi_heads"):
+              "roi_heads", "dense_heads", "vr_detector"):
         importlib.import_module("." + m, __package__)          # every module that registers classes (some import lazily)
     done = []
     try:
@@ -144,4 +148,13 @@ def late_register():
         done.append("pcdet.roi_heads")
     except Exception:
         pass
+    for src, path in ((DENSE_HEADS, "pcdet.models.dense_heads"), (BACKBONES_2D, "pcdet.models.backbones_2d"),
+                      (MAP_TO_BEV, "pcdet.models.backbones_2d.map_to_bev"), (DETECTORS_PCDET, "pcdet.models.detectors")):
+        try:
+            dst = importlib.import_module(path)
+            for k, v in src.module_dict.items():
+                dst.__all__[k] = v
+            done.append(path)
+        except Exception:
+            pass
     return done

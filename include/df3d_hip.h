@@ -1412,6 +1412,60 @@ int df3d_voxel_pool_fused(const float *rows_in, const float *xyz, long long n_ro
                           const float *w_pos, int pool_method, float *pooled, int32_t *idx, uint8_t *empty,
                           void *stream);
 
+/* ------------------------------------------------------------------------------------
+ * Voxel-RCNN tail (csrc/proposals.hip): anchor head maps -> RoIs, and RoIs + RCNN outputs -> final boxes,
+ * each one call for all frames with no device-to-host copy.
+ *
+ * df3d_anchor_proposals replaces AnchorHeadTemplate.generate_predicted_boxes + RoIHeadTemplate.proposal_layer
+ * (VR/pcdet/models/dense_heads/anchor_head_template.py:225-272, roi_heads/roi_head_template.py:45-102,
+ * model_utils/model_nms_utils.py:6-25).  Head maps are channels-last pixel rows [(b, y, x)][channels] f32 with row strides
+ * ld_* in floats: cls [B*H*W, A*C], box [B*H*W, A*7], dir [B*H*W, A*NB] or NULL (no direction classifier).  Anchor
+ * i = (y*W + x)*A + a of a frame: score = max_c of the RAW logit cls[a*C + c], label = first arg-max + 1; the
+ * k = min(pre_max, H*W*A) best by descending float32 logit (ties: lower anchor index) are decoded
+ * (ResidualCoder.decode_torch, utils/box_coder_utils.py:45-77, plus the direction-bin correction) against anchors read
+ * from TABLES: x_shifts [num_sets][W], y_shifts [num_sets][H] (device f32), and per anchor a its table anchor_set[a] and
+ * anchor[a] = (centre z, dx, dy, dz, rotation).  Rotated NMS (nms_threshold), at most post_max kept.
+ *   rois [B, post_max, 7] f32, roi_scores [B, post_max] f32 (the raw logits), roi_labels [B, post_max] i64, num [B] i32;
+ *   slots past num[b] hold zeros and label 1 (the reference's new_zeros + 1).
+ *   Limits: A <= DF3D_MAX_ANCHORS, B <= 255, H*W*A <= 2^22, pre_max <= 4096.
+ *
+ * df3d_roi_decode_select replaces RoIHeadTemplate.generate_predicted_boxes (roi_head_template.py:233-261) and the
+ * class-agnostic branch of Detector3DTemplate.post_processing (detectors/detector3d_template.py:251-269):
+ * rois [B, N, 7], rcnn_cls [B*N, ld_cls] (num_classes logits), rcnn_reg [B*N, ld_reg] (7 codes), roi_labels [B, N] i64
+ * or NULL (label = arg-max + 1).  box_preds [B, N, 7] = decode against the RoI with its centre zeroed, rotated about z
+ * by the RoI heading, plus the RoI centre.  score = max_c sigmoid; RoIs with score >= score_threshold in descending
+ * score order (ties: lower index), the first pre_max through rotated NMS, the first post_max kept:
+ *   pred_boxes [B, post_max, 7], pred_scores [B, post_max] (the raw max logit when output_raw_score),
+ *   pred_labels [B, post_max] i64, counts [B] i32; slots past counts[b] hold zeros.
+ *   Limits: B <= 255, N <= 4096, pre_max <= 4096. */
+#define DF3D_MAX_ANCHORS 32
+typedef struct df3d_anchor_cfg {
+  int batch, H, W;
+  int num_anchors, num_classes, num_dir_bins; /* A, C, NB (0 without direction classifier) */
+  int num_sets;
+  int anchor_set[DF3D_MAX_ANCHORS];
+  float anchor[DF3D_MAX_ANCHORS][5];
+  float dir_offset, dir_limit_offset;
+  float nms_threshold;
+  int pre_max, post_max;
+} df3d_anchor_cfg;
+size_t df3d_anchor_proposals_workspace_bytes(const df3d_anchor_cfg *cfg);
+int df3d_anchor_proposals(const float *cls, int ld_cls, const float *box, int ld_box, const float *dir, int ld_dir,
+                          const float *x_shifts, const float *y_shifts, const df3d_anchor_cfg *cfg, float *rois,
+                          float *roi_scores, long long *roi_labels, int32_t *num, void *workspace, size_t workspace_bytes,
+                          void *stream);
+typedef struct df3d_roi_decode_cfg {
+  int batch, num_rois, num_classes;
+  float score_threshold, nms_threshold;
+  int pre_max, post_max;
+  int output_raw_score;
+} df3d_roi_decode_cfg;
+size_t df3d_roi_decode_select_workspace_bytes(const df3d_roi_decode_cfg *cfg);
+int df3d_roi_decode_select(const float *rois, const float *rcnn_cls, int ld_cls, const float *rcnn_reg, int ld_reg,
+                           const long long *roi_labels, const df3d_roi_decode_cfg *cfg, float *box_preds, float *pred_boxes,
+                           float *pred_scores, long long *pred_labels, int32_t *counts, void *workspace,
+                           size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
