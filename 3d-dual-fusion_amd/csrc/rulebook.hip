@@ -349,7 +349,8 @@ extern "C" int df3d_subm_neighbors(const void *grid, const int32_t *perm, const 
                                    const int *shape, const int *ksize, const int *dilation, int32_t *nbr,
                                    void *stream_) {
   hipStream_t stream = (hipStream_t)stream_;
-  DF3D_CHECK_ARG(grid && indices && nbr && shape && ksize, "subm_neighbors: null argument");
+  // (an empty voxel set comes with null row pointers: legal, nothing to write)
+  DF3D_CHECK_ARG(grid && shape && ksize && n >= 0 && (n == 0 || (indices && nbr)), "subm_neighbors: null argument");
   ConvGeom cg;
   int K = fill_geom(cg, ksize, nullptr, nullptr, dilation, shape, shape);
   DF3D_CHECK_ARG(K <= DF3D_MAX_KVOL, "subm_neighbors: kernel volume %d > %d", K, DF3D_MAX_KVOL);
@@ -374,7 +375,7 @@ extern "C" int df3d_conv_out_indices(const int32_t *indices, int n, int batch, c
                                      const int *dilation, void *out_grid, size_t out_grid_bytes,
                                      int32_t *out_indices, int out_cap, int32_t *num_out, void *stream_) {
   hipStream_t stream = (hipStream_t)stream_;
-  DF3D_CHECK_ARG(indices && out_grid && out_indices && num_out, "conv_out_indices: null argument");
+  DF3D_CHECK_ARG(out_grid && out_indices && num_out && n >= 0 && (n == 0 || indices), "conv_out_indices: null argument");
   ConvGeom cg;
   int K = fill_geom(cg, ksize, stride, padding, dilation, in_shape, out_shape);
   DF3D_CHECK_ARG(K <= DF3D_MAX_KVOL, "conv_out_indices: kernel volume %d > %d", K, DF3D_MAX_KVOL);
@@ -407,7 +408,8 @@ extern "C" int df3d_conv_transpose_out_indices(const int32_t *indices, int n, in
                                                size_t out_grid_bytes, int32_t *out_indices, int out_cap,
                                                int32_t *num_out, void *stream_) {
   hipStream_t stream = (hipStream_t)stream_;
-  DF3D_CHECK_ARG(indices && out_grid && out_indices && num_out, "conv_transpose_out_indices: null argument");
+  DF3D_CHECK_ARG(out_grid && out_indices && num_out && n >= 0 && (n == 0 || indices),
+                 "conv_transpose_out_indices: null argument");
   ConvGeom cg;
   int K = fill_geom(cg, ksize, stride, padding, dilation, in_shape, out_shape);
   DF3D_CHECK_ARG(K <= DF3D_MAX_KVOL, "conv_transpose_out_indices: kernel volume %d > %d", K, DF3D_MAX_KVOL);
@@ -440,7 +442,7 @@ extern "C" int df3d_conv_transpose_neighbors(const void *in_grid, const int32_t 
                                              const int *stride, const int *padding, const int *dilation, int32_t *nbr,
                                              void *stream_) {
   hipStream_t stream = (hipStream_t)stream_;
-  DF3D_CHECK_ARG(in_grid && out_indices && nbr, "conv_transpose_neighbors: null argument");
+  DF3D_CHECK_ARG(in_grid && n_out >= 0 && (n_out == 0 || (out_indices && nbr)), "conv_transpose_neighbors: null argument");
   ConvGeom cg;
   int K = fill_geom(cg, ksize, stride, padding, dilation, in_shape, nullptr);
   DF3D_CHECK_ARG(K <= DF3D_MAX_KVOL, "conv_transpose_neighbors: kernel volume %d > %d", K, DF3D_MAX_KVOL);
@@ -458,7 +460,7 @@ extern "C" int df3d_conv_neighbors(const void *in_grid, const int32_t *in_perm, 
                                    int n_out, int batch, const int *in_shape, const int *ksize, const int *stride,
                                    const int *padding, const int *dilation, int32_t *nbr, void *stream_) {
   hipStream_t stream = (hipStream_t)stream_;
-  DF3D_CHECK_ARG(in_grid && out_indices && nbr, "conv_neighbors: null argument");
+  DF3D_CHECK_ARG(in_grid && n_out >= 0 && (n_out == 0 || (out_indices && nbr)), "conv_neighbors: null argument");
   ConvGeom cg;
   int K = fill_geom(cg, ksize, stride, padding, dilation, in_shape, nullptr);
   DF3D_CHECK_ARG(K <= DF3D_MAX_KVOL, "conv_neighbors: kernel volume %d > %d", K, DF3D_MAX_KVOL);
@@ -484,8 +486,10 @@ extern "C" size_t df3d_nbr_to_pairs_workspace_bytes(int kvol, int n_out) {
 extern "C" int df3d_nbr_to_pairs(const int32_t *nbr, int kvol, int n_out, int n_in, int32_t *indice_pairs,
                                  int32_t *indice_num, void *workspace, size_t workspace_bytes, void *stream_) {
   hipStream_t stream = (hipStream_t)stream_;
-  DF3D_CHECK_ARG(nbr && indice_pairs && indice_num && kvol > 0 && kvol <= DF3D_MAX_KVOL, "nbr_to_pairs: bad args");
-  DF3D_HIP(hipMemsetAsync(indice_pairs, 0xff, (size_t)kvol * 2 * (size_t)n_in * 4, stream));
+  DF3D_CHECK_ARG(indice_num && kvol > 0 && kvol <= DF3D_MAX_KVOL && n_out >= 0 && n_in >= 0 && (nbr || n_out == 0) &&
+                     (indice_pairs || n_in == 0),
+                 "nbr_to_pairs: bad args");
+  if (n_in > 0) DF3D_HIP(hipMemsetAsync(indice_pairs, 0xff, (size_t)kvol * 2 * (size_t)n_in * 4, stream));
   DF3D_HIP(hipMemsetAsync(indice_num, 0, (size_t)kvol * 4, stream));
   size_t n = (size_t)kvol * n_out;
   if (n == 0) return DF3D_OK;
@@ -510,8 +514,10 @@ extern "C" int df3d_nbr_to_pairs(const int32_t *nbr, int kvol, int n_out, int n_
 extern "C" int df3d_pairs_to_nbr(const int32_t *indice_pairs, const int32_t *indice_num_host, int kvol, int n_in,
                                  int n_out, int32_t *nbr, void *stream_) {
   hipStream_t stream = (hipStream_t)stream_;
-  DF3D_CHECK_ARG(indice_pairs && indice_num_host && nbr && kvol > 0 && kvol <= DF3D_MAX_KVOL, "pairs_to_nbr: bad args");
-  DF3D_HIP(hipMemsetAsync(nbr, 0xff, (size_t)kvol * (size_t)n_out * 4, stream));
+  DF3D_CHECK_ARG(indice_num_host && kvol > 0 && kvol <= DF3D_MAX_KVOL && n_in >= 0 && n_out >= 0 && (nbr || n_out == 0) &&
+                     (indice_pairs || n_in == 0),
+                 "pairs_to_nbr: bad args");
+  if (n_out > 0) DF3D_HIP(hipMemsetAsync(nbr, 0xff, (size_t)kvol * (size_t)n_out * 4, stream));
   if (n_in == 0 || n_out == 0) return DF3D_OK;
   NumArr na;
   for (int k = 0; k < DF3D_MAX_KVOL; ++k) na.v[k] = k < kvol ? indice_num_host[k] : 0;
