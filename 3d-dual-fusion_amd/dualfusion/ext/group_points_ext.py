@@ -15,8 +15,8 @@ def forward(b, c, n, npoints, nsample, points_tensor, idx_tensor, out_tensor):
     if tuple(points_tensor.shape) != (b, c, n) or tuple(idx_tensor.shape) != (b, npoints, nsample) or idx_tensor.dtype != torch.int32:
         raise RuntimeError("group_points forward: points [b, c, n], idx int32 [b, npoints, nsample]")
     lib = _lib.load()
-    _lib.check(lib.df3d_group_points(_ptr(points_tensor), _ptr(idx_tensor), int(b), int(c), int(n), int(npoints), int(nsample),
-                                     _ptr(out_tensor), _stream()), "df3d_group_points")
+    lib.df3d_group_points(_ptr(points_tensor), _ptr(idx_tensor), int(b), int(c), int(n), int(npoints), int(nsample),
+                          _ptr(out_tensor), _stream())
     return 1
 
 
@@ -28,6 +28,6 @@ def backward(b, c, n, npoints, nsample, grad_out_tensor, idx_tensor, grad_points
             or idx_tensor.dtype != torch.int32:
         raise RuntimeError("group_points backward: grad_out [b, c, npoints, nsample], grad_points [b, c, n]")
     lib = _lib.load()
-    _lib.check(lib.df3d_group_points_grad(_ptr(grad_out_tensor), _ptr(idx_tensor), int(b), int(c), int(n), int(npoints),
-                                          int(nsample), _ptr(grad_points_tensor), _stream()), "df3d_group_points_grad")
+    lib.df3d_group_points_grad(_ptr(grad_out_tensor), _ptr(idx_tensor), int(b), int(c), int(n), int(npoints),
+                               int(nsample), _ptr(grad_points_tensor), _stream())
     return 1

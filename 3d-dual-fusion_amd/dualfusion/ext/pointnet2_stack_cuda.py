@@ -32,10 +32,9 @@ def voxel_query_wrapper(M, R1, R2, R3, nsample, radius, z_range, y_range, x_rang
         raise RuntimeError("voxel_query: new_coords [M, 4], new_xyz [M, 3], idx [M, nsample]")
     shp_p, k1 = _lib.int3((R1, R2, R3))
     rng_p, k2 = _lib.int3((z_range, y_range, x_range))
-    _lib.check(_lib.load().df3d_voxel_query_dense(
+    _lib.load().df3d_voxel_query_dense(
         _ptr(point_indices_tensor), point_indices_tensor.shape[0], shp_p, _ptr(xyz_tensor), xyz_tensor.shape[0],
-        _ptr(new_xyz_tensor), _ptr(new_coords_tensor), int(M), rng_p, float(radius), int(nsample), _ptr(idx_tensor), _stream()),
-        "df3d_voxel_query_dense")
+        _ptr(new_xyz_tensor), _ptr(new_coords_tensor), int(M), rng_p, float(radius), int(nsample), _ptr(idx_tensor), _stream())
     return 1
 
 
@@ -57,9 +56,9 @@ def group_points_wrapper(B, M, C, nsample, features_tensor, features_batch_cnt_t
                          out_tensor):
     _stack_check(B, M, C, nsample, features_tensor, features_batch_cnt_tensor, idx_tensor, idx_batch_cnt_tensor, out_tensor,
                  "out")
-    _lib.check(_lib.load().df3d_group_points_stack(
+    _lib.load().df3d_group_points_stack(
         _ptr(features_tensor), _ptr(features_batch_cnt_tensor), _ptr(idx_tensor), _ptr(idx_batch_cnt_tensor), int(B), int(M),
-        int(C), int(nsample), features_tensor.shape[0], _ptr(out_tensor), _stream()), "df3d_group_points_stack")
+        int(C), int(nsample), features_tensor.shape[0], _ptr(out_tensor), _stream())
     return 1
 
 

@@ -540,11 +540,10 @@ class VoxelWithPointProjection(nn.Module):
         pinv = torch.empty((n, 3), dtype=torch.float32, device=dev)
         sp, k1 = _lib.float_arr(scale)
         mp, k2 = _lib.float_arr(pmin)
-        rc = lib.df3d_project_voxels(_p(ind), n, inp['B'], ncam, sp, mp, _p(inp['l2c']), _p(inp['intr']),
-                                     _p(inp['raw_hw']), _p(inp['thres']), float(np.float32(self.image_scale)),
-                                     _p(inp['feat_scale']), _p(grid), _p(mask), _p(pinv), None, _p(inp.get('aug_inv')),
-                                     _ops._stream())
-        _lib.check(rc, "df3d_project_voxels")
+        lib.df3d_project_voxels(_p(ind), n, inp['B'], ncam, sp, mp, _p(inp['l2c']), _p(inp['intr']),
+                                _p(inp['raw_hw']), _p(inp['thres']), float(np.float32(self.image_scale)),
+                                _p(inp['feat_scale']), _p(grid), _p(mask), _p(pinv), None, _p(inp.get('aug_inv')),
+                                _ops._stream())
         return grid, mask, pinv
 
     def _canvas(self, x, grid, mask, pinv, inp):
@@ -554,10 +553,9 @@ class VoxelWithPointProjection(nn.Module):
         NI = inp['B'] * inp['ncam']
         winner = torch.empty((NI, inp['h'], inp['w']), dtype=torch.int32, device=feats.device)
         canvas = torch.empty((NI, C + 3, inp['h'], inp['w']), dtype=torch.float32, device=feats.device)
-        rc = lib.df3d_scatter_to_image(_p(feats), _p(pinv), _p(x.indices.contiguous()), _p(grid), _p(mask), n, C,
-                                       inp['B'], inp['ncam'], inp['h'], inp['w'], _p(winner), _p(canvas),
-                                       _ops._stream())
-        _lib.check(rc, "df3d_scatter_to_image")
+        lib.df3d_scatter_to_image(_p(feats), _p(pinv), _p(x.indices.contiguous()), _p(grid), _p(mask), n, C,
+                                  inp['B'], inp['ncam'], inp['h'], inp['w'], _p(winner), _p(canvas),
+                                  _ops._stream())
         return canvas
 
     # ------------------------------------------------------------------ forward
@@ -567,8 +565,7 @@ class VoxelWithPointProjection(nn.Module):
         ncam = mask.shape[0]
         pos = torch.empty((ncam, n), dtype=torch.int32, device=ind.device)
         counts = torch.empty((B * ncam,), dtype=torch.int32, device=ind.device)
-        rc = _lib.load().df3d_query_slots(_p(mask), _p(ind), n, B, ncam, _p(pos), _p(counts), _ops._stream())
-        _lib.check(rc, "df3d_query_slots")
+        _lib.load().df3d_query_slots(_p(mask), _p(ind), n, B, ncam, _p(pos), _p(counts), _ops._stream())
         max_ne = int(counts.max().item()) if n > 0 else 0                                     # the one host sync
         return pos, max_ne, counts
 
@@ -700,9 +697,8 @@ class VoxelWithPointProjection(nn.Module):
         n = x.features.shape[0]
         NI = inp['B'] * inp['ncam']
         winner = torch.empty((NI, inp['h'], inp['w']), dtype=torch.int32, device=x.features.device)
-        rc = _lib.load().df3d_scatter_winner(_p(x.indices.contiguous()), _p(grid), _p(mask), n, inp['B'], inp['ncam'],
-                                             inp['h'], inp['w'], _p(winner), _ops._stream())
-        _lib.check(rc, "df3d_scatter_winner")
+        _lib.load().df3d_scatter_winner(_p(x.indices.contiguous()), _p(grid), _p(mask), n, inp['B'], inp['ncam'],
+                                        inp['h'], inp['w'], _p(winner), _ops._stream())
         return winner
 
     def _forward_inference(self, batch_dict, example, encoded_voxel_list, layer_name, img_conv_func, d_factor_list):
@@ -780,9 +776,8 @@ class VoxelWithPointProjection(nn.Module):
                 if (sidx in have and feats_s.dtype == torch.float32 and feats_s.shape[1] % 4 == 0 and Ts.dtype == torch.float32
                         and os.environ.get("DF3D_GATE_ROWS", "1") == "1"):
                     # the winner map of this scale came with the frame head (it depends on the coordinates alone)
-                    rc = lib.df3d_gate_rows(_p(feats_s.contiguous()), feats_s.shape[1], _p(pinv_s.contiguous()),
-                                            _p(Ts.contiguous()), _p(have[sidx]), NI, H, W, _p(S), int(first), _ops._stream())
-                    _lib.check(rc, "df3d_gate_rows")
+                    lib.df3d_gate_rows(_p(feats_s.contiguous()), feats_s.shape[1], _p(pinv_s.contiguous()),
+                                       _p(Ts.contiguous()), _p(have[sidx]), NI, H, W, _p(S), int(first), _ops._stream())
                     first = False
                     continue
                 if winner is None:
@@ -790,24 +785,21 @@ class VoxelWithPointProjection(nn.Module):
                 if (feats_s.dtype == torch.float32 and feats_s.shape[1] % 4 == 0 and Ts.dtype == torch.float32
                         and os.environ.get("DF3D_GATE_ROWS", "1") == "1"):
                     # the 9 responses of a row matter for the rows that win a pixel only: computed inside the scatter
-                    rc = lib.df3d_gate_scatter_rows(_p(feats_s.contiguous()), feats_s.shape[1], _p(pinv_s.contiguous()),
-                                                    _p(Ts.contiguous()), _p(x.indices.contiguous()), _p(grid_s), _p(mask_s),
-                                                    feats_s.shape[0], B, ncam, H, W, _p(winner), _p(S), int(first),
-                                                    _ops._stream())
-                    _lib.check(rc, "df3d_gate_scatter_rows")
+                    lib.df3d_gate_scatter_rows(_p(feats_s.contiguous()), feats_s.shape[1], _p(pinv_s.contiguous()),
+                                               _p(Ts.contiguous()), _p(x.indices.contiguous()), _p(grid_s), _p(mask_s),
+                                               feats_s.shape[0], B, ncam, H, W, _p(winner), _p(S), int(first),
+                                               _ops._stream())
                 else:
                     rows = torch.cat([feats_s, pinv_s], 1)
                     s9 = (rows @ Ts.t()).contiguous()                           # [n, 9]
-                    rc = lib.df3d_gate_scatter(_p(s9), _p(x.indices.contiguous()), _p(grid_s), _p(mask_s), rows.shape[0],
-                                               B, ncam, H, W, _p(winner), _p(S), int(first), _ops._stream())
-                    _lib.check(rc, "df3d_gate_scatter")
+                    lib.df3d_gate_scatter(_p(s9), _p(x.indices.contiguous()), _p(grid_s), _p(mask_s), rows.shape[0],
+                                          B, ncam, H, W, _p(winner), _p(S), int(first), _ops._stream())
                 first = False
             att = torch.empty((NI, H, W), dtype=torch.float32, device=dev)
             if gate_bias is not None:                       # the summary's bias is added inside (no element-wise pass)
-                rc = lib.df3d_gate_finish_bias(_p(gate), _p(gate_bias), _p(S), _p(kg), NI, H, W, _p(att), _ops._stream())
+                lib.df3d_gate_finish_bias(_p(gate), _p(gate_bias), _p(S), _p(kg), NI, H, W, _p(att), _ops._stream())
             else:
-                rc = lib.df3d_gate_finish(_p(gate), _p(S), _p(kg), NI, H, W, _p(att), _ops._stream())
-            _lib.check(rc, "df3d_gate_finish")
+                lib.df3d_gate_finish(_p(gate), _p(S), _p(kg), NI, H, W, _p(att), _ops._stream())
         fold = self.pfat.can_fold()
         if not fold:
             # input_proj(img * att) = att * (W img) + b   (att is a per-pixel scalar)
@@ -840,22 +832,19 @@ class VoxelWithPointProjection(nn.Module):
             # a wave per SLOT (no dead candidate waves); with `compact` the image rows of the sampled pixels are pixel-major
             # (written by the image projection): one contiguous 1 KB row per query instead of 256 scattered elements
             slot_rows = torch.empty((NI * max_ne, 4), dtype=torch.int32, device=dev)
-            rc = lib.df3d_assemble_queries2_slots(_p(feats), _p(pinv), _p(ind), _p(grid), _p(mask), _p(pos), None,
-                                                  _p(inp['img_ptrs']), _p(att), n, C, Ci, B, ncam, H, W, max_ne, _p(v_feat),
-                                                  _p(v_i_feat), _p(qgrid), _p(qpts), _p(qpos), _p(counts), _p(slot_rows),
-                                                  _p(prep["pixrow"][0]) if compact is not None else None, _p(compact),
-                                                  _ops._stream())
-            _lib.check(rc, "df3d_assemble_queries2_slots")
+            lib.df3d_assemble_queries2_slots(_p(feats), _p(pinv), _p(ind), _p(grid), _p(mask), _p(pos), None,
+                                             _p(inp['img_ptrs']), _p(att), n, C, Ci, B, ncam, H, W, max_ne, _p(v_feat),
+                                             _p(v_i_feat), _p(qgrid), _p(qpts), _p(qpos), _p(counts), _p(slot_rows),
+                                             _p(prep["pixrow"][0]) if compact is not None else None, _p(compact),
+                                             _ops._stream())
         elif compact is not None:
-            rc = lib.df3d_assemble_queries2_compact(_p(feats), _p(pinv), _p(ind), _p(grid), _p(mask), _p(pos), _p(prep["pixrow"][0]),
-                                                    _p(compact), _p(att), n, C, Ci, B, ncam, H, W, max_ne, _p(v_feat),
-                                                    _p(v_i_feat), _p(qgrid), _p(qpts), _p(qpos), _p(counts), _ops._stream())
-            _lib.check(rc, "df3d_assemble_queries2_compact")
+            lib.df3d_assemble_queries2_compact(_p(feats), _p(pinv), _p(ind), _p(grid), _p(mask), _p(pos), _p(prep["pixrow"][0]),
+                                               _p(compact), _p(att), n, C, Ci, B, ncam, H, W, max_ne, _p(v_feat),
+                                               _p(v_i_feat), _p(qgrid), _p(qpts), _p(qpos), _p(counts), _ops._stream())
         else:
-            rc = lib.df3d_assemble_queries2(_p(feats), _p(pinv), _p(ind), _p(grid), _p(mask), _p(pos), None, _p(inp['img_ptrs']),
-                                            _p(att), n, C, Ci, B, ncam, H, W, max_ne, _p(v_feat), _p(v_i_feat), _p(qgrid),
-                                            _p(qpts), _p(qpos), _p(counts), _ops._stream())
-            _lib.check(rc, "df3d_assemble_queries2")
+            lib.df3d_assemble_queries2(_p(feats), _p(pinv), _p(ind), _p(grid), _p(mask), _p(pos), None, _p(inp['img_ptrs']),
+                                       _p(att), n, C, Ci, B, ncam, H, W, max_ne, _p(v_feat), _p(v_i_feat), _p(qgrid),
+                                       _p(qpts), _p(qpos), _p(counts), _ops._stream())
         # (a10-a12) ACTR
         if fold:
             enh = self.pfat.forward_folded(v_feat, qgrid, both[0] if isinstance(both, tuple) else both,
@@ -868,16 +857,14 @@ class VoxelWithPointProjection(nn.Module):
         if C % 8 == 0 and os.environ.get("DF3D_FUSION_TAIL", "1") == "1":
             # 16-byte accesses + the operand split the convolution behind the adapter reads (no df3d_split_rows pass)
             osplit = torch.empty((n, 4 * C), dtype=torch.uint8, device=dev) if _ops.CONV_PRECISION == "split" else None
-            rc = lib.df3d_fusion_writeback_split(_p(feats), _p(enh), _p(ind), _p(mask), _p(pos), n, C, ncam, max_ne, _p(out),
-                                                 _p(osplit), _ops._stream())
-            _lib.check(rc, "df3d_fusion_writeback_split")
+            lib.df3d_fusion_writeback_split(_p(feats), _p(enh), _p(ind), _p(mask), _p(pos), n, C, ncam, max_ne, _p(out),
+                                            _p(osplit), _ops._stream())
             y = x_last.replace_feature(out)
             if osplit is not None:
                 y.set_operand("split", osplit)
             return y
-        rc = lib.df3d_fusion_writeback(_p(feats), _p(enh), _p(ind), _p(mask), _p(pos), n, C, ncam, max_ne, _p(out),
-                                       _ops._stream())
-        _lib.check(rc, "df3d_fusion_writeback")
+        lib.df3d_fusion_writeback(_p(feats), _p(enh), _p(ind), _p(mask), _p(pos), n, C, ncam, max_ne, _p(out),
+                                  _ops._stream())
         return x_last.replace_feature(out)
 
 

@@ -177,8 +177,7 @@ class ACTRFusionLayer(nn.Module):
         pinv = pts[:, 1:4].contiguous()
         pos = torch.empty((ncam, n), dtype=torch.int32, device=dev)
         counts = torch.empty((batch_size * ncam,), dtype=torch.int32, device=dev)
-        _lib.check(lib.df3d_query_slots(P(mask), P(ind), n, batch_size, ncam, P(pos), P(counts), _ops._stream()),
-                   "df3d_query_slots")
+        lib.df3d_query_slots(P(mask), P(ind), n, batch_size, ncam, P(pos), P(counts), _ops._stream())
         max_ne = int(counts.max().item()) if n > 0 else 0                                      # the one host sync
         N6 = batch_size * ncam
         v_feat = torch.empty((N6, max_ne, C), dtype=torch.float32, device=dev)
@@ -187,9 +186,9 @@ class ACTRFusionLayer(nn.Module):
         qpts = torch.empty((N6, max_ne, 3), dtype=torch.float32, device=dev)
         depth_pos = self.actr.pos_encode_method == "depth" and C % 2 == 0
         qpos = torch.empty((N6, max_ne, C), dtype=torch.float32, device=dev) if depth_pos else None
-        _lib.check(lib.df3d_assemble_queries2(P(pts_feats), P(pinv), P(ind), P(grid), P(mask), P(pos), P(f0), None, None, n, C,
-                                              Ci, batch_size, ncam, H, W, max_ne, P(v_feat), P(v_i_feat), P(qgrid), P(qpts),
-                                              P(qpos), P(counts), _ops._stream()), "df3d_assemble_queries2")
+        lib.df3d_assemble_queries2(P(pts_feats), P(pinv), P(ind), P(grid), P(mask), P(pos), P(f0), None, None, n, C,
+                                   Ci, batch_size, ncam, H, W, max_ne, P(v_feat), P(v_i_feat), P(qgrid), P(qpts),
+                                   P(qpos), P(counts), _ops._stream())
         # the reference's query coordinates are the un-truncated image coordinates over the padded input shape
         # (coor_2d, :538-546), not pixel centres of the feature map: overwrite the kernel's integer-grid values
         seg = pts[:, 0].long() * ncam + cam_id
@@ -197,8 +196,8 @@ class ACTRFusionLayer(nn.Module):
         qgrid[seg, slot] = norm
         enh = self._actr(v_feat, qgrid, [f0], qpts, v_i_feat, q_pos=qpos).contiguous()
         out = torch.empty_like(pts_feats)
-        _lib.check(lib.df3d_fusion_writeback(P(pts_feats), P(enh), P(ind), P(mask), P(pos), n, C, ncam, max_ne, P(out),
-                                             _ops._stream()), "df3d_fusion_writeback")
+        lib.df3d_fusion_writeback(P(pts_feats), P(enh), P(ind), P(mask), P(pos), n, C, ncam, max_ne, P(out),
+                                  _ops._stream())
         return out
 
     def _forward_autograd(self, img_feats, pts, pts_feats, cam_id, norm, pix, batch_size):
@@ -230,17 +229,16 @@ class ACTRFusionLayer(nn.Module):
             pinv = pts[:, 1:4].contiguous()
             pos = torch.empty((ncam, n), dtype=torch.int32, device=dev)
             counts = torch.empty((N6,), dtype=torch.int32, device=dev)
-            _lib.check(lib.df3d_query_slots(P(mask), P(ind), n, batch_size, ncam, P(pos), P(counts), _ops._stream()),
-                       "df3d_query_slots")
+            lib.df3d_query_slots(P(mask), P(ind), n, batch_size, ncam, P(pos), P(counts), _ops._stream())
             max_ne = int(counts.max().item()) if n > 0 else 0                                  # the one host sync
             rows_nograd = pts_feats.detach().contiguous()
             v_feat0 = torch.empty((N6, max_ne, C), dtype=torch.float32, device=dev)
             v_i_feat = torch.empty((N6, max_ne, Ci), dtype=torch.float32, device=dev)
             qgrid = torch.empty((N6, max_ne, 2), dtype=torch.float32, device=dev)
             qpts = torch.empty((N6, max_ne, 3), dtype=torch.float32, device=dev)
-            _lib.check(lib.df3d_assemble_queries2(P(rows_nograd), P(pinv), P(ind), P(grid), P(mask), P(pos), P(f0), None, None,
-                                                  n, C, Ci, batch_size, ncam, H, W, max_ne, P(v_feat0), P(v_i_feat), P(qgrid),
-                                                  P(qpts), None, P(counts), _ops._stream()), "df3d_assemble_queries2")
+            lib.df3d_assemble_queries2(P(rows_nograd), P(pinv), P(ind), P(grid), P(mask), P(pos), P(f0), None, None,
+                                       n, C, Ci, batch_size, ncam, H, W, max_ne, P(v_feat0), P(v_i_feat), P(qgrid),
+                                       P(qpts), None, P(counts), _ops._stream())
             seg = pts[:, 0].long() * ncam + cam_id
             slot = pos[cam_id, torch.arange(n, device=dev)].long()
             qgrid[seg, slot] = norm                    # the un-truncated image coordinates (see _forward_native)

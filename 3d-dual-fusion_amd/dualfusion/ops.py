@@ -113,14 +113,13 @@ def hard_voxelize(points, voxel_size, coors_range, max_points, max_voxels, break
     vs_p, vs_keep = _lib.float_arr(list(voxel_size))
     rg_p, rg_keep = _lib.float_arr(list(coors_range))
     if batch_index is None:
-        rc = lib.df3d_hard_voxelize(_ptr(points), P, C, vs_p, rg_p, int(max_points), cap, int(bool(break_at_cap)),
-                                    _ptr(voxels), _ptr(coors), _ptr(num), _ptr(mean), _ptr(count), _ptr(ws), wsb,
-                                    _stream())
+        lib.df3d_hard_voxelize(_ptr(points), P, C, vs_p, rg_p, int(max_points), cap, int(bool(break_at_cap)),
+                               _ptr(voxels), _ptr(coors), _ptr(num), _ptr(mean), _ptr(count), _ptr(ws), wsb,
+                               _stream())
     else:
-        rc = lib.df3d_hard_voxelize_batched(_ptr(points), P, C, vs_p, rg_p, int(max_points), cap,
-                                            int(bool(break_at_cap)), int(batch_index), _ptr(voxels), _ptr(coors),
-                                            _ptr(num), _ptr(mean), _ptr(count), _ptr(ws), wsb, _stream())
-    _lib.check(rc, "df3d_hard_voxelize")
+        lib.df3d_hard_voxelize_batched(_ptr(points), P, C, vs_p, rg_p, int(max_points), cap,
+                                       int(bool(break_at_cap)), int(batch_index), _ptr(voxels), _ptr(coors),
+                                       _ptr(num), _ptr(mean), _ptr(count), _ptr(ws), wsb, _stream())
     if defer:
         return voxels, coors, num, mean, count
     n = _read_count(count, while_waiting)
@@ -197,9 +196,8 @@ def hard_voxelize_into(points, voxels, coors, num, voxel_size, coors_range, max_
     ws = torch.empty((max(wsb, 1),), dtype=torch.uint8, device=points.device)
     vs_p, vs_keep = _lib.float_arr(list(voxel_size))
     rg_p, rg_keep = _lib.float_arr(list(coors_range))
-    rc = lib.df3d_hard_voxelize(_ptr(points), P, C, vs_p, rg_p, int(max_points), cap, int(bool(break_at_cap)), _ptr(voxels),
-                                _ptr(coors), _ptr(num), None, _ptr(count), _ptr(ws), wsb, _stream())
-    _lib.check(rc, "df3d_hard_voxelize")
+    lib.df3d_hard_voxelize(_ptr(points), P, C, vs_p, rg_p, int(max_points), cap, int(bool(break_at_cap)), _ptr(voxels),
+                           _ptr(coors), _ptr(num), None, _ptr(count), _ptr(ws), wsb, _stream())
     return _read_count(count, None)
 
 
@@ -219,8 +217,7 @@ def grid_build(indices, batch, shape, rows_sorted=False):
     blob = torch.empty((nbytes,), dtype=torch.uint8, device=indices.device)
     n = indices.shape[0]
     perm = None if rows_sorted else torch.empty((max(n, 1),), dtype=torch.int32, device=indices.device)
-    rc = lib.df3d_grid_build(_ptr(indices), n, int(batch), shp_p, _ptr(blob), nbytes, _ptr(perm), _stream())
-    _lib.check(rc, "df3d_grid_build")
+    lib.df3d_grid_build(_ptr(indices), n, int(batch), shp_p, _ptr(blob), nbytes, _ptr(perm), _stream())
     return GridDirectory(blob, perm, batch, shape)
 
 
@@ -232,9 +229,8 @@ def subm_neighbors(grid, indices, ksize, dilation=(1, 1, 1)):
     shp_p, k1 = _lib.int3(grid.shape)
     ks_p, k2 = _lib.int3(ksize)
     dl_p, k3 = _lib.int3(dilation)
-    rc = lib.df3d_subm_neighbors(_ptr(grid.blob), _ptr(grid.perm), _ptr(indices), n, grid.batch, shp_p, ks_p, dl_p,
-                                 _ptr(nbr), _stream())
-    _lib.check(rc, "df3d_subm_neighbors")
+    lib.df3d_subm_neighbors(_ptr(grid.blob), _ptr(grid.perm), _ptr(indices), n, grid.batch, shp_p, ks_p, dl_p,
+                            _ptr(nbr), _stream())
     return nbr
 
 
@@ -262,9 +258,8 @@ def conv_out_indices(indices, batch, in_shape, out_shape, ksize, stride, padding
     pd_p, k4 = _lib.int3(padding)
     dl_p, k5 = _lib.int3(dilation)
     fn = lib.df3d_conv_transpose_out_indices if transpose else lib.df3d_conv_out_indices
-    rc = fn(_ptr(indices), n, int(batch), ish_p, osh_p, ks_p, st_p, pd_p, dl_p, _ptr(blob), nbytes, _ptr(out_ind), cap,
-            _ptr(count), _stream())
-    _lib.check(rc, "df3d_conv_out_indices")
+    fn(_ptr(indices), n, int(batch), ish_p, osh_p, ks_p, st_p, pd_p, dl_p, _ptr(blob), nbytes, _ptr(out_ind), cap,
+       _ptr(count), _stream())
     n_out = int(count.item())
     if n_out > cap:
         raise _lib.Df3dError("conv_out_indices: %d outputs exceed the capacity bound %d" % (n_out, cap))
@@ -282,9 +277,8 @@ def conv_neighbors(in_grid, out_indices, ksize, stride, padding, dilation=(1, 1,
     pd_p, k4 = _lib.int3(padding)
     dl_p, k5 = _lib.int3(dilation)
     fn = lib.df3d_conv_transpose_neighbors if transpose else lib.df3d_conv_neighbors
-    rc = fn(_ptr(in_grid.blob), _ptr(in_grid.perm), _ptr(out_indices), n_out, in_grid.batch, ish_p, ks_p, st_p, pd_p, dl_p,
-            _ptr(nbr), _stream())
-    _lib.check(rc, "df3d_conv_neighbors")
+    fn(_ptr(in_grid.blob), _ptr(in_grid.perm), _ptr(out_indices), n_out, in_grid.batch, ish_p, ks_p, st_p, pd_p, dl_p,
+       _ptr(nbr), _stream())
     return nbr
 
 
@@ -296,8 +290,7 @@ def nbr_to_pairs(nbr, n_in):
     num = torch.empty((K,), dtype=torch.int32, device=nbr.device)
     wsb = lib.df3d_nbr_to_pairs_workspace_bytes(K, n_out)
     ws = torch.empty((max(wsb, 1),), dtype=torch.uint8, device=nbr.device)
-    rc = lib.df3d_nbr_to_pairs(_ptr(nbr), K, n_out, max(n_in, 1), _ptr(pairs), _ptr(num), _ptr(ws), wsb, _stream())
-    _lib.check(rc, "df3d_nbr_to_pairs")
+    lib.df3d_nbr_to_pairs(_ptr(nbr), K, n_out, max(n_in, 1), _ptr(pairs), _ptr(num), _ptr(ws), wsb, _stream())
     return pairs[:, :, :n_in], num
 
 
@@ -307,9 +300,8 @@ def pairs_to_nbr(indice_pairs, indice_num, n_out):
     K, _, n_in = indice_pairs.shape
     num_host = indice_num.to("cpu", torch.int32).contiguous()
     nbr = torch.empty((K, n_out), dtype=torch.int32, device=indice_pairs.device)
-    rc = lib.df3d_pairs_to_nbr(_ptr(indice_pairs), ctypes.c_void_p(num_host.data_ptr()), K, n_in, n_out, _ptr(nbr),
-                               _stream())
-    _lib.check(rc, "df3d_pairs_to_nbr")
+    lib.df3d_pairs_to_nbr(_ptr(indice_pairs), ctypes.c_void_p(num_host.data_ptr()), K, n_in, n_out, _ptr(nbr),
+                          _stream())
     return nbr
 
 
@@ -346,8 +338,8 @@ class KernelTimer(object):
         pairs = ctypes.c_longlong()
         split = ctypes.c_int()
         for i in range(n):
-            _lib.check(lib.df3d_timing_get2(i, ctypes.cast(shape, ctypes.c_void_p), ctypes.addressof(ms),
-                                            ctypes.addressof(pairs), ctypes.addressof(split)), "df3d_timing_get2")
+            lib.df3d_timing_get2(i, ctypes.cast(shape, ctypes.c_void_p), ctypes.addressof(ms),
+                                 ctypes.addressof(pairs), ctypes.addressof(split))
             # split: 0 = fp32 MFMA kernel, 1 = split precision, 2 = bf16 rows; bit 3 = the launch wrote fp32 AND split rows
             self.records.append(dict(cin=shape[0], cout=shape[1], kvol=shape[2], n_out=shape[3], ms=float(ms.value),
                                      pairs=int(pairs.value), split=int(split.value) & 3, both=bool(int(split.value) & 8)))
@@ -368,8 +360,7 @@ def conv_tiles(nbr, cin, cout):
     tiles = torch.empty((nt + 1,), dtype=torch.int32, device=nbr.device)
     wsb = lib.df3d_conv_tiles_workspace_bytes(int(n_out))
     ws = torch.empty((wsb,), dtype=torch.uint8, device=nbr.device)
-    rc = lib.df3d_conv_tiles(_ptr(nbr), K, n_out, nt, _ptr(tiles), _ptr(ws), wsb, _stream())
-    _lib.check(rc, "df3d_conv_tiles")
+    lib.df3d_conv_tiles(_ptr(nbr), K, n_out, nt, _ptr(tiles), _ptr(ws), wsb, _stream())
     return tiles
 
 
@@ -404,10 +395,9 @@ def sparse_conv_grouped(features, filters, nbr, n_out, bias=None, scale=None, sh
           or out_col + G * cout > out.shape[1]):
         raise _lib.Df3dError("sparse_conv_grouped: out must be float32 [n_out, >= %d] rows" % (out_col + G * cout))
     dst = out[:, out_col:] if out_col else out
-    rc = lib.df3d_sparse_conv_grouped(_ptr(features), features.shape[0], cin, int(features.stride(0)), int(group_in), _ptr(filters),
-                                      K, cout, G, _ptr(nbr), n_out, _ptr(bias), _ptr(scale), _ptr(shift), int(bool(relu)),
-                                      _ptr(dst), int(out.stride(0)), cout, _stream())
-    _lib.check(rc, "df3d_sparse_conv_grouped")
+    lib.df3d_sparse_conv_grouped(_ptr(features), features.shape[0], cin, int(features.stride(0)), int(group_in), _ptr(filters),
+                                 K, cout, G, _ptr(nbr), n_out, _ptr(bias), _ptr(scale), _ptr(shift), int(bool(relu)),
+                                 _ptr(dst), int(out.stride(0)), cout, _stream())
     return out
 
 
@@ -432,11 +422,10 @@ def sparse_conv_fused(features, filters, nbr, n_out, bias=None, scale=None, shif
         if t is not None:
             _chk(t, torch.float32, nm)
     out = torch.empty((n_out, cout), dtype=torch.float32, device=features.device)
-    rc = lib.df3d_sparse_conv_fused_tiled(_ptr(features), n_in, cin, _ptr(filters), K, cout, _ptr(nbr), n_out,
-                                          _ptr(bias), _ptr(scale), _ptr(shift), _ptr(residual), int(bool(relu)),
-                                          _ptr(out), _ptr(tiles), (tiles.shape[0] - 1) if tiles is not None else 0,
-                                          _stream())
-    _lib.check(rc, "df3d_sparse_conv_fused")
+    lib.df3d_sparse_conv_fused_tiled(_ptr(features), n_in, cin, _ptr(filters), K, cout, _ptr(nbr), n_out,
+                                     _ptr(bias), _ptr(scale), _ptr(shift), _ptr(residual), int(bool(relu)),
+                                     _ptr(out), _ptr(tiles), (tiles.shape[0] - 1) if tiles is not None else 0,
+                                     _stream())
     return out
 
 
@@ -616,7 +605,7 @@ def _pack_filters(kind, filters, grouped=False):
         raise _lib.Df3dError("no %s%s kernel for K=%d cin=%d cout=%d" % ("grouped " if grouped else "", kind, K, cin, cout))
     packed = torch.empty((G * nbytes,), dtype=torch.uint8, device=filters.device)
     args = (_ptr(filters),) + ((G,) if entry in _PACK_TAKES_GROUPS else ()) + (K, cin, cout, _ptr(packed), _stream())
-    _lib.check(getattr(lib, entry)(*args), entry)
+    getattr(lib, entry)(*args)
     return packed
 
 
@@ -642,7 +631,7 @@ def operand_rows(kind, features):
     _chk(features, torch.float32, "features")
     n, c = features.shape
     out = torch.empty((n, operand_width(kind, c)), dtype=fmt.dtype, device=features.device)
-    _lib.check(getattr(lib, fmt.rows)(_ptr(features), n, c, _ptr(out), _stream()), fmt.rows)
+    getattr(lib, fmt.rows)(_ptr(features), n, c, _ptr(out), _stream())
     return out
 
 
@@ -662,7 +651,7 @@ def rows_from_bf16(rows):
     _chk(rows, torch.bfloat16, "rows")
     n, c = rows.shape
     out = torch.empty((n, c), dtype=torch.float32, device=rows.device)
-    _lib.check(lib.df3d_rows_from_bf16(_ptr(rows), n, c, _ptr(out), _stream()), "df3d_rows_from_bf16")
+    lib.df3d_rows_from_bf16(_ptr(rows), n, c, _ptr(out), _stream())
     return out
 
 
@@ -676,8 +665,7 @@ def split_rows_scaled(features, inv_channels):
     out = torch.empty((n, 4 * c), dtype=torch.uint8, device=features.device)
     scale = torch.empty((int(lib.df3d_pow2_scale_floats()),), dtype=torch.float32, device=features.device)
     inv = torch.empty((int(inv_channels),), dtype=torch.float32, device=features.device)
-    rc = lib.df3d_split_rows_scaled(_ptr(features), n, c, _ptr(out), _ptr(scale), _ptr(inv), int(inv_channels), _stream())
-    _lib.check(rc, "df3d_split_rows_scaled")
+    lib.df3d_split_rows_scaled(_ptr(features), n, c, _ptr(out), _ptr(scale), _ptr(inv), int(inv_channels), _stream())
     return out, inv, scale
 
 
@@ -704,15 +692,14 @@ def _conv_operands(kind, rows, packed, nbr, n_out, cin, cout, bias, scale, shift
     head = (_ptr(rows), rows.shape[0], cin)
     epilogue = (_ptr(bias), _ptr(scale), _ptr(shift), _ptr(residual), int(bool(relu)))
     if kind == "bf16":
-        rc = lib.df3d_sparse_conv_bf16(*head, _ptr(packed), K, cout, _ptr(nbr), int(n_out), *epilogue, _ptr(out), _ptr(orows),
-                                       _stream())
+        lib.df3d_sparse_conv_bf16(*head, _ptr(packed), K, cout, _ptr(nbr), int(n_out), *epilogue, _ptr(out), _ptr(orows),
+                                  _stream())
     elif kind == "split":
-        rc = lib.df3d_sparse_conv_split(*head, _ptr(packed), K, cout, _ptr(nbr), int(n_out), *epilogue, _ptr(out), _ptr(orows),
-                                        _ptr(order), -1 if order is not None else 0, _stream())
+        lib.df3d_sparse_conv_split(*head, _ptr(packed), K, cout, _ptr(nbr), int(n_out), *epilogue, _ptr(out), _ptr(orows),
+                                   _ptr(order), -1 if order is not None else 0, _stream())
     else:                                   # the grouped three-part entry with one group
-        rc = lib.df3d_conv_rows_split3(*head, cin, 0, _ptr(packed), K, cout, 1, _ptr(nbr), int(n_out), *epilogue, _ptr(out), cout,
-                                       None, _ptr(orows), _stream())
-    _lib.check(rc, fmt.conv)
+        lib.df3d_conv_rows_split3(*head, cin, 0, _ptr(packed), K, cout, 1, _ptr(nbr), int(n_out), *epilogue, _ptr(out), cout,
+                                  None, _ptr(orows), _stream())
     return out, orows
 
 
@@ -789,8 +776,7 @@ def invert_neighbors(nbr, n_in):
     _chk(nbr, torch.int32, "nbr")
     K, n_out = nbr.shape
     inv = torch.empty((K, int(n_in)), dtype=torch.int32, device=nbr.device)
-    rc = lib.df3d_invert_neighbors(_ptr(nbr), K, n_out, int(n_in), _ptr(inv), _stream())
-    _lib.check(rc, "df3d_invert_neighbors")
+    lib.df3d_invert_neighbors(_ptr(nbr), K, n_out, int(n_in), _ptr(inv), _stream())
     return inv
 
 
@@ -800,7 +786,7 @@ def rows_pow2_scale(x):
     lib = _lib.load()
     _chk(x, torch.float32, "x")
     scale = torch.empty((int(lib.df3d_pow2_scale_floats()),), dtype=torch.float32, device=x.device)
-    _lib.check(lib.df3d_rows_pow2_scale(_ptr(x), int(x.numel()), _ptr(scale), _stream()), "df3d_rows_pow2_scale")
+    lib.df3d_rows_pow2_scale(_ptr(x), int(x.numel()), _ptr(scale), _stream())
     return scale
 
 
@@ -824,9 +810,8 @@ def sparse_conv_grad_filters(features, grad_out, nbr, grad_scale=None, bf16=Fals
     elif grad_scale is not None and grad_scaled():
         _chk(grad_scale, torch.float32, "grad_scale")
         entry, scale = entry + "_scaled", (_ptr(grad_scale),)
-    rc = getattr(lib, entry)(_ptr(features), features.shape[0], cin, _ptr(grad_out), n_out, cout, _ptr(nbr), K, *scale, _ptr(gw),
-                             _stream())
-    _lib.check(rc, entry)
+    getattr(lib, entry)(_ptr(features), features.shape[0], cin, _ptr(grad_out), n_out, cout, _ptr(nbr), K, *scale, _ptr(gw),
+                        _stream())
     return gw
 
 
@@ -846,7 +831,7 @@ def rows_grad_weights(x, grad_out, x_scale=None, g_scale=None, two_part=False):
     entry, scales = "df3d_rows_grad_weights", ()
     if (two_part or x_scale is not None or g_scale is not None) and grad_scaled():
         entry, scales = entry + "_scaled", (_ptr(x_scale), _ptr(g_scale))
-    _lib.check(getattr(lib, entry)(_ptr(x), _ptr(grad_out), int(n), int(cin), int(cout), *scales, _ptr(gw), _stream()), entry)
+    getattr(lib, entry)(_ptr(x), _ptr(grad_out), int(n), int(cin), int(cout), *scales, _ptr(gw), _stream())
     return gw
 
 
@@ -916,10 +901,9 @@ def conv_rows_split(in_split, cin, in_group_stride, packed, cout, groups, nbr, n
 
     def launch(po, oc, pcols, ps):
         residual = (None,) if fmt.parts == 3 else ()          # (only the three-part entry has the parameter)
-        rc = getattr(lib, fmt.conv_rows)(_ptr(in_split), n_in, in_channels, int(cin), int(in_group_stride), _ptr(packed), K,
-                                         int(cout), int(groups), _ptr(nbr), int(n_out), _ptr(bias), _ptr(scale), _ptr(shift),
-                                         *residual, int(bool(relu)), po, oc, pcols, ps, _stream())
-        _lib.check(rc, fmt.conv_rows)
+        getattr(lib, fmt.conv_rows)(_ptr(in_split), n_in, in_channels, int(cin), int(in_group_stride), _ptr(packed), K,
+                                    int(cout), int(groups), _ptr(nbr), int(n_out), _ptr(bias), _ptr(scale), _ptr(shift),
+                                    *residual, int(bool(relu)), po, oc, pcols, ps, _stream())
 
     if into is not None:
         out, osp, col0 = into
@@ -955,7 +939,7 @@ def head_final_pack(weights):
     if tuple(weights.shape[1:]) != (9, 64, 4):
         raise _lib.Df3dError("head_final_pack: weights [G,9,64,4] expected")
     packed = torch.empty(int(lib.df3d_head_final_packed_bytes(G)), dtype=torch.uint8, device=weights.device)
-    _lib.check(lib.df3d_head_final_pack(_ptr(weights), G, _ptr(packed), _stream()), "df3d_head_final_pack")
+    lib.df3d_head_final_pack(_ptr(weights), G, _ptr(packed), _stream())
     return packed
 
 
@@ -979,14 +963,12 @@ def head_final_conv(in_split, batch, H, W, weights, bias, out_cols, out_channels
         _chk(packed, torch.uint8, "packed")
         if packed.numel() != lib.df3d_head_final_packed_bytes(G):
             raise _lib.Df3dError("head_final_conv: packed filters do not match %d branches" % G)
-        rc = lib.df3d_head_final_conv_packed(_ptr(in_split), in_split.shape[1] // 4, int(batch), int(H), int(W), G,
-                                             _ptr(packed), _ptr(bias), _ptr(out_cols), _ptr(out), int(out_channels),
-                                             _stream())
-        _lib.check(rc, "df3d_head_final_conv_packed")
+        lib.df3d_head_final_conv_packed(_ptr(in_split), in_split.shape[1] // 4, int(batch), int(H), int(W), G,
+                                        _ptr(packed), _ptr(bias), _ptr(out_cols), _ptr(out), int(out_channels),
+                                        _stream())
         return out
-    rc = lib.df3d_head_final_conv(_ptr(in_split), in_split.shape[1] // 4, int(batch), int(H), int(W), G, _ptr(weights),
-                                  _ptr(bias), _ptr(out_cols), _ptr(out), int(out_channels), _stream())
-    _lib.check(rc, "df3d_head_final_conv")
+    lib.df3d_head_final_conv(_ptr(in_split), in_split.shape[1] // 4, int(batch), int(H), int(W), G, _ptr(weights),
+                             _ptr(bias), _ptr(out_cols), _ptr(out), int(out_channels), _stream())
     return out
 
 
@@ -999,7 +981,7 @@ def head_regress_pack(filters):
         raise _lib.Df3dError("head_regress_pack: filters [banks,9,64,64] expected")
     banks = filters.shape[0]
     packed = torch.empty(int(lib.df3d_head_regress_packed_bytes(banks)), dtype=torch.uint8, device=filters.device)
-    _lib.check(lib.df3d_head_regress_pack(_ptr(filters), banks, _ptr(packed), _stream()), "df3d_head_regress_pack")
+    lib.df3d_head_regress_pack(_ptr(filters), banks, _ptr(packed), _stream())
     return packed
 
 
@@ -1044,9 +1026,8 @@ def head_regress_at(s1_split, batch, H, W, inds, masks, packed, bias1, scale1, s
         keep.append((ind, mask))
         tg[i].ind, tg[i].mask = ind.data_ptr(), mask.data_ptr()
     pred = torch.empty((T, int(batch) * M, LOSS_MAX_CODES), dtype=torch.float32, device=s1_split.device)
-    rc = lib.df3d_head_regress_at(_ptr(s1_split), int(batch), int(H), int(W), ctypes.byref(tg), T, M, banks // T, _ptr(packed),
-                                  _ptr(bias1), _ptr(scale1), _ptr(shift1), _ptr(w2), _ptr(b2), _ptr(cols), _ptr(pred), _stream())
-    _lib.check(rc, "df3d_head_regress_at")
+    lib.df3d_head_regress_at(_ptr(s1_split), int(batch), int(H), int(W), ctypes.byref(tg), T, M, banks // T, _ptr(packed),
+                             _ptr(bias1), _ptr(scale1), _ptr(shift1), _ptr(w2), _ptr(b2), _ptr(cols), _ptr(pred), _stream())
     return pred
 
 
@@ -1057,8 +1038,7 @@ def sparse_to_dense(features, indices, batch, shape):
     n, C = features.shape
     out = torch.empty([int(batch), C] + [int(s) for s in shape], dtype=torch.float32, device=features.device)
     shp_p, keep = _lib.int3(shape)
-    rc = lib.df3d_sparse_to_dense(_ptr(features), _ptr(indices), n, C, int(batch), shp_p, _ptr(out), _stream())
-    _lib.check(rc, "df3d_sparse_to_dense")
+    lib.df3d_sparse_to_dense(_ptr(features), _ptr(indices), n, C, int(batch), shp_p, _ptr(out), _stream())
     return out
 
 
@@ -1072,8 +1052,7 @@ def sparse_to_dense_rows(features, indices, batch, shape):
     D, H, W = [int(v) for v in shape]
     out = torch.empty((int(batch) * H * W, C * D), dtype=torch.float32, device=features.device)
     shp_p, keep = _lib.int3(shape)
-    rc = lib.df3d_sparse_to_dense_rows(_ptr(features), _ptr(indices), n, C, int(batch), shp_p, _ptr(out), _stream())
-    _lib.check(rc, "df3d_sparse_to_dense_rows")
+    lib.df3d_sparse_to_dense_rows(_ptr(features), _ptr(indices), n, C, int(batch), shp_p, _ptr(out), _stream())
     return out
 
 
@@ -1086,8 +1065,7 @@ def sparse_to_dense_rows_split(features, indices, batch, shape):
     D, H, W = [int(v) for v in shape]
     out = torch.empty((int(batch) * H * W, 4 * C * D), dtype=torch.uint8, device=features.device)
     shp_p, keep = _lib.int3(shape)
-    rc = lib.df3d_sparse_to_dense_rows_split(_ptr(features), _ptr(indices), n, C, int(batch), shp_p, _ptr(out), _stream())
-    _lib.check(rc, "df3d_sparse_to_dense_rows_split")
+    lib.df3d_sparse_to_dense_rows_split(_ptr(features), _ptr(indices), n, C, int(batch), shp_p, _ptr(out), _stream())
     return out
 
 
@@ -1099,9 +1077,8 @@ def conv2d_neighbors(batch, H, W, kh, kw, stride, pad, transposed, device):
     else:
         Ho, Wo = (H + 2 * pad - kh) // stride + 1, (W + 2 * pad - kw) // stride + 1
     nbr = torch.empty((kh * kw, int(batch) * Ho * Wo), dtype=torch.int32, device=device)
-    rc = lib.df3d_conv2d_neighbors(int(batch), int(H), int(W), int(kh), int(kw), int(stride), int(pad),
-                                   int(bool(transposed)), _ptr(nbr), _stream())
-    _lib.check(rc, "df3d_conv2d_neighbors")
+    lib.df3d_conv2d_neighbors(int(batch), int(H), int(W), int(kh), int(kw), int(stride), int(pad),
+                              int(bool(transposed)), _ptr(nbr), _stream())
     return nbr, Ho, Wo
 
 
@@ -1117,9 +1094,8 @@ def boxes_bev_pairwise(boxes_a, boxes_b, iou=True):
     if boxes_a.dim() != 2 or boxes_b.dim() != 2 or boxes_a.shape[1] != 7 or boxes_b.shape[1] != 7:
         raise ValueError("boxes must be [N, 7] (x, y, z, dx, dy, dz, heading)")
     out = torch.zeros((boxes_a.shape[0], boxes_b.shape[0]), dtype=torch.float32, device=boxes_a.device)
-    rc = lib.df3d_boxes_bev_pairwise(_ptr(boxes_a), boxes_a.shape[0], _ptr(boxes_b), boxes_b.shape[0], int(bool(iou)),
-                                     _ptr(out), _stream())
-    _lib.check(rc, "df3d_boxes_bev_pairwise")
+    lib.df3d_boxes_bev_pairwise(_ptr(boxes_a), boxes_a.shape[0], _ptr(boxes_b), boxes_b.shape[0], int(bool(iou)),
+                                _ptr(out), _stream())
     return out
 
 
@@ -1140,19 +1116,20 @@ def nms_bev(boxes, thresh, mode=NMS_ROTATED, counts=None, max_keep=0):
     num = torch.zeros((S,), dtype=torch.int32, device=boxes.device)
     nbytes = lib.df3d_nms_bev_workspace_bytes(S, cap)
     ws = torch.empty((max(int(nbytes), 8),), dtype=torch.uint8, device=boxes.device)
-    rc = lib.df3d_nms_bev(_ptr(boxes), _ptr(counts) if counts is not None else None, S, cap, float(thresh), int(mode),
-                          int(max_keep), _ptr(keep), _ptr(num), _ptr(ws), int(nbytes), _stream())
-    _lib.check(rc, "df3d_nms_bev")
+    lib.df3d_nms_bev(_ptr(boxes), _ptr(counts) if counts is not None else None, S, cap, float(thresh), int(mode),
+                     int(max_keep), _ptr(keep), _ptr(num), _ptr(ws), int(nbytes), _stream())
     return (keep[0], num[0]) if single else (keep, num)
 
 
 class _HeadTask(ctypes.Structure):
+    _c_name_ = "df3d_head_task"
     _fields_ = [(n, ctypes.c_void_p) for n in ("hm", "reg", "height", "dim", "rot", "vel")] + \
                [(n, ctypes.c_int) for n in ("ld_hm", "ld_reg", "ld_height", "ld_dim", "ld_rot", "ld_vel", "num_classes",
                                             "label_base")]
 
 
 class _HeadCfg(ctypes.Structure):
+    _c_name_ = "df3d_head_decode_cfg"
     _fields_ = [("batch", ctypes.c_int), ("H", ctypes.c_int), ("W", ctypes.c_int), ("out_size_factor", ctypes.c_float),
                 ("voxel_size", ctypes.c_float * 2), ("pc_range", ctypes.c_float * 2),
                 ("has_post_center_range", ctypes.c_int), ("post_center_range", ctypes.c_float * 6),
@@ -1205,9 +1182,8 @@ def centerhead_predict(tasks, batch, H, W, out_size_factor, voxel_size, pc_range
     if nbytes == 0:
         raise ValueError("df3d_centerhead_predict: unsupported configuration")
     ws = torch.empty((int(nbytes),), dtype=torch.uint8, device=dev)
-    rc = lib.df3d_centerhead_predict(ctypes.byref(arr), n, ctypes.byref(cfg), _ptr(boxes), _ptr(scores), _ptr(labels),
-                                     _ptr(counts), _ptr(ws), int(nbytes), _stream())
-    _lib.check(rc, "df3d_centerhead_predict")
+    lib.df3d_centerhead_predict(ctypes.byref(arr), n, ctypes.byref(cfg), _ptr(boxes), _ptr(scores), _ptr(labels),
+                                _ptr(counts), _ptr(ws), int(nbytes), _stream())
     return boxes, scores, labels, counts
 
 
@@ -1216,6 +1192,7 @@ TAIL_MAX_CANDIDATES = 4096      # cap of df3d_topk_keys and df3d_nms_bev
 
 
 class _AnchorCfg(ctypes.Structure):
+    _c_name_ = "df3d_anchor_cfg"
     _fields_ = [(n, ctypes.c_int) for n in ("batch", "H", "W", "num_anchors", "num_classes", "num_dir_bins", "num_sets")] + \
                [("anchor_set", ctypes.c_int * MAX_ANCHORS), ("anchor", (ctypes.c_float * 5) * MAX_ANCHORS),
                 ("dir_offset", ctypes.c_float), ("dir_limit_offset", ctypes.c_float), ("nms_threshold", ctypes.c_float),
@@ -1223,6 +1200,7 @@ class _AnchorCfg(ctypes.Structure):
 
 
 class _RoiDecodeCfg(ctypes.Structure):
+    _c_name_ = "df3d_roi_decode_cfg"
     _fields_ = [("batch", ctypes.c_int), ("num_rois", ctypes.c_int), ("num_classes", ctypes.c_int),
                 ("score_threshold", ctypes.c_float), ("nms_threshold", ctypes.c_float), ("pre_max", ctypes.c_int),
                 ("post_max", ctypes.c_int), ("output_raw_score", ctypes.c_int)]
@@ -1285,11 +1263,10 @@ def anchor_proposals(cls_rows, box_rows, dir_rows, x_shifts, y_shifts, batch, H,
     num = torch.empty((cfg.batch,), dtype=torch.int32, device=dev)
     nbytes = int(lib.df3d_anchor_proposals_workspace_bytes(ctypes.byref(cfg)))
     ws = torch.empty((max(nbytes, 8),), dtype=torch.uint8, device=dev)
-    rc = lib.df3d_anchor_proposals(_ptr(cls_rows), int(cls_rows.stride(0)), _ptr(box_rows), int(box_rows.stride(0)),
-                                   _ptr(dir_rows), int(dir_rows.stride(0)) if dir_rows is not None else 0, _ptr(x_shifts),
-                                   _ptr(y_shifts), ctypes.byref(cfg), _ptr(rois), _ptr(scores), _ptr(labels), _ptr(num),
-                                   _ptr(ws), nbytes, _stream())
-    _lib.check(rc, "df3d_anchor_proposals")
+    lib.df3d_anchor_proposals(_ptr(cls_rows), int(cls_rows.stride(0)), _ptr(box_rows), int(box_rows.stride(0)),
+                              _ptr(dir_rows), int(dir_rows.stride(0)) if dir_rows is not None else 0, _ptr(x_shifts),
+                              _ptr(y_shifts), ctypes.byref(cfg), _ptr(rois), _ptr(scores), _ptr(labels), _ptr(num),
+                              _ptr(ws), nbytes, _stream())
     return rois, scores, labels, num
 
 
@@ -1323,14 +1300,14 @@ def roi_decode_select(rois, rcnn_cls, rcnn_reg, roi_labels, score_threshold, nms
     counts = torch.empty((B,), dtype=torch.int32, device=dev)
     nbytes = int(lib.df3d_roi_decode_select_workspace_bytes(ctypes.byref(cfg)))
     ws = torch.empty((max(nbytes, 8),), dtype=torch.uint8, device=dev)
-    rc = lib.df3d_roi_decode_select(_ptr(rois), _ptr(rcnn_cls), int(rcnn_cls.stride(0)), _ptr(rcnn_reg), int(rcnn_reg.stride(0)),
-                                    _ptr(roi_labels), ctypes.byref(cfg), _ptr(box_preds), _ptr(boxes), _ptr(scores),
-                                    _ptr(labels), _ptr(counts), _ptr(ws), nbytes, _stream())
-    _lib.check(rc, "df3d_roi_decode_select")
+    lib.df3d_roi_decode_select(_ptr(rois), _ptr(rcnn_cls), int(rcnn_cls.stride(0)), _ptr(rcnn_reg), int(rcnn_reg.stride(0)),
+                               _ptr(roi_labels), ctypes.byref(cfg), _ptr(box_preds), _ptr(boxes), _ptr(scores),
+                               _ptr(labels), _ptr(counts), _ptr(ws), nbytes, _stream())
     return box_preds, boxes, scores, labels, counts
 
 
 class _HeadTargets(ctypes.Structure):
+    _c_name_ = "df3d_head_targets"
     _fields_ = [(n, ctypes.c_void_p) for n in ("hm", "ind", "mask", "cat", "box")]
 
 
@@ -1399,16 +1376,14 @@ def centerhead_loss(tasks, targets, batch, H, W, code_weights, weight, grad_task
     if grad_tasks is not None:
         garr = (_HeadTask * n)()
         _fill_head_tasks(garr, grad_tasks, batch * H * W)
-        rc = lib.df3d_centerhead_loss_grad(ctypes.byref(arr), ctypes.byref(garr), ctypes.byref(tg), n, int(batch), int(H),
-                                           int(W), M, D, ctypes.cast(cw, ctypes.c_void_p), len(code_weights), float(weight),
-                                           _ptr(out), _ptr(ws), nbytes, _stream())
-        _lib.check(rc, "df3d_centerhead_loss_grad")
+        lib.df3d_centerhead_loss_grad(ctypes.byref(arr), ctypes.byref(garr), ctypes.byref(tg), n, int(batch), int(H),
+                                      int(W), M, D, ctypes.cast(cw, ctypes.c_void_p), len(code_weights), float(weight),
+                                      _ptr(out), _ptr(ws), nbytes, _stream())
         return out
     entry = "df3d_centerhead_loss_slots" if reg_by_slot else "df3d_centerhead_loss"
-    rc = getattr(lib, entry)(ctypes.byref(arr), ctypes.byref(tg), n, int(batch), int(H), int(W), M, D,
-                             ctypes.cast(cw, ctypes.c_void_p), len(code_weights), float(weight), _ptr(out), _ptr(ws),
-                             nbytes, _stream())
-    _lib.check(rc, entry)
+    getattr(lib, entry)(ctypes.byref(arr), ctypes.byref(tg), n, int(batch), int(H), int(W), M, D,
+                        ctypes.cast(cw, ctypes.c_void_p), len(code_weights), float(weight), _ptr(out), _ptr(ws),
+                        nbytes, _stream())
     return out
 
 
@@ -1449,10 +1424,8 @@ def split_overflow(reset=True):
     (activations |x| < 2047, filters |w| < 511; or a NaN / inf) since the last reset.  Synchronises the device."""
     lib = _lib.load()
     buf = ctypes.create_string_buffer(256)
-    rc = lib.df3d_split_overflow(int(bool(reset)), buf, 256)
-    if rc < 0:
-        _lib.check(rc, "df3d_split_overflow")
-    return bool(rc), buf.value.decode()
+    hit = lib.df3d_split_overflow(int(bool(reset)), buf, 256)
+    return bool(hit), buf.value.decode()
 
 
 def check_split_overflow():
@@ -1481,7 +1454,7 @@ def overflow_word(reset=True):
     host copy you make anyway -- `read_with_range_flag` does that for the usual case of a few integers."""
     lib = _lib.load()
     word = torch.zeros((1,), dtype=torch.int32, device=torch.device("cuda", torch.cuda.current_device()))
-    _lib.check(lib.df3d_split_overflow_collect(_ptr(word), int(bool(reset)), _stream()), "df3d_split_overflow_collect")
+    lib.df3d_split_overflow_collect(_ptr(word), int(bool(reset)), _stream())
     return word
 
 
@@ -1608,13 +1581,13 @@ def rows_linear(x0, pack, x1=None, x2=None, csplit=None, n0=None, n1=0, ln=None)
         res, norm = ln
         _chk(res, torch.float32, "ln residual")
         gamma, beta, eps = norm.weight, norm.bias, float(norm.eps)
-    rc = lib.df3d_rows_linear(_ptr(x0), _ptr(x1), _ptr(x2), rows, int(cin), _ptr(packed), int(cout), csplit, _ptr(bias),
-                              _ptr(out0), n0, n0, _ptr(out1), int(n1), int(n1), _ptr(res), _ptr(gamma), _ptr(beta), eps, _stream())
-    _lib.check(rc, "df3d_rows_linear")
+    lib.df3d_rows_linear(_ptr(x0), _ptr(x1), _ptr(x2), rows, int(cin), _ptr(packed), int(cout), csplit, _ptr(bias),
+                         _ptr(out0), n0, n0, _ptr(out1), int(n1), int(n1), _ptr(res), _ptr(gamma), _ptr(beta), eps, _stream())
     return (out0, out1) if n1 else out0
 
 # ------------------------------------------------------------------------- TransFusion head: matching costs + losses
 class _TfMatchCfg(ctypes.Structure):
+    _c_name_ = "df3d_tf_match_cfg"
     _fields_ = [("out_size_factor", ctypes.c_float), ("voxel_size", ctypes.c_float * 2), ("pc_range", ctypes.c_float * 2),
                 ("point_cloud_range", ctypes.c_float * 6), ("cls_weight", ctypes.c_float), ("cls_alpha", ctypes.c_float),
                 ("cls_gamma", ctypes.c_float), ("cls_eps", ctypes.c_float), ("reg_weight", ctypes.c_float),
@@ -1622,11 +1595,13 @@ class _TfMatchCfg(ctypes.Structure):
 
 
 class _TfSplatCfg(ctypes.Structure):
+    _c_name_ = "df3d_tf_splat_cfg"
     _fields_ = [("voxel_size", ctypes.c_float * 2), ("out_size_factor", ctypes.c_float),
                 ("point_cloud_range", ctypes.c_float * 2), ("gaussian_overlap", ctypes.c_double), ("min_radius", ctypes.c_int)]
 
 
 class _TfLossCfg(ctypes.Structure):
+    _c_name_ = "df3d_tf_loss_cfg"
     _fields_ = [("encode_step", ctypes.c_float * 2), ("pc_range", ctypes.c_float * 2), ("cls_alpha", ctypes.c_float),
                 ("cls_gamma", ctypes.c_float), ("cls_loss_weight", ctypes.c_float), ("bbox_loss_weight", ctypes.c_float),
                 ("pos_weight", ctypes.c_float), ("code_weights", ctypes.c_float * 10)]
@@ -1641,8 +1616,7 @@ def boxes_overlap_bev_xyxyr(boxes_a, boxes_b):
     if boxes_a.dim() != 2 or boxes_b.dim() != 2 or boxes_a.shape[1] != 5 or boxes_b.shape[1] != 5:
         raise ValueError("boxes must be [N, 5] (x1, y1, x2, y2, angle)")
     out = torch.zeros((boxes_a.shape[0], boxes_b.shape[0]), dtype=torch.float32, device=boxes_a.device)
-    rc = lib.df3d_boxes_overlap_bev_xyxyr(_ptr(boxes_a), boxes_a.shape[0], _ptr(boxes_b), boxes_b.shape[0], _ptr(out), _stream())
-    _lib.check(rc, "df3d_boxes_overlap_bev_xyxyr")
+    lib.df3d_boxes_overlap_bev_xyxyr(_ptr(boxes_a), boxes_a.shape[0], _ptr(boxes_b), boxes_b.shape[0], _ptr(out), _stream())
     return out
 
 
@@ -1673,9 +1647,8 @@ def tf_match_cost(rows, col_cls, num_classes, gt, gt_labels, gt_off, gmax, out_s
     cost = torch.empty((B, P, gmax), dtype=torch.float32, device=rows.device)
     iou = torch.empty((B, P, gmax), dtype=torch.float32, device=rows.device)
     boxes = torch.empty((B, P, 7), dtype=torch.float32, device=rows.device)
-    rc = lib.df3d_tf_match_cost(_ptr(rows), B, P, ld, int(col_cls), int(num_classes), _ptr(gt), _ptr(gt_labels), _ptr(gt_off),
-                                int(gt.shape[1]), gmax, ctypes.byref(cfg), _ptr(cost), _ptr(iou), _ptr(boxes), _stream())
-    _lib.check(rc, "df3d_tf_match_cost")
+    lib.df3d_tf_match_cost(_ptr(rows), B, P, ld, int(col_cls), int(num_classes), _ptr(gt), _ptr(gt_labels), _ptr(gt_off),
+                           int(gt.shape[1]), gmax, ctypes.byref(cfg), _ptr(cost), _ptr(iou), _ptr(boxes), _stream())
     return cost, iou, boxes
 
 
@@ -1690,9 +1663,8 @@ def draw_heatmap_gaussian(gt, gt_labels, gt_off, batch, num_classes, H, W, voxel
     cfg.point_cloud_range[0], cfg.point_cloud_range[1] = float(point_cloud_range[0]), float(point_cloud_range[1])
     cfg.gaussian_overlap, cfg.min_radius = float(gaussian_overlap), int(min_radius)
     heat = torch.empty((int(batch), int(num_classes), int(H), int(W)), dtype=torch.float32, device=gt_off.device)
-    rc = lib.df3d_draw_heatmap_gaussian(_ptr(gt), _ptr(gt_labels), _ptr(gt_off), int(gt.shape[1]), int(gt.shape[0]), int(batch),
-                                        int(num_classes), int(H), int(W), ctypes.byref(cfg), _ptr(heat), _stream())
-    _lib.check(rc, "df3d_draw_heatmap_gaussian")
+    lib.df3d_draw_heatmap_gaussian(_ptr(gt), _ptr(gt_labels), _ptr(gt_off), int(gt.shape[1]), int(gt.shape[0]), int(batch),
+                                   int(num_classes), int(H), int(W), ctypes.byref(cfg), _ptr(heat), _stream())
     return heat
 
 
@@ -1709,10 +1681,9 @@ def gaussian_focal_loss(logits, target, alpha=2.0, gamma=4.0, loss_weight=1.0, w
     ws = torch.empty((max(int(lib.df3d_gaussian_focal_loss_workspace_bytes(n)), 8),), dtype=torch.uint8, device=target.device)
     out = torch.empty((3,), dtype=torch.float32, device=target.device)
     grad = torch.empty((B, C, H, W), dtype=torch.float32, device=target.device) if want_grad else None
-    rc = lib.df3d_gaussian_focal_loss(_ptr(logits), logits.stride(0), logits.stride(1), logits.stride(3), _ptr(target), B, C,
-                                      H * W, float(alpha), float(gamma), float(loss_weight), _ptr(grad), _ptr(out), _ptr(ws),
-                                      ws.numel(), _stream())
-    _lib.check(rc, "df3d_gaussian_focal_loss")
+    lib.df3d_gaussian_focal_loss(_ptr(logits), logits.stride(0), logits.stride(1), logits.stride(3), _ptr(target), B, C,
+                                 H * W, float(alpha), float(gamma), float(loss_weight), _ptr(grad), _ptr(out), _ptr(ws),
+                                 ws.numel(), _stream())
     return out, grad
 
 
@@ -1738,14 +1709,14 @@ def tf_query_loss(rows, assigned, iou, num_proposals, col_cls, num_classes, code
     layers = P_all // int(num_proposals)
     out = torch.empty((2 * layers + 2,), dtype=torch.float32, device=rows.device)
     grad = torch.zeros_like(rows) if want_grad else None
-    rc = lib.df3d_tf_query_loss(_ptr(rows), _ptr(assigned), _ptr(iou), B, P_all, int(num_proposals), ld, int(col_cls),
-                                int(num_classes), int(code_size), _ptr(gt), _ptr(gt_labels), _ptr(gt_off), int(gt.shape[1]),
-                                int(iou.shape[2]), ctypes.byref(cfg), _ptr(grad), _ptr(out), _stream())
-    _lib.check(rc, "df3d_tf_query_loss")
+    lib.df3d_tf_query_loss(_ptr(rows), _ptr(assigned), _ptr(iou), B, P_all, int(num_proposals), ld, int(col_cls),
+                           int(num_classes), int(code_size), _ptr(gt), _ptr(gt_labels), _ptr(gt_off), int(gt.shape[1]),
+                           int(iou.shape[2]), ctypes.byref(cfg), _ptr(grad), _ptr(out), _stream())
     return out, grad
 
 
 class _QueryHeads(ctypes.Structure):
+    _c_name_ = "df3d_query_heads"
     _fields_ = [(n, ctypes.c_void_p) for n in ("heatmap", "center", "height", "dim", "rot", "vel")] + \
                [(n, ctypes.c_int) for n in ("ld_heatmap", "ld_center", "ld_height", "ld_dim", "ld_rot", "ld_vel")]
 
@@ -1787,12 +1758,11 @@ def heatmap_proposals(heat_rows, batch, num_classes, H, W, nms_kernel_size, exem
     if nbytes == 0:
         raise ValueError("df3d_heatmap_proposals: unsupported map size")
     ws = torch.empty((int(nbytes),), dtype=torch.uint8, device=dev)
-    rc = lib.df3d_heatmap_proposals(_ptr(heat_rows), int(heat_rows.stride(0)), int(batch), C, int(H), int(W),
-                                    int(nms_kernel_size), mask, K, _ptr(feat_rows),
-                                    int(feat_rows.stride(0)) if feat_rows is not None else 0, ch, _ptr(class_weight),
-                                    _ptr(class_bias), _ptr(top_class), _ptr(top_pixel), _ptr(qscore), _ptr(qpos),
-                                    _ptr(qfeat), _ptr(ws), int(nbytes), _stream())
-    _lib.check(rc, "df3d_heatmap_proposals")
+    lib.df3d_heatmap_proposals(_ptr(heat_rows), int(heat_rows.stride(0)), int(batch), C, int(H), int(W),
+                               int(nms_kernel_size), mask, K, _ptr(feat_rows),
+                               int(feat_rows.stride(0)) if feat_rows is not None else 0, ch, _ptr(class_weight),
+                               _ptr(class_bias), _ptr(top_class), _ptr(top_pixel), _ptr(qscore), _ptr(qpos),
+                               _ptr(qfeat), _ptr(ws), int(nbytes), _stream())
     return top_class, top_pixel, qscore, qpos, qfeat
 
 
@@ -1832,9 +1802,8 @@ def transfusion_decode(heads, query_score, query_label, batch, num_proposals, nu
     scores = torch.empty((B, K), dtype=torch.float32, device=dev)
     labels = torch.empty((B, K), dtype=torch.int32, device=dev)
     counts = torch.empty((B,), dtype=torch.int32, device=dev)
-    rc = lib.df3d_transfusion_decode(ctypes.byref(qh), _ptr(query_score), _ptr(query_label), B, K, int(num_classes),
-                                     ctypes.byref(cfg), _ptr(boxes), _ptr(scores), _ptr(labels), _ptr(counts), _stream())
-    _lib.check(rc, "df3d_transfusion_decode")
+    lib.df3d_transfusion_decode(ctypes.byref(qh), _ptr(query_score), _ptr(query_label), B, K, int(num_classes),
+                                ctypes.byref(cfg), _ptr(boxes), _ptr(scores), _ptr(labels), _ptr(counts), _stream())
     return boxes, scores, labels, counts
 
 
@@ -1845,8 +1814,7 @@ def sparse_maxpool(features, nbr, n_out):
     _chk(nbr, torch.int32, "nbr")
     n_in, C = features.shape
     out = torch.empty((int(n_out), C), dtype=torch.float32, device=features.device)
-    rc = lib.df3d_sparse_maxpool(_ptr(features), n_in, C, _ptr(nbr), nbr.shape[0], int(n_out), _ptr(out), _stream())
-    _lib.check(rc, "df3d_sparse_maxpool")
+    lib.df3d_sparse_maxpool(_ptr(features), n_in, C, _ptr(nbr), nbr.shape[0], int(n_out), _ptr(out), _stream())
     return out
 
 
@@ -1858,9 +1826,8 @@ def sparse_maxpool_backward(features, out_features, grad_out, inv):
     _chk(inv, torch.int32, "inv")
     n_in, C = features.shape
     gin = torch.empty_like(features)
-    rc = lib.df3d_sparse_maxpool_backward(_ptr(features), _ptr(out_features), _ptr(grad_out), n_in, C, _ptr(inv),
-                                          inv.shape[0], _ptr(gin), _stream())
-    _lib.check(rc, "df3d_sparse_maxpool_backward")
+    lib.df3d_sparse_maxpool_backward(_ptr(features), _ptr(out_features), _ptr(grad_out), n_in, C, _ptr(inv),
+                                     inv.shape[0], _ptr(gin), _stream())
     return gin
 
 
@@ -1873,9 +1840,8 @@ def dynamic_voxelize(points, voxel_size, coors_range, out=None):
     coors = torch.empty((P, 3), dtype=torch.int32, device=points.device) if out is None else _chk(out, torch.int32, "coors")
     vs = (ctypes.c_float * 3)(*[float(v) for v in voxel_size])
     rng = (ctypes.c_float * 6)(*[float(v) for v in coors_range])
-    rc = lib.df3d_dynamic_voxelize(_ptr(points), P, F, ctypes.cast(vs, ctypes.c_void_p), ctypes.cast(rng, ctypes.c_void_p),
-                                   _ptr(coors), _stream())
-    _lib.check(rc, "df3d_dynamic_voxelize")
+    lib.df3d_dynamic_voxelize(_ptr(points), P, F, ctypes.cast(vs, ctypes.c_void_p), ctypes.cast(rng, ctypes.c_void_p),
+                              _ptr(coors), _stream())
     return coors
 
 
@@ -1941,9 +1907,8 @@ def dynamic_scatter_plan(coors):
     offsets = torch.empty((N + 1,), dtype=torch.int32, device=dev)
     ids = torch.empty((N,), dtype=torch.int32, device=dev)
     status = torch.empty((2,), dtype=torch.int32, device=dev)
-    rc = lib.df3d_dynamic_scatter_plan(_ptr(coors), N, ndim, _ptr(voxel_coors), _ptr(p2v), _ptr(count), _ptr(offsets),
-                                       _ptr(ids), _ptr(status), _ptr(ws), wsb, stream)
-    _lib.check(rc, "df3d_dynamic_scatter_plan")
+    lib.df3d_dynamic_scatter_plan(_ptr(coors), N, ndim, _ptr(voxel_coors), _ptr(p2v), _ptr(count), _ptr(offsets),
+                                  _ptr(ids), _ptr(status), _ptr(ws), wsb, stream)
     M, overflow = status.tolist()                                    # the one D2H read
     if overflow:
         raise _lib.Df3dError("dynamic_scatter_plan: the product of (max + 1) over the coordinate columns does not fit in "
@@ -1975,9 +1940,8 @@ def dynamic_scatter_reduce(feats, plan, reduce):
     out = torch.empty((M, C), dtype=feats.dtype, device=feats.device)
     if M == 0 or C == 0:
         return out
-    rc = _lib.load().df3d_dynamic_scatter_reduce(_ptr(feats), int(feats.dtype == torch.float64), C, _ptr(plan.point_ids),
-                                                 _ptr(plan.offsets), M, code, _ptr(out), _stream())
-    _lib.check(rc, "df3d_dynamic_scatter_reduce")
+    _lib.load().df3d_dynamic_scatter_reduce(_ptr(feats), int(feats.dtype == torch.float64), C, _ptr(plan.point_ids),
+                                            _ptr(plan.offsets), M, code, _ptr(out), _stream())
     return out
 
 
@@ -1988,10 +1952,9 @@ def _voxel_to_point(voxel_rows, plan, mean=False):
     out = torch.empty((N, C), dtype=voxel_rows.dtype, device=voxel_rows.device)
     if N == 0 or C == 0:
         return out
-    rc = _lib.load().df3d_voxel_to_point(_ptr(voxel_rows), int(voxel_rows.dtype == torch.float64), C,
-                                         _ptr(plan.point2voxel_map), _ptr(plan.voxel_points_count if mean else None), N,
-                                         _ptr(out), _stream())
-    _lib.check(rc, "df3d_voxel_to_point")
+    _lib.load().df3d_voxel_to_point(_ptr(voxel_rows), int(voxel_rows.dtype == torch.float64), C,
+                                    _ptr(plan.point2voxel_map), _ptr(plan.voxel_points_count if mean else None), N,
+                                    _ptr(out), _stream())
     return out
 
 
@@ -2018,13 +1981,11 @@ def dynamic_scatter_backward(grad_voxel_feats, feats, voxel_feats, point2voxel_m
     dbl = int(feats.dtype == torch.float64)
     if code == 2:
         arg = torch.empty((max(M * C, 1),), dtype=torch.int32, device=feats.device)
-        rc = lib.df3d_dynamic_scatter_max_backward(_ptr(feats), _ptr(voxel_feats), _ptr(grad_voxel_feats), dbl, N, M, C,
-                                                   _ptr(point2voxel_map), _ptr(arg), _ptr(grad), _stream())
-        _lib.check(rc, "df3d_dynamic_scatter_max_backward")
+        lib.df3d_dynamic_scatter_max_backward(_ptr(feats), _ptr(voxel_feats), _ptr(grad_voxel_feats), dbl, N, M, C,
+                                              _ptr(point2voxel_map), _ptr(arg), _ptr(grad), _stream())
     else:
-        rc = lib.df3d_voxel_to_point(_ptr(grad_voxel_feats), dbl, C, _ptr(point2voxel_map),
-                                     _ptr(voxel_points_count if code == 1 else None), N, _ptr(grad), _stream())
-        _lib.check(rc, "df3d_voxel_to_point")
+        lib.df3d_voxel_to_point(_ptr(grad_voxel_feats), dbl, C, _ptr(point2voxel_map),
+                                _ptr(voxel_points_count if code == 1 else None), N, _ptr(grad), _stream())
     return grad
 
 
@@ -2091,8 +2052,7 @@ def topk_keys(keys, k):
     if nbytes == 0:
         raise _lib.Df3dError("df3d_topk_keys: unsupported sizes (1 <= k <= 4096)")
     ws = torch.empty((int(nbytes),), dtype=torch.uint8, device=keys.device)
-    rc = lib.df3d_topk_keys(_ptr(keys), S, n, int(k), _ptr(out), _ptr(cnt), _ptr(ws), int(nbytes), _stream())
-    _lib.check(rc, "df3d_topk_keys")
+    lib.df3d_topk_keys(_ptr(keys), S, n, int(k), _ptr(out), _ptr(cnt), _ptr(ws), int(nbytes), _stream())
     return out, cnt
 
 
@@ -2112,10 +2072,9 @@ def cross_attention(q, k, v, batch, heads, scale=None):
     if nbytes == 0:
         raise ValueError("df3d_cross_attention: unsupported sizes")
     ws = torch.empty((int(nbytes),), dtype=torch.uint8, device=q.device)
-    rc = lib.df3d_cross_attention(_ptr(q), int(q.stride(0)), _ptr(k), int(k.stride(0)), _ptr(v), int(v.stride(0)), int(batch),
-                                  nq, nk, int(heads), 16, float(scale if scale is not None else 0.25), _ptr(out), E, _ptr(ws),
-                                  int(nbytes), _stream())
-    _lib.check(rc, "df3d_cross_attention")
+    lib.df3d_cross_attention(_ptr(q), int(q.stride(0)), _ptr(k), int(k.stride(0)), _ptr(v), int(v.stride(0)), int(batch),
+                             nq, nk, int(heads), 16, float(scale if scale is not None else 0.25), _ptr(out), E, _ptr(ws),
+                             int(nbytes), _stream())
     return out
 
 
@@ -2132,9 +2091,8 @@ class _CrossAttention(torch.autograd.Function):
         lse = torch.empty((B, heads, nq), dtype=torch.float32, device=q.device)
         nbytes = int(lib.df3d_cross_attention_workspace_bytes(B, heads, nq, nk))
         ws = torch.empty((nbytes,), dtype=torch.uint8, device=q.device)
-        rc = lib.df3d_cross_attention_train(_ptr(q), E, _ptr(k), E, _ptr(v), E, B, nq, nk, heads, 16, float(scale), float(p),
-                                            int(seed), _ptr(out), E, _ptr(lse), _ptr(ws), nbytes, _stream())
-        _lib.check(rc, "df3d_cross_attention_train")
+        lib.df3d_cross_attention_train(_ptr(q), E, _ptr(k), E, _ptr(v), E, B, nq, nk, heads, 16, float(scale), float(p),
+                                       int(seed), _ptr(out), E, _ptr(lse), _ptr(ws), nbytes, _stream())
         ctx.save_for_backward(q, k, v, out, lse)
         ctx.cfg = (heads, float(scale), float(p), int(seed))
         return out
@@ -2148,10 +2106,9 @@ class _CrossAttention(torch.autograd.Function):
         grad = grad.contiguous()
         delta = (grad * out).view(B, nq, heads, 16).sum(-1).transpose(1, 2).contiguous()       # [B, heads, nq]
         dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
-        rc = _lib.load().df3d_cross_attention_backward(_ptr(q), E, _ptr(k), E, _ptr(v), E, _ptr(grad), E, _ptr(lse), _ptr(delta),
-                                                       B, nq, nk, heads, 16, scale, p, seed, _ptr(dq), E, _ptr(dk), E,
-                                                       _ptr(dv), E, _stream())
-        _lib.check(rc, "df3d_cross_attention_backward")
+        _lib.load().df3d_cross_attention_backward(_ptr(q), E, _ptr(k), E, _ptr(v), E, _ptr(grad), E, _ptr(lse), _ptr(delta),
+                                                  B, nq, nk, heads, 16, scale, p, seed, _ptr(dq), E, _ptr(dk), E,
+                                                  _ptr(dv), E, _stream())
         return dq, dk, dv, None, None, None, None
 
 
@@ -2200,10 +2157,9 @@ def ms_deform_attn_forward(value, spatial_shapes, level_start_index, sampling_lo
         N, S, M, D = value.shape
         _, Lq, _, L, P, _ = sampling_locations.shape
         out = torch.empty((N, Lq, M * D), dtype=torch.float64, device=value.device)
-        rc = lib.df3d_ms_deform_attn_forward_f64(_ptr(value), _ptr(spatial_shapes), _ptr(level_start_index),
-                                                 _ptr(sampling_locations), _ptr(attention_weights), N, S, M, D, Lq, L, P,
-                                                 _ptr(out), _stream())
-        _lib.check(rc, "df3d_ms_deform_attn_forward_f64")
+        lib.df3d_ms_deform_attn_forward_f64(_ptr(value), _ptr(spatial_shapes), _ptr(level_start_index),
+                                            _ptr(sampling_locations), _ptr(attention_weights), N, S, M, D, Lq, L, P,
+                                            _ptr(out), _stream())
         return out
     _chk(value, torch.float32, "value")
     _chk(spatial_shapes, torch.int64, "spatial_shapes")
@@ -2213,10 +2169,9 @@ def ms_deform_attn_forward(value, spatial_shapes, level_start_index, sampling_lo
     N, S, M, D = value.shape
     _, Lq, _, L, P, _ = sampling_locations.shape
     out = torch.empty((N, Lq, M * D), dtype=torch.float32, device=value.device)
-    rc = lib.df3d_ms_deform_attn_forward(_ptr(value), _ptr(spatial_shapes), _ptr(level_start_index),
-                                         _ptr(sampling_locations), _ptr(attention_weights), N, S, M, D, Lq, L, P,
-                                         _ptr(out), _stream())
-    _lib.check(rc, "df3d_ms_deform_attn_forward")
+    lib.df3d_ms_deform_attn_forward(_ptr(value), _ptr(spatial_shapes), _ptr(level_start_index),
+                                    _ptr(sampling_locations), _ptr(attention_weights), N, S, M, D, Lq, L, P,
+                                    _ptr(out), _stream())
     return out
 
 
@@ -2285,11 +2240,11 @@ def msda_backward_plan(N, S, M, D, Lq, L, P, level_hw, level_start, mode=None):
     if len(keep_hw) < 2 * L or len(keep_st) < L:
         raise ValueError("level_hw / level_start must hold %d levels" % L)
     lib = _lib.load()
-    code = int(lib.df3d_ms_deform_attn_backward_plan(int(N), int(S), int(M), int(D), int(Lq), int(L), int(P), hw, st,
-                                                     _MSDA_BWD_MODES[mode]))
-    if code >= 0:
-        return _MSDA_BWD_PLANS[code]
-    why = lib.df3d_last_error()
+    try:
+        return _MSDA_BWD_PLANS[lib.df3d_ms_deform_attn_backward_plan(int(N), int(S), int(M), int(D), int(Lq), int(L), int(P), hw, st,
+                                                                     _MSDA_BWD_MODES[mode])]
+    except _lib.Df3dError:                  # a refusal: the library names the limit
+        why = lib.df3d_last_error()
     why = why.decode() if why else "shape not served"
     if torch.is_deterministic_algorithms_warn_only_enabled() and os.environ.get("DF3D_MSDA_BWD") is None:
         if not _msda_bwd_warned:
@@ -2323,10 +2278,9 @@ def ms_deform_attn_backward(value, spatial_shapes, level_start_index, sampling_l
         gl = torch.empty_like(sampling_locations)
         ga = torch.empty_like(attention_weights)
         ws = torch.empty((nbytes,), dtype=torch.uint8, device=value.device)
-        rc = lib.df3d_ms_deform_attn_backward_f64(_ptr(value), _ptr(spatial_shapes), _ptr(level_start_index),
-                                                  _ptr(sampling_locations), _ptr(attention_weights), _ptr(grad_output), N, S, M,
-                                                  D, Lq, L, P, _ptr(gv), _ptr(gl), _ptr(ga), _ptr(ws), nbytes, _stream())
-        _lib.check(rc, "df3d_ms_deform_attn_backward_f64")
+        lib.df3d_ms_deform_attn_backward_f64(_ptr(value), _ptr(spatial_shapes), _ptr(level_start_index),
+                                             _ptr(sampling_locations), _ptr(attention_weights), _ptr(grad_output), N, S, M,
+                                             D, Lq, L, P, _ptr(gv), _ptr(gl), _ptr(ga), _ptr(ws), nbytes, _stream())
         return gv, gl, ga
     for t, name in ((value, "value"), (sampling_locations, "sampling_locations"), (attention_weights, "attention_weights"),
                     (grad_output, "grad_output")):
@@ -2353,11 +2307,10 @@ def ms_deform_attn_backward(value, spatial_shapes, level_start_index, sampling_l
         ws = torch.empty((nbytes,), dtype=torch.uint8, device=value.device)
         slabs = torch.empty((int(lib.df3d_ms_deform_attn_backward_binned_slab_bytes(N, M, D, Lq, P, H, W)) // 4,),
                             dtype=torch.float32, device=value.device)
-        rc = lib.df3d_ms_deform_attn_backward_binned(_ptr(value), _ptr(spatial_shapes), _ptr(level_start_index),
-                                                     _ptr(sampling_locations), _ptr(attention_weights), _ptr(grad_output), N, M,
-                                                     D, Lq, P, H, W, _ptr(gv), _ptr(gl), _ptr(ga), _ptr(ws), nbytes, _ptr(slabs),
-                                                     _stream())
-        _lib.check(rc, "df3d_ms_deform_attn_backward_binned")
+        lib.df3d_ms_deform_attn_backward_binned(_ptr(value), _ptr(spatial_shapes), _ptr(level_start_index),
+                                                _ptr(sampling_locations), _ptr(attention_weights), _ptr(grad_output), N, M,
+                                                D, Lq, P, H, W, _ptr(gv), _ptr(gl), _ptr(ga), _ptr(ws), nbytes, _ptr(slabs),
+                                                _stream())
         return gv, gl, ga
     if plan != "atomic":
         # several levels / heads of 32 or 64 channels / the ordered sum: bins of (level, tile, head)
@@ -2369,16 +2322,14 @@ def ms_deform_attn_backward(value, spatial_shapes, level_start_index, sampling_l
         ws = torch.empty((nbytes,), dtype=torch.uint8, device=value.device)
         slabs = torch.empty((int(lib.df3d_ms_deform_attn_backward_binned_ml_slab_bytes(N, M, D, Lq, L, P, hw)) // 4,),
                             dtype=torch.float32, device=value.device)
-        rc = lib.df3d_ms_deform_attn_backward_binned_ml(_ptr(value), _ptr(spatial_shapes), _ptr(level_start_index),
-                                                        _ptr(sampling_locations), _ptr(attention_weights), _ptr(grad_output), hw, st,
-                                                        N, M, D, Lq, L, P, ordered, _ptr(gv), _ptr(gl), _ptr(ga), _ptr(ws), nbytes,
-                                                        _ptr(slabs), _stream())
-        _lib.check(rc, "df3d_ms_deform_attn_backward_binned_ml")
+        lib.df3d_ms_deform_attn_backward_binned_ml(_ptr(value), _ptr(spatial_shapes), _ptr(level_start_index),
+                                                   _ptr(sampling_locations), _ptr(attention_weights), _ptr(grad_output), hw, st,
+                                                   N, M, D, Lq, L, P, ordered, _ptr(gv), _ptr(gl), _ptr(ga), _ptr(ws), nbytes,
+                                                   _ptr(slabs), _stream())
         return gv, gl, ga
-    rc = lib.df3d_ms_deform_attn_backward(_ptr(value), _ptr(spatial_shapes), _ptr(level_start_index),
-                                          _ptr(sampling_locations), _ptr(attention_weights), _ptr(grad_output), N, S, M,
-                                          D, Lq, L, P, _ptr(gv), _ptr(gl), _ptr(ga), _stream())
-    _lib.check(rc, "df3d_ms_deform_attn_backward")
+    lib.df3d_ms_deform_attn_backward(_ptr(value), _ptr(spatial_shapes), _ptr(level_start_index),
+                                     _ptr(sampling_locations), _ptr(attention_weights), _ptr(grad_output), N, S, M,
+                                     D, Lq, L, P, _ptr(gv), _ptr(gl), _ptr(ga), _stream())
     return gv, gl, ga
 
 
@@ -2407,11 +2358,9 @@ def ms_deform_attn_fused(value, spatial_shapes, level_start_index, ref_xy, offse
         bstride = int(image_bias.stride(0))
     out = torch.empty((N, Lq, M * D), dtype=torch.float32, device=value.device)
     fn = lib.df3d_ms_deform_attn_fused_bf16 if value.dtype == torch.bfloat16 else lib.df3d_ms_deform_attn_fused
-    rc = fn(_ptr(value), int(value.stride(1)), _ptr(spatial_shapes),
-                                       _ptr(level_start_index), _ptr(ref_xy), _ptr(offsets), _ptr(logits),
-                                       _ptr(pixel_scale), _ptr(image_bias), bstride, N, S, M, D,
-                                       Lq, int(n_levels), int(n_points), _ptr(out), _stream())
-    _lib.check(rc, "df3d_ms_deform_attn_fused")
+    fn(_ptr(value), int(value.stride(1)), _ptr(spatial_shapes), _ptr(level_start_index), _ptr(ref_xy), _ptr(offsets),
+       _ptr(logits), _ptr(pixel_scale), _ptr(image_bias), bstride, N, S, M, D, Lq, int(n_levels), int(n_points), _ptr(out),
+       _stream())
     return out
 
 
@@ -2427,15 +2376,13 @@ def groupnorm_fold(u, gate, conv_bias, gn, weight, bias):
     if gate is not None:
         _chk(gate, torch.float32, "gate")
     mom = torch.empty((N, C, 2), dtype=torch.float64, device=u.device)
-    rc = lib.df3d_scaled_moments(_ptr(u), int(u.stride(0)), int(u.stride(1)), _ptr(gate), N, S, C, _ptr(mom),
-                                 _stream())
-    _lib.check(rc, "df3d_scaled_moments")
+    lib.df3d_scaled_moments(_ptr(u), int(u.stride(0)), int(u.stride(1)), _ptr(gate), N, S, C, _ptr(mom),
+                            _stream())
     Wf = torch.empty((N, O, C), dtype=torch.float32, device=u.device)
     cf = torch.empty((N, O), dtype=torch.float32, device=u.device)
-    rc = lib.df3d_groupnorm_fold(_ptr(mom), _ptr(conv_bias), _ptr(gn.weight), _ptr(gn.bias), float(gn.eps), N, S, C,
-                                 int(gn.num_groups), _ptr(weight.contiguous()), _ptr(bias), O, _ptr(Wf), _ptr(cf),
-                                 _stream())
-    _lib.check(rc, "df3d_groupnorm_fold")
+    lib.df3d_groupnorm_fold(_ptr(mom), _ptr(conv_bias), _ptr(gn.weight), _ptr(gn.bias), float(gn.eps), N, S, C,
+                            int(gn.num_groups), _ptr(weight.contiguous()), _ptr(bias), O, _ptr(Wf), _ptr(cf),
+                            _stream())
     return Wf, cf
 
 
@@ -2454,8 +2401,7 @@ def ffn_pack(w1, w2):
         raise _lib.Df3dError("fused FFN serves d_model 64 / 128, d_ffn %% 128 == 0 (got %s, %s)" % (tuple(w1.shape),
                                                                                               tuple(w2.shape)))
     packed = torch.empty((nbytes,), dtype=torch.uint8, device=w1.device)
-    rc = lib.df3d_ffn_pack(_ptr(w1), _ptr(w2), d_model, d_ffn, _ptr(packed), _stream())
-    _lib.check(rc, "df3d_ffn_pack")
+    lib.df3d_ffn_pack(_ptr(w1), _ptr(w2), d_model, d_ffn, _ptr(packed), _stream())
     return packed
 
 
@@ -2475,13 +2421,13 @@ def ffn_fused(x, packed, b1, b2, d_ffn, residual=None, ln_weight=None, ln_bias=N
         _chk(residual, torch.float32, "residual")
     C = x.shape[-1]
     out = torch.empty_like(x)
-    rc = lib.df3d_ffn_fused(_ptr(x), x.numel() // C, C, int(d_ffn), _ptr(packed), _ptr(b1), _ptr(b2), _ptr(residual),
-                            _ptr(ln_weight), _ptr(ln_bias), float(eps), _ptr(out), _stream())
-    _lib.check(rc, "df3d_ffn_fused")
+    lib.df3d_ffn_fused(_ptr(x), x.numel() // C, C, int(d_ffn), _ptr(packed), _ptr(b1), _ptr(b2), _ptr(residual),
+                       _ptr(ln_weight), _ptr(ln_bias), float(eps), _ptr(out), _stream())
     return out
 
 
 class _FfnJob(ctypes.Structure):
+    _c_name_ = "df3d_ffn_job"
     _fields_ = [("x", ctypes.c_void_p), ("rows", ctypes.c_longlong), ("packed", ctypes.c_void_p), ("b1", ctypes.c_void_p),
                 ("b2", ctypes.c_void_p), ("residual", ctypes.c_void_p), ("ln_weight", ctypes.c_void_p),
                 ("ln_bias", ctypes.c_void_p), ("eps", ctypes.c_float), ("out", ctypes.c_void_p)]
@@ -2505,8 +2451,7 @@ def ffn_fused_jobs(jobs, d_ffn):
         arr[i].ln_bias = j["ln_bias"].data_ptr() if j.get("ln_bias") is not None else None
         arr[i].eps = float(j.get("eps", 1e-5))
         arr[i].out = out.data_ptr()
-    rc = lib.df3d_ffn_fused_jobs(ctypes.byref(arr), len(jobs), int(C), int(d_ffn), _stream())
-    _lib.check(rc, "df3d_ffn_fused_jobs")
+    lib.df3d_ffn_fused_jobs(ctypes.byref(arr), len(jobs), int(C), int(d_ffn), _stream())
     return outs
 
 
@@ -2524,8 +2469,7 @@ def imgproj_pack(wcat):
         raise _lib.Df3dError("image projection kernel serves 256 input channels and <= 144 rows (got %s)" %
                              (tuple(wcat.shape),))
     packed = torch.empty((nbytes,), dtype=torch.uint8, device=wcat.device)
-    rc = lib.df3d_imgproj_pack(_ptr(wcat), rows, cin, _ptr(packed), _stream())
-    _lib.check(rc, "df3d_imgproj_pack")
+    lib.df3d_imgproj_pack(_ptr(wcat), rows, cin, _ptr(packed), _stream())
     return packed
 
 
@@ -2539,12 +2483,10 @@ def imgproj_split(img_ptrs, nimg, cin, S, packed, pixrow=None, pixrow_total=0):
     if pixrow is not None and pixrow_total > 0:
         _chk(pixrow, torch.int32, "pixrow")
         compact = torch.empty((int(pixrow_total), cin), dtype=torch.float32, device=packed.device)
-        rc = lib.df3d_imgproj_split_compact(_ptr(img_ptrs), nimg, cin, S, _ptr(packed), _ptr(u), _ptr(gate), _ptr(pixrow),
-                                            _ptr(compact), _stream())
-        _lib.check(rc, "df3d_imgproj_split_compact")
+        lib.df3d_imgproj_split_compact(_ptr(img_ptrs), nimg, cin, S, _ptr(packed), _ptr(u), _ptr(gate), _ptr(pixrow),
+                                       _ptr(compact), _stream())
         return u, gate, compact
-    rc = lib.df3d_imgproj_split(_ptr(img_ptrs), nimg, cin, S, _ptr(packed), _ptr(u), _ptr(gate), _stream())
-    _lib.check(rc, "df3d_imgproj_split")
+    lib.df3d_imgproj_split(_ptr(img_ptrs), nimg, cin, S, _ptr(packed), _ptr(u), _ptr(gate), _stream())
     return u, gate
 
 
@@ -2566,10 +2508,9 @@ def value_fold_gemm(u_split, att, conv_bias, gn, W, wb, bf16=False, stream=None)
     cf = torch.empty((nimg, 256), dtype=torch.float32, device=dev)
     value = torch.empty((nimg, S, 256), dtype=torch.bfloat16 if bf16 else torch.float32, device=dev)
     fn = lib.df3d_value_fold_gemm_bf16 if bf16 else lib.df3d_value_fold_gemm
-    rc = fn(_ptr(u_split), _ptr(att), nimg, S, _ptr(conv_bias), _ptr(gn.weight), _ptr(gn.bias), float(gn.eps),
-            int(gn.num_groups), _ptr(W), _ptr(wb), _ptr(mom), _ptr(pw), _ptr(cf), _ptr(value),
-            _stream() if stream is None else _lib.StreamArg(stream.cuda_stream))
-    _lib.check(rc, "df3d_value_fold_gemm")
+    fn(_ptr(u_split), _ptr(att), nimg, S, _ptr(conv_bias), _ptr(gn.weight), _ptr(gn.bias), float(gn.eps),
+       int(gn.num_groups), _ptr(W), _ptr(wb), _ptr(mom), _ptr(pw), _ptr(cf), _ptr(value),
+       _stream() if stream is None else _lib.StreamArg(stream.cuda_stream))
     if stream is not None:
         value._df3d_keep = (mom, pw)            # scratch of kernels that may still be queued on `stream`
     return value, cf
@@ -2582,9 +2523,8 @@ def rows_groupnorm(x, gn):
     N, Q, C = x.shape
     stats = torch.empty((N, gn.num_groups, 2), dtype=torch.float64, device=x.device)
     out = torch.empty_like(x)
-    rc = lib.df3d_rows_groupnorm(_ptr(x), N, Q, C, int(gn.num_groups), _ptr(gn.weight), _ptr(gn.bias), float(gn.eps),
-                                 _ptr(stats), _ptr(out), _stream())
-    _lib.check(rc, "df3d_rows_groupnorm")
+    lib.df3d_rows_groupnorm(_ptr(x), N, Q, C, int(gn.num_groups), _ptr(gn.weight), _ptr(gn.bias), float(gn.eps),
+                            _ptr(stats), _ptr(out), _stream())
     return out
 
 
@@ -2595,8 +2535,7 @@ def actr_prep(q, qi, pos):
         _chk(t, torch.float32, name)
     A, Bw = torch.empty_like(q), torch.empty_like(q)
     C = q.shape[-1]
-    rc = lib.df3d_actr_prep(_ptr(q), _ptr(qi), _ptr(pos), q.numel() // C, C, _ptr(A), _ptr(Bw), _stream())
-    _lib.check(rc, "df3d_actr_prep")
+    lib.df3d_actr_prep(_ptr(q), _ptr(qi), _ptr(pos), q.numel() // C, C, _ptr(A), _ptr(Bw), _stream())
     return A, Bw
 
 
@@ -2612,13 +2551,11 @@ def add_layernorm(x, y, weight, bias, eps, want_split=False):
     if want_split:
         rows = x.numel() // C
         sp = torch.empty((rows, 4 * C), dtype=torch.uint8, device=x.device)
-        rc = lib.df3d_add_layernorm_split(_ptr(x), _ptr(y), _ptr(weight), _ptr(bias), float(eps), rows, C, _ptr(out),
-                                          _ptr(sp), _stream())
-        _lib.check(rc, "df3d_add_layernorm_split")
+        lib.df3d_add_layernorm_split(_ptr(x), _ptr(y), _ptr(weight), _ptr(bias), float(eps), rows, C, _ptr(out),
+                                     _ptr(sp), _stream())
         return out, sp
-    rc = lib.df3d_add_layernorm(_ptr(x), _ptr(y), _ptr(weight), _ptr(bias), float(eps), x.numel() // C, C, _ptr(out),
-                                _stream())
-    _lib.check(rc, "df3d_add_layernorm")
+    lib.df3d_add_layernorm(_ptr(x), _ptr(y), _ptr(weight), _ptr(bias), float(eps), x.numel() // C, C, _ptr(out),
+                           _stream())
     return out
 
 
@@ -2641,7 +2578,7 @@ class _ReluDropout(torch.autograd.Function):
     def forward(ctx, h, p, seed):
         lib = _lib.load()
         fn = lib.df3d_relu_dropout_bf16 if h.dtype == torch.bfloat16 else lib.df3d_relu_dropout
-        _lib.check(fn(_ptr(h), h.numel(), float(p), int(seed), _stream()), "df3d_relu_dropout")
+        fn(_ptr(h), h.numel(), float(p), int(seed), _stream())
         ctx.mark_dirty(h)
         ctx.save_for_backward(h)
         ctx.p = float(p)
@@ -2654,7 +2591,7 @@ class _ReluDropout(torch.autograd.Function):
         out = torch.empty_like(grad)
         lib = _lib.load()
         fn = lib.df3d_relu_dropout_backward_bf16 if h.dtype == torch.bfloat16 else lib.df3d_relu_dropout_backward
-        _lib.check(fn(_ptr(h), _ptr(grad), h.numel(), ctx.p, _ptr(out), _stream()), "df3d_relu_dropout_backward")
+        fn(_ptr(h), _ptr(grad), h.numel(), ctx.p, _ptr(out), _stream())
         return out, None, None
 
 
@@ -2679,9 +2616,8 @@ class _DropoutAddLayerNorm(torch.autograd.Function):
         rows = x.numel() // C
         out, xhat = torch.empty_like(x), torch.empty_like(x)
         rstd = torch.empty((rows,), dtype=torch.float32, device=x.device)
-        rc = _lib.load().df3d_dropout_add_layernorm(_ptr(x), _ptr(y), _ptr(weight), _ptr(bias), float(eps), float(p), int(seed),
-                                                    rows, C, _ptr(out), _ptr(xhat), _ptr(rstd), _stream())
-        _lib.check(rc, "df3d_dropout_add_layernorm")
+        _lib.load().df3d_dropout_add_layernorm(_ptr(x), _ptr(y), _ptr(weight), _ptr(bias), float(eps), float(p), int(seed),
+                                               rows, C, _ptr(out), _ptr(xhat), _ptr(rstd), _stream())
         ctx.save_for_backward(xhat, rstd, weight)
         ctx.p, ctx.seed = float(p), int(seed)
         ctx.has_y = y is not None                      # (None: LayerNorm(x) alone, `layernorm_rows`)
@@ -2696,10 +2632,9 @@ class _DropoutAddLayerNorm(torch.autograd.Function):
         # the kernel drops nothing -- and writes no d y -- where its threshold rounds to 0 (0 < p < 2^-24): d y = d x there
         dy = torch.empty_like(xhat) if _dropout_threshold(ctx.p) and ctx.has_y else None
         dwb = torch.zeros((2, C), dtype=torch.float32, device=xhat.device)
-        rc = _lib.load().df3d_dropout_add_layernorm_backward(_ptr(grad), _ptr(xhat), _ptr(rstd), _ptr(weight), ctx.p, ctx.seed,
-                                                             xhat.numel() // C, C, _ptr(dx), _ptr(dy), _ptr(dwb[0]),
-                                                             _ptr(dwb[1]), _stream())
-        _lib.check(rc, "df3d_dropout_add_layernorm_backward")
+        _lib.load().df3d_dropout_add_layernorm_backward(_ptr(grad), _ptr(xhat), _ptr(rstd), _ptr(weight), ctx.p, ctx.seed,
+                                                        xhat.numel() // C, C, _ptr(dx), _ptr(dy), _ptr(dwb[0]),
+                                                        _ptr(dwb[1]), _stream())
         return dx, ((dy if dy is not None else dx) if ctx.has_y else None), dwb[0], dwb[1], None, None, None
 
 
@@ -2724,9 +2659,8 @@ def bigate_sum(q, qi, wb, bb, wa, ba):
     _chk(qi, torch.float32, "qi")
     C = q.shape[-1]
     qo, qio = torch.empty_like(q), torch.empty_like(qi)
-    rc = lib.df3d_bigate_sum(_ptr(q), _ptr(qi), _ptr(wb), _ptr(bb), _ptr(wa), _ptr(ba), q.numel() // C, C, _ptr(qo),
-                             _ptr(qio), _stream())
-    _lib.check(rc, "df3d_bigate_sum")
+    lib.df3d_bigate_sum(_ptr(q), _ptr(qi), _ptr(wb), _ptr(bb), _ptr(wa), _ptr(ba), q.numel() // C, C, _ptr(qo),
+                        _ptr(qio), _stream())
     return qo, qio
 
 
@@ -2737,8 +2671,7 @@ def furthest_point_sample(xyz, m):
     B, N, _ = xyz.shape
     idx = torch.empty((B, m), dtype=torch.int32, device=xyz.device)
     temp = torch.empty((B, N), dtype=torch.float32, device=xyz.device)
-    rc = lib.df3d_furthest_point_sample(_ptr(xyz), B, N, int(m), _ptr(temp), _ptr(idx), _stream())
-    _lib.check(rc, "df3d_furthest_point_sample")
+    lib.df3d_furthest_point_sample(_ptr(xyz), B, N, int(m), _ptr(temp), _ptr(idx), _stream())
     return idx
 
 
@@ -2749,9 +2682,8 @@ def ball_query(min_radius, max_radius, nsample, xyz, new_xyz):
     B, N, _ = xyz.shape
     m = new_xyz.shape[1]
     idx = torch.empty((B, m, nsample), dtype=torch.int32, device=xyz.device)
-    rc = lib.df3d_ball_query(_ptr(new_xyz), _ptr(xyz), B, N, m, float(min_radius), float(max_radius), int(nsample),
-                             _ptr(idx), _stream())
-    _lib.check(rc, "df3d_ball_query")
+    lib.df3d_ball_query(_ptr(new_xyz), _ptr(xyz), B, N, m, float(min_radius), float(max_radius), int(nsample),
+                        _ptr(idx), _stream())
     return idx
 
 
@@ -2762,8 +2694,7 @@ def _group_points(features, idx):
     B, C, N = features.shape
     _, npoint, nsample = idx.shape
     out = torch.empty((B, C, npoint, nsample), dtype=torch.float32, device=features.device)
-    rc = lib.df3d_group_points(_ptr(features), _ptr(idx), B, C, N, npoint, nsample, _ptr(out), _stream())
-    _lib.check(rc, "df3d_group_points")
+    lib.df3d_group_points(_ptr(features), _ptr(idx), B, C, N, npoint, nsample, _ptr(out), _stream())
     return out
 
 
@@ -2774,8 +2705,7 @@ def _gather_points(features, idx):
     B, C, N = features.shape
     npoint = idx.shape[1]
     out = torch.empty((B, C, npoint), dtype=torch.float32, device=features.device)
-    rc = lib.df3d_gather_points(_ptr(features), _ptr(idx), B, C, N, npoint, _ptr(out), _stream())
-    _lib.check(rc, "df3d_gather_points")
+    lib.df3d_gather_points(_ptr(features), _ptr(idx), B, C, N, npoint, _ptr(out), _stream())
     return out
 
 
@@ -2797,8 +2727,7 @@ class _GroupPoints(torch.autograd.Function):
         B, C = grad.shape[:2]
         out = torch.zeros((B, C, ctx.n), dtype=torch.float32, device=grad.device)
         nsample = idx.shape[2] if idx.dim() == 3 else 1
-        rc = _lib.load().df3d_group_points_grad(_ptr(grad), _ptr(idx), B, C, ctx.n, idx.shape[1], nsample, _ptr(out), _stream())
-        _lib.check(rc, "df3d_group_points_grad")
+        _lib.load().df3d_group_points_grad(_ptr(grad), _ptr(idx), B, C, ctx.n, idx.shape[1], nsample, _ptr(out), _stream())
         return out, None
 
 
@@ -2826,9 +2755,8 @@ def head_final_conv_backward(acts, grad_out, batch, H, W, groups, weights, out_c
     _chk(out_cols, torch.int32, "out_cols")
     g_a = torch.zeros_like(acts) if (want_acts and acts.shape[1] > groups * 64) else (torch.empty_like(acts) if want_acts else None)
     g_w = torch.empty_like(weights) if want_weights else None
-    rc = lib.df3d_head_final_conv_backward(_ptr(acts), acts.shape[1], _ptr(grad_out), grad_out.shape[1], int(batch), int(H),
-                                           int(W), int(groups), _ptr(weights), _ptr(out_cols), _ptr(g_a), _ptr(g_w), _stream())
-    _lib.check(rc, "df3d_head_final_conv_backward")
+    lib.df3d_head_final_conv_backward(_ptr(acts), acts.shape[1], _ptr(grad_out), grad_out.shape[1], int(batch), int(H),
+                                      int(W), int(groups), _ptr(weights), _ptr(out_cols), _ptr(g_a), _ptr(g_w), _stream())
     return g_a, g_w
 
 
@@ -2852,9 +2780,8 @@ class BatchNormRowsFunction(torch.autograd.Function):
         y = torch.empty_like(x)
         w = weight.detach().float().contiguous() if weight is not None else None
         b = bias.detach().float().contiguous() if bias is not None else None
-        rc = lib.df3d_bn_rows_forward(_ptr(x), n, c, _ptr(w), _ptr(b), float(eps), float(momentum), int(bool(relu)),
-                                      _ptr(running_mean), _ptr(running_var), _ptr(sums), _ptr(saved), _ptr(y), _stream())
-        _lib.check(rc, "df3d_bn_rows_forward")
+        lib.df3d_bn_rows_forward(_ptr(x), n, c, _ptr(w), _ptr(b), float(eps), float(momentum), int(bool(relu)),
+                                 _ptr(running_mean), _ptr(running_var), _ptr(sums), _ptr(saved), _ptr(y), _stream())
         ctx.save_for_backward(x, saved)
         ctx.relu, ctx.sums = bool(relu), sums
         ctx.has = (weight is not None, bias is not None)
@@ -2870,9 +2797,8 @@ class BatchNormRowsFunction(torch.autograd.Function):
         dx = torch.empty_like(x)
         dw = torch.empty((c,), dtype=torch.float32, device=x.device) if ctx.has[0] else None
         db = torch.empty((c,), dtype=torch.float32, device=x.device) if ctx.has[1] else None
-        rc = lib.df3d_bn_rows_backward(_ptr(x), _ptr(dy), n, c, _ptr(saved), int(ctx.relu), _ptr(ctx.sums), _ptr(dx),
-                                       _ptr(dw), _ptr(db), _stream())
-        _lib.check(rc, "df3d_bn_rows_backward")
+        lib.df3d_bn_rows_backward(_ptr(x), _ptr(dy), n, c, _ptr(saved), int(ctx.relu), _ptr(ctx.sums), _ptr(dx),
+                                  _ptr(dw), _ptr(db), _stream())
         return dx, dw, db, None, None, None, None, None
 
 
@@ -2916,12 +2842,10 @@ def group_attention(qkv, tokens, groups, heads, split_only=False):
         return _GroupAttention.apply(qkv, int(tokens), int(groups), int(heads))
     if split_only:                                 # split rows for the out-projection, no fp32 copy
         sp = torch.empty((tokens * groups, 4 * C), dtype=torch.uint8, device=qkv.device)
-        rc = lib.df3d_group_attention_split(_ptr(qkv), int(tokens), int(groups), int(heads), 16, None, _ptr(sp), _stream())
-        _lib.check(rc, "df3d_group_attention_split")
+        lib.df3d_group_attention_split(_ptr(qkv), int(tokens), int(groups), int(heads), 16, None, _ptr(sp), _stream())
         return sp
     out = torch.empty((tokens * groups, C), dtype=torch.float32, device=qkv.device)
-    rc = lib.df3d_group_attention(_ptr(qkv), int(tokens), int(groups), int(heads), 16, _ptr(out), _stream())
-    _lib.check(rc, "df3d_group_attention")
+    lib.df3d_group_attention(_ptr(qkv), int(tokens), int(groups), int(heads), 16, _ptr(out), _stream())
     return out
 
 
@@ -2943,8 +2867,7 @@ class _GroupAttention(torch.autograd.Function):
         tokens, groups, heads = ctx.shape
         grad = _chk(grad.contiguous(), torch.float32, "grad")
         out = torch.empty_like(qkv)
-        rc = _lib.load().df3d_group_attention_backward(_ptr(qkv), _ptr(grad), tokens, groups, heads, 16, _ptr(out), _stream())
-        _lib.check(rc, "df3d_group_attention_backward")
+        _lib.load().df3d_group_attention_backward(_ptr(qkv), _ptr(grad), tokens, groups, heads, 16, _ptr(out), _stream())
         return out, None, None, None
 
 
@@ -2995,9 +2918,8 @@ def voxel_image_sample(indices, batch, voxel_stride, voxel_size_zyx, range_min_z
     h, w = int(hw[0]), int(hw[1])
     sy = float(np.float32(Hin) / np.float32(h))
     sx = float(np.float32(Win) / np.float32(w))
-    rc = lib.df3d_voxel_image_sample(_ptr(indices), n, int(batch), float(voxel_stride), vs, r0, _ptr(aug), _ptr(lidar2img), _ptr(fmap),
-                                     C, Hin, Win, h, w, sy, sx, _ptr(add), _ptr(rows), _ptr(out), _ptr(uv), _ptr(grid), _stream())
-    _lib.check(rc, "df3d_voxel_image_sample")
+    lib.df3d_voxel_image_sample(_ptr(indices), n, int(batch), float(voxel_stride), vs, r0, _ptr(aug), _ptr(lidar2img), _ptr(fmap),
+                                C, Hin, Win, h, w, sy, sx, _ptr(add), _ptr(rows), _ptr(out), _ptr(uv), _ptr(grid), _stream())
     return out, uv
 
 
@@ -3043,9 +2965,8 @@ def lt_layer(x, packed, vec, heads, ffn, eps1, eps2, group_major=False):
     else:
         L, G, C = x.shape
     out = torch.empty_like(x)
-    rc = lib.df3d_lt_layer(_ptr(x), int(L), int(G), int(C), int(heads), int(ffn), int(bool(group_major)), _ptr(packed), _ptr(vec),
-                           float(eps1), float(eps2), _ptr(out), _stream())
-    _lib.check(rc, "df3d_lt_layer")
+    lib.df3d_lt_layer(_ptr(x), int(L), int(G), int(C), int(heads), int(ffn), int(bool(group_major)), _ptr(packed), _ptr(vec),
+                      float(eps1), float(eps2), _ptr(out), _stream())
     return out
 
 
@@ -3075,9 +2996,8 @@ def lt_layer_gather(points, sel, gxyz, groups, packed_pe, vec_pe, eps1, eps2):
     if points.shape[1] != 64 or sel.numel() != 32 * groups or gxyz.shape != (32 * groups, 3):
         raise _lib.Df3dError("lt_layer_gather: points [rows, 64], sel [32 * groups], gxyz [32 * groups, 3]")
     out = torch.empty((32, groups, 64), dtype=torch.float32, device=points.device)
-    rc = lib.df3d_lt_layer_gather(_ptr(points), _ptr(sel), _ptr(gxyz), int(groups), _ptr(packed_pe), _ptr(vec_pe), float(eps1),
-                                  float(eps2), _ptr(out), _stream())
-    _lib.check(rc, "df3d_lt_layer_gather")
+    lib.df3d_lt_layer_gather(_ptr(points), _ptr(sel), _ptr(gxyz), int(groups), _ptr(packed_pe), _ptr(vec_pe), float(eps1),
+                             float(eps2), _ptr(out), _stream())
     return out
 
 
@@ -3093,9 +3013,8 @@ def lt_layer_scatter(x, packed, vec, eps1, eps2, dst, points):
     L, G, C = x.shape
     if L != 32 or C != 64 or dst.numel() != L * G or points.shape[1] != 64:
         raise _lib.Df3dError("lt_layer_scatter: x [32, groups, 64], dst [32 * groups], points [rows, 64]")
-    rc = lib.df3d_lt_layer_scatter(_ptr(x), int(G), _ptr(packed), _ptr(vec), float(eps1), float(eps2), _ptr(dst), _ptr(points),
-                                   _stream())
-    _lib.check(rc, "df3d_lt_layer_scatter")
+    lib.df3d_lt_layer_scatter(_ptr(x), int(G), _ptr(packed), _ptr(vec), float(eps1), float(eps2), _ptr(dst), _ptr(points),
+                              _stream())
     return points
 
 
@@ -3133,9 +3052,8 @@ def pe_gather_add(feat, sel, xyz, w0, b0, w1, b1):
     _chk(sel, torch.int64, "sel")
     rows, C, H1 = sel.shape[0], feat.shape[1], w0.shape[0]
     out = torch.empty((rows, C), dtype=torch.float32, device=feat.device)
-    rc = lib.df3d_pe_gather_add(_ptr(feat), _ptr(sel), _ptr(xyz), _ptr(w0), _ptr(b0), _ptr(w1), _ptr(b1), rows, C, H1,
-                                _ptr(out), _stream())
-    _lib.check(rc, "df3d_pe_gather_add")
+    lib.df3d_pe_gather_add(_ptr(feat), _ptr(sel), _ptr(xyz), _ptr(w0), _ptr(b0), _ptr(w1), _ptr(b1), rows, C, H1,
+                           _ptr(out), _stream())
     return out
 
 
@@ -3229,8 +3147,7 @@ class _ChannelFirstLinear(torch.autograd.Function):
             if weight.shape[0] == 1 and x.dtype == torch.float32 and x.is_contiguous() and g.is_contiguous():
                 lib = _lib.load()
                 part = torch.empty((N, Cin), dtype=torch.float32, device=x.device)
-                _lib.check(lib.df3d_chanfirst_dot(_ptr(x), _ptr(g), int(N), int(Cin), int(S), _ptr(part), _stream()),
-                           "df3d_chanfirst_dot")
+                lib.df3d_chanfirst_dot(_ptr(x), _ptr(g), int(N), int(Cin), int(S), _ptr(part), _stream())
                 gw = part.sum(0, keepdim=True)
             else:
                 gw = torch.bmm(x, g.transpose(1, 2)).sum(0).t()
@@ -3302,18 +3219,16 @@ def voxel_query(max_range, radius, nsample, xyz, new_xyz, new_coords, voxel2poin
     if isinstance(voxel2point, GridDirectory):
         g = voxel2point
         shp_p, keep2 = _lib.int3(g.shape)
-        rc = lib.df3d_voxel_query(_ptr(g.blob), _ptr(g.perm), g.batch, shp_p, _ptr(xyz), xyz.shape[0], _ptr(new_xyz),
-                                  _ptr(new_coords), M, rng_p, float(radius), int(nsample), _ptr(idx), _stream())
-        _lib.check(rc, "df3d_voxel_query")
+        lib.df3d_voxel_query(_ptr(g.blob), _ptr(g.perm), g.batch, shp_p, _ptr(xyz), xyz.shape[0], _ptr(new_xyz),
+                             _ptr(new_coords), M, rng_p, float(radius), int(nsample), _ptr(idx), _stream())
     else:
         _chk(voxel2point, torch.int32, "voxel2point_indices")
         if voxel2point.dim() != 4:
             raise _lib.Df3dError("voxel2point_indices must be [B, Z, Y, X]")
         shp_p, keep2 = _lib.int3(voxel2point.shape[1:])
-        rc = lib.df3d_voxel_query_dense(_ptr(voxel2point), voxel2point.shape[0], shp_p, _ptr(xyz), xyz.shape[0],
-                                        _ptr(new_xyz), _ptr(new_coords), M, rng_p, float(radius), int(nsample), _ptr(idx),
-                                        _stream())
-        _lib.check(rc, "df3d_voxel_query_dense")
+        lib.df3d_voxel_query_dense(_ptr(voxel2point), voxel2point.shape[0], shp_p, _ptr(xyz), xyz.shape[0],
+                                   _ptr(new_xyz), _ptr(new_coords), M, rng_p, float(radius), int(nsample), _ptr(idx),
+                                   _stream())
     return idx
 
 
@@ -3332,9 +3247,8 @@ def _group_points_stack(features, features_batch_cnt, idx, idx_batch_cnt):
     N, C = features.shape
     M, nsample = idx.shape
     out = torch.empty((M, C, nsample), dtype=torch.float32, device=features.device)
-    rc = _lib.load().df3d_group_points_stack(_ptr(features), _ptr(features_batch_cnt), _ptr(idx), _ptr(idx_batch_cnt),
-                                             features_batch_cnt.shape[0], M, C, nsample, N, _ptr(out), _stream())
-    _lib.check(rc, "df3d_group_points_stack")
+    _lib.load().df3d_group_points_stack(_ptr(features), _ptr(features_batch_cnt), _ptr(idx), _ptr(idx_batch_cnt),
+                                        features_batch_cnt.shape[0], M, C, nsample, N, _ptr(out), _stream())
     return out
 
 
@@ -3359,9 +3273,8 @@ def group_points_stack_backward(grad_out, idx, idx_batch_cnt, features_batch_cnt
             raise _lib.Df3dError("group_points_stack backward: no workspace size for M * nsample = %d (limit 2^31 - 1)"
                                  % (M * nsample))
         ws = torch.empty((wsb,), dtype=torch.uint8, device=grad_out.device)
-    rc = lib.df3d_group_points_stack_grad(_ptr(grad_out), _ptr(idx), _ptr(idx_batch_cnt), _ptr(features_batch_cnt),
-                                          features_batch_cnt.shape[0], M, C, N, nsample, _ptr(out), _ptr(ws), wsb, stream)
-    _lib.check(rc, "df3d_group_points_stack_grad")
+    lib.df3d_group_points_stack_grad(_ptr(grad_out), _ptr(idx), _ptr(idx_batch_cnt), _ptr(features_batch_cnt),
+                                     features_batch_cnt.shape[0], M, C, N, nsample, _ptr(out), _ptr(ws), wsb, stream)
     return out
 
 
@@ -3425,11 +3338,10 @@ def voxel_pool_fused(rows_in, xyz, grid, new_xyz, new_coords, max_range, radius,
     idx = torch.empty((M, int(nsample)), dtype=torch.int32, device=dev) if want_idx else None
     empty = torch.empty((M,), dtype=torch.uint8, device=dev) if want_idx else None
     shp_p, keep2 = _lib.int3(grid.shape)
-    rc = _lib.load().df3d_voxel_pool_fused(_ptr(rows_in), _ptr(xyz), xyz.shape[0], C, _ptr(grid.blob), _ptr(grid.perm),
-                                           grid.batch, shp_p, _ptr(new_xyz), _ptr(new_coords), M, rng_p, float(radius),
-                                           int(nsample), _ptr(w_pos), _POOL_METHODS[pool_method], _ptr(pooled), _ptr(idx),
-                                           _ptr(empty), _stream())
-    _lib.check(rc, "df3d_voxel_pool_fused")
+    _lib.load().df3d_voxel_pool_fused(_ptr(rows_in), _ptr(xyz), xyz.shape[0], C, _ptr(grid.blob), _ptr(grid.perm),
+                                      grid.batch, shp_p, _ptr(new_xyz), _ptr(new_coords), M, rng_p, float(radius),
+                                      int(nsample), _ptr(w_pos), _POOL_METHODS[pool_method], _ptr(pooled), _ptr(idx),
+                                      _ptr(empty), _stream())
     if want_idx:
         return pooled, idx, empty.bool()
     return pooled

@@ -25,10 +25,12 @@ MAX_PROJ = 4
 
 
 class _Project(ctypes.Structure):
+    _c_name_ = "df3d_head_project"
     _fields_ = [("layer", ctypes.c_int), ("scale_xyz", ctypes.c_float * 3), ("want_winner", ctypes.c_int)]
 
 
 class _Desc(ctypes.Structure):
+    _c_name_ = "df3d_frame_head_desc"
     _fields_ = [("batch", ctypes.c_int), ("point_channels", ctypes.c_int), ("points", ctypes.c_void_p),
                 ("num_points", ctypes.c_void_p), ("voxel_size", ctypes.c_float * 3), ("coors_range", ctypes.c_float * 6),
                 ("max_points", ctypes.c_int), ("max_voxels", ctypes.c_int), ("break_at_cap", ctypes.c_int),
@@ -43,6 +45,7 @@ class _Desc(ctypes.Structure):
 
 
 class _Out(ctypes.Structure):
+    _c_name_ = "df3d_frame_head_out"
     _fields_ = [("features", ctypes.c_void_p), ("coors", ctypes.c_void_p), ("n", ctypes.c_int), ("max_ne", ctypes.c_int),
                 ("grid_xy", ctypes.c_void_p * MAX_PROJ), ("mask", ctypes.c_void_p * MAX_PROJ),
                 ("point_inv", ctypes.c_void_p * MAX_PROJ), ("proj_n", ctypes.c_int * MAX_PROJ), ("pos", ctypes.c_void_p),
@@ -64,8 +67,7 @@ class Prepared(object):
         if self.geometry is not None:
             self.geometry.wait()
             if self.fusion is not None and "both" in self.fusion:
-                _lib.check(_lib.load().df3d_frame_head_image_wait(self.geometry.handle, _ops._stream()),
-                           "df3d_frame_head_image_wait")
+                _lib.load().df3d_frame_head_image_wait(self.geometry.handle, _ops._stream())
 
 
 class _Ticket(object):
@@ -166,9 +168,8 @@ class FrameHead(object):
         arena = t.slot.arena("geo", t.plan._geo_bytes, self.device)
         t.arena = arena
         handle = ctypes.c_void_p(0)
-        rc = self.lib.df3d_frame_head_submit(self.worker, ctypes.byref(t.job[0]), _ops._ptr(arena), arena.numel(),
-                                             ctypes.byref(handle))
-        _lib.check(rc, "df3d_frame_head_submit")
+        self.lib.df3d_frame_head_submit(self.worker, ctypes.byref(t.job[0]), _ops._ptr(arena), arena.numel(),
+                                        ctypes.byref(handle))
         t.handle = handle
 
     # ------------------------------------------------------------------ take
@@ -183,16 +184,18 @@ class FrameHead(object):
             views, out = (_View * nl)(), _Out()
             used, handle = ctypes.c_size_t(0), ctypes.c_void_p(0)
             t0 = time.perf_counter()
-            rc = self.lib.df3d_frame_head_wait(t.handle, views, ctypes.byref(out), ctypes.byref(used), ctypes.byref(handle))
-            self.stats["take_wait_s"] += time.perf_counter() - t0
-            t.handle = None
-            if rc == _lib.DF3D_ENOMEM and plan._geo_bytes < (64 << 30):
-                plan._geo_bytes = max(2 * plan._geo_bytes, int(used.value) + (64 << 20))
-                torch.cuda.synchronize(self.device)            # the failed attempt's kernels still write the small arena
-                self._submit(t)
-                continue
-            _lib.check(rc, "df3d_frame_head_wait")
-            break
+            try:
+                self.lib.df3d_frame_head_wait(t.handle, views, ctypes.byref(out), ctypes.byref(used), ctypes.byref(handle))
+                break
+            except _lib.Df3dError as e:
+                if e.rc != _lib.DF3D_ENOMEM or plan._geo_bytes >= (64 << 30):
+                    raise
+            finally:
+                self.stats["take_wait_s"] += time.perf_counter() - t0
+                t.handle = None
+            plan._geo_bytes = max(2 * plan._geo_bytes, int(used.value) + (64 << 20))
+            torch.cuda.synchronize(self.device)                # the failed attempt's kernels still write the small arena
+            self._submit(t)
         arena = t.arena
         base = arena.data_ptr()
 
@@ -250,11 +253,13 @@ class FrameHead(object):
     def close(self):
         if self.worker:
             self.drop_all()
-            self.lib.df3d_head_worker_destroy(self.worker)
-            self.worker = None
-            # the last job's kernels may still be writing the frame slots' arenas on the worker's stream (a stream the caching
-            # allocator knows nothing about): nothing may recycle that memory before they are done
-            torch.cuda.synchronize(self.device)
+            worker, self.worker = self.worker, None
+            try:
+                self.lib.df3d_head_worker_destroy(worker)
+            finally:
+                # the last job's kernels may still be writing the frame slots' arenas on the worker's stream (a stream the
+                # caching allocator knows nothing about): nothing may recycle that memory before they are done
+                torch.cuda.synchronize(self.device)
 
     def __del__(self):
         try:

@@ -5,7 +5,7 @@ import ctypes
 
 def _lib():
     from dualfusion import _lib
-    return _lib.load()
+    return _lib.bind(ctypes.CDLL(_lib.LIB_PATH), check=False)
 
 
 def test_workspace_size_is_nonzero_and_monotone():

@@ -16,7 +16,7 @@ def _lib():
     import __graft_entry__ as ge
     ge._load(os.path.join(ge.PKG, "csrc", "build.py"), "df3d_build").build()
     from dualfusion import _lib
-    return _lib.load()
+    return _lib.bind(ctypes.CDLL(_lib.LIB_PATH), check=False)
 
 
 class _Env(object):

@@ -32,7 +32,7 @@ def test_symbols_are_declared_exported_and_bound():
 
 def test_null_arguments_and_limits_are_reported_without_a_gpu():
     from dualfusion import _lib
-    lib = _lib.load()
+    lib = _lib.bind(ctypes.CDLL(_lib.LIB_PATH), check=False)
     assert lib.df3d_voxel_query(None, None, 1, None, None, 0, None, None, 0, None, 0.5, 4, None, None) == -1
     assert b"voxel_query: null" in lib.df3d_last_error()
     assert lib.df3d_voxel_query_dense(None, 1, None, None, 0, None, None, 0, None, 0.5, 4, None, None) == -1

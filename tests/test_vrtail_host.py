@@ -51,7 +51,7 @@ def test_symbols_are_declared_exported_and_bound():
 
 def test_argument_errors_are_reported_without_a_gpu():
     from dualfusion import _lib, ops
-    lib = _lib.load()
+    lib = _lib.bind(ctypes.CDLL(_lib.LIB_PATH), check=False)
     byref = ctypes.byref
     assert lib.df3d_anchor_proposals(None, 0, None, 0, None, 0, None, None, None, None, None, None, None, None, 0, None) == -1
     assert b"anchor_proposals: null config" in lib.df3d_last_error()
