@@ -6,8 +6,9 @@ weight gradient grad^T x is a [C_out x rows] . [rows x C_in] product -- a contra
 GEMM runs at a fifth of its rate (and, for inputs with a batch dimension, as a batched product plus a sum over the batch).
 `Linear` is a drop-in subclass (same parameters, same state_dict keys, same forward values -- the forward IS F.linear); only
 the backward differs: grad_input = grad W (library GEMM), grad_weight = df3d_rows_grad_weights_scaled(grad, x) -- fp16 pairs, the
-gradient under its own power-of-two block scale, three products, fp32 accumulate: fp32-grade of scale (tests/test_gpu_ops.py),
-grad_bias = column sums.  DF3D_LINEAR_WGRAD=0 keeps autograd's own backward (A/B switch, read per call)."""
+gradient under its own power-of-two block scale, three products, fp32 accumulate: fp32-grade of scale (tests/test_gpu_ops.py;
+the activation operand sits at the fixed scale, |x| < 2047, so a forward in the "split3" mode gets df3d_rows_grad_weights on
+three bf16 parts instead: `ops.rows_grad_weights_for`), grad_bias = column sums.  DF3D_LINEAR_WGRAD=0 keeps autograd's own backward (A/B switch, read per call)."""
 import os
 
 import torch
@@ -21,6 +22,7 @@ class _LinearFunction(torch.autograd.Function):
     def forward(ctx, x, weight, bias):
         ctx.save_for_backward(x, weight)
         ctx.has_bias = bias is not None
+        ctx.mode = _ops.CONV_PRECISION                 # the backward runs in the arithmetic the forward was called in
         return torch.nn.functional.linear(x, weight, bias)
 
     @staticmethod
@@ -37,8 +39,7 @@ class _LinearFunction(torch.autograd.Function):
             g2c, x2c = g2.contiguous(), x2.contiguous()
             if g2c.shape[1] % 4:                      # (a gate with one output: columns padded to the kernel's 4-channel pieces)
                 g2c = torch.nn.functional.pad(g2c, (0, (-g2c.shape[1]) % 4))
-            # two-part operands: the gradient under its own power-of-two block scale, the activation at the fixed scale
-            gw = _ops.rows_grad_weights(g2c, x2c, x_scale=_ops.rows_pow2_scale(g2c))[:g2.shape[1]]
+            gw = _ops.rows_grad_weights_for(ctx.mode, g2c, x2c)[:g2.shape[1]]
         if ctx.has_bias and ctx.needs_input_grad[2]:
             gb = g2.sum(0)
         return gx, gw, gb

@@ -835,6 +835,16 @@ def rows_grad_weights(x, grad_out, x_scale=None, g_scale=None, two_part=False):
     return gw
 
 
+def rows_grad_weights_for(mode, grad_rows, x):
+    """The weight gradient grad_rows^T x of a linear layer whose forward ran in the arithmetic `mode`.  Two-part operands: the
+    gradient under its own power-of-two block scale, the activation at the fixed scale 2^5 (|x| < 2047, range-checked like
+    every two-part operand).  "split3" promises fp32's exponent range (data known to leave the two-part range; the rerun of
+    `with_range_fallback*`): three bf16 parts per operand, no scale."""
+    if mode == "split3":
+        return rows_grad_weights(grad_rows, x)
+    return rows_grad_weights(grad_rows, x, x_scale=rows_pow2_scale(grad_rows))
+
+
 def _column_blocks(wt):
     """Transposed filters [K, cout, cin] (cin a multiple of 128) -> [cin / 128, K, cout, 128]: the banks of one grouped launch
     whose group g writes the input-gradient columns 128 g .. 128 g + 127."""
@@ -1493,21 +1503,81 @@ def raise_if_range_flag(mask):
 def with_range_fallback(fn, *args, **kwargs):
     """fn(*args, **kwargs); when it raises SplitRangeError (a read inside it found the range flag) the SAME call again with
     every convolution / GEMM on three bf16 parts ("split3": 24 significand bits, fp32's exponent range, twice the matrix work),
-    a warning the first time, RANGE_STATS['range_fallbacks'] += 1.  fn must be repeatable (an inference frame)."""
+    a warning the first time, RANGE_STATS['range_fallbacks'] += 1.
+    Nothing the first attempt changed is put back, so fn must be repeatable: an inference frame (`simple_test` under eval():
+    no BatchNorm update, no dropout).  A forward in train() mode is NOT -- it updates the BatchNorm running statistics (from
+    rows that hold inf / NaN in the attempt that left the range) and draws dropout seeds: such callers (`training_step`) use
+    `with_range_fallback_training`."""
+    return _range_fallback(None, fn, args, kwargs)
+
+
+def with_range_fallback_training(modules, fn, *args, **kwargs):
+    """`with_range_fallback` for a forward in train() mode.  `modules`: the nn.Module (or a list of them) whose forward fn
+    runs.  Before the first attempt the persistent state a training forward rewrites is saved: running_mean / running_var /
+    num_batches_tracked of every BatchNorm below `modules` (device copies on the current stream, no host wait) and the
+    generator state of the CPU and of the current CUDA device (host values).  On SplitRangeError all of it is put back
+    before the rerun, so the step leaves ONE momentum update, one count and one forward's worth of random numbers behind,
+    the same as a step that stayed in range.  Any other exception passes through with the state as fn left it; outside the
+    two-part mode nothing is rerun, so nothing is saved."""
+    return _range_fallback(_TrainingState(modules) if CONV_PRECISION == "split" else None, fn, args, kwargs)
+
+
+class _TrainingState(object):
+    """What `with_range_fallback_training` saves and restores.  The BatchNorm layers below a module are looked up once and
+    kept with it (walking a detector's module tree costs more than the copies); the copies' storage is reused while the
+    buffers it mirrors are the same tensors (`.to()` / `.double()` replace them: new storage).  A BatchNorm layer ADDED to
+    the tree after its first step is not seen: `del module.__dict__["_df3d_range_state"]` then."""
+
+    def __init__(self, modules):
+        roots = [modules] if isinstance(modules, torch.nn.Module) else list(modules)
+        self.live, self.saved = [], []
+        for root in roots:
+            kept = root.__dict__.get("_df3d_range_state")
+            if kept is None:
+                kept = root.__dict__["_df3d_range_state"] = dict(
+                    norms=[m for m in root.modules() if isinstance(m, torch.nn.modules.batchnorm._BatchNorm)], live=[], saved=[])
+            live = [b for m in kept["norms"] for b in m._buffers.values() if b is not None]
+            if len(live) != len(kept["live"]) or any(a is not b for a, b in zip(live, kept["live"])):
+                kept["live"], kept["saved"] = live, [torch.empty_like(b) for b in live]
+            self.live += live
+            self.saved += kept["saved"]
+        if self.live:
+            with torch.no_grad():
+                torch._foreach_copy_(self.saved, self.live)
+        self.cpu_rng = torch.get_rng_state()
+        self.cuda_gen = None
+        if torch.cuda.is_available() and torch.cuda.is_initialized():
+            self.cuda_gen = torch.cuda.default_generators[torch.cuda.current_device()]
+            self.cuda_rng = self.cuda_gen.get_state()
+
+    def restore(self):
+        if self.live:
+            with torch.no_grad():
+                torch._foreach_copy_(self.live, self.saved)
+        torch.set_rng_state(self.cpu_rng)
+        if self.cuda_gen is not None:
+            self.cuda_gen.set_state(self.cuda_rng)
+
+
+def _range_fallback(state, fn, args, kwargs):
     try:
         return fn(*args, **kwargs)
     except SplitRangeError as e:
         if CONV_PRECISION != "split":
             raise
-        RANGE_STATS["range_fallbacks"] += 1
-        if not _RANGE_WARNED[0]:
-            _RANGE_WARNED[0] = True
-            import warnings
-            warnings.warn("dualfusion: %s  Rerunning the frame in the three-part mode (this warning appears once)." % (e,),
-                          RuntimeWarning, stacklevel=2)
-        split_overflow(reset=True)                       # (flags raised by kernels queued behind the read)
-        with precision("split3"):
-            return fn(*args, **kwargs)
+        why = str(e)
+    # (outside the handler: the traceback -- and with it the first attempt's activations -- is released before the rerun)
+    RANGE_STATS["range_fallbacks"] += 1
+    if not _RANGE_WARNED[0]:
+        _RANGE_WARNED[0] = True
+        import warnings
+        warnings.warn("dualfusion: %s  Rerunning the frame in the three-part mode (this warning appears once)." % (why,),
+                      RuntimeWarning, stacklevel=3)
+    split_overflow(reset=True)                       # (flags raised by kernels queued behind the read)
+    if state is not None:
+        state.restore()
+    with precision("split3"):
+        return fn(*args, **kwargs)
 
 
 def unsplit_rows(split, n, c):
@@ -3090,6 +3160,7 @@ class _LinearRows(torch.autograd.Function):
     def forward(ctx, x, weight, bias):
         ctx.save_for_backward(x, weight)
         ctx.has_bias = bias is not None
+        ctx.mode = CONV_PRECISION                      # the backward runs in the arithmetic the forward was called in
         return torch.nn.functional.linear(x, weight, bias)
 
     @staticmethod
@@ -3103,11 +3174,11 @@ class _LinearRows(torch.autograd.Function):
                 and os.environ.get("DF3D_LINEAR_WGRAD", "1") != "0"):
             # (round 5) the contraction over rows on the matrix cores: df3d_rows_grad_weights_scaled -- fp16 PAIRS, the gradient
             # operand under its own power-of-two block scale (any magnitude), the activation operand at the fixed scale 2^5
-            # (|x| < 2047: range-checked like every split operand); gradient columns padded to the kernel's 4-channel pieces
-            # (the gates have one output)
+            # (|x| < 2047: range-checked like every split operand; three bf16 parts when the forward ran in "split3");
+            # gradient columns padded to the kernel's 4-channel pieces (the gates have one output)
             pad = (-g2.shape[1]) % 4
             gp = torch.nn.functional.pad(g2, (0, pad)) if pad else g2.contiguous()
-            gw = rows_grad_weights(gp, x2.contiguous(), x_scale=rows_pow2_scale(gp))[:g2.shape[1]]
+            gw = rows_grad_weights_for(ctx.mode, gp, x2.contiguous())[:g2.shape[1]]
         elif d and n // d >= 8:
             gw = torch.bmm(g2.view(n // d, d, -1).transpose(1, 2), x2.view(n // d, d, -1)).sum(0)
         else:

@@ -200,7 +200,8 @@ class CenterPointDetector(nn.Module):
         host_copies: True = the reference's logging copies (`hm_loss` / `loc_loss_elem` as CPU tensors: `.cpu()` right after the
         backward is queued -- the host then waits for the whole backward before it queues the optimizer step and the next frame);
         "async" = the same values into pinned host memory without waiting: they are valid once `rets["host_copies_ready"]`
-        (an event) has completed, and the host goes on queueing -- a trainer that logs every N steps synchronises there."""
+        (an event) has completed, and the host goes on queueing -- a trainer that logs every N steps synchronises there.
+        When the step raises `SplitRangeError` (it is not rerun) the BatchNorm buffers may hold non-finite running statistics."""
         hp = self.hot_path
         if hp.fusion is not None and batch_dict is None:
             raise ValueError("training_step: a detector with a camera-fusion adapter needs batch_dict (camera features / calibration)")

@@ -181,7 +181,9 @@ class TransFusionDetector(nn.Module):
             reducer.zero_grad()
         elif optimizer is not None:
             optimizer.zero_grad(set_to_none=True)
+        ran_in = []
         def forward_losses():
+            ran_in[:] = [_ops.CONV_PRECISION]
             if voxels is None:
                 return self.forward_train(points=points, img_metas=img_metas, gt_bboxes_3d=gt_bboxes_3d,
                                           gt_labels_3d=gt_labels_3d, img_feats=img_feats)
@@ -189,10 +191,13 @@ class TransFusionDetector(nn.Module):
                                              gt_labels_3d)
         with torch.enable_grad():
             # (`loss_device` reads the range flag of the fp16 operand format with its matching costs, BEFORE anything is
-            # back-propagated: a forward that met a value the format cannot hold is repeated on three bf16 parts)
-            losses = _ops.with_range_fallback(forward_losses)
+            # back-propagated: a forward that met a value the format cannot hold is repeated on three bf16 parts, from the
+            # BatchNorm statistics and generator states the step began with -- one update per step either way; the backward
+            # runs in the arithmetic of the forward it differentiates)
+            losses = _ops.with_range_fallback_training(self, forward_losses)
             loss, log_vars = parse_losses(losses)
-            loss.backward()
+            with _ops.precision(ran_in[0]):
+                loss.backward()
         if reducer is not None:
             reducer.finish()
         if grad_clip is not None:

@@ -40,17 +40,20 @@ def _with_precision(mode):
     return old
 
 
-def _step_three_ways(smooth, seed=0):
+def _step_three_ways(smooth, seed=0, prepare=None):
     """One training step at reduced size (160 x 160 x 40 grid, 2 samples x 6 cameras, 24 proposals) on the GPU, and the same
     detector on the host in float64 and in float32 with every HIP kernel replaced by an independent torch composition
     (tests/f64_reference.py: convolutions on the ORACLE's rulebooks, grid_sample for the deformable sampling, torch BatchNorm /
     conv2d / attention, the plain-torch `loss` with its own Hungarian matching).  smooth: without rectifiers (see
     f64_reference.without_relu).  -> (device log_vars, float64 log_vars, rows (our error, plain fp32 torch's error, L2-relative
-    error, name) per parameter -- errors against float64 relative to the gradient's largest entry --, the three detectors)."""
+    error, name) per parameter -- errors against float64 relative to the gradient's largest entry --, the three detectors).
+    prepare(det): changes the freshly loaded host detector in place before it is copied three ways (another checkpoint, hooks)."""
     import contextlib
     from dualfusion.transfusion import parse_losses
     B = 2
     det = _loaded(fr.small_transfusion_detector(), "tftrain")
+    if prepare is not None:
+        prepare(det)
     d64, d32 = copy.deepcopy(det).double().train(), copy.deepcopy(det).train()
     det = det.to(DEV).train()
     points, img, metas, gts, labels = _device_inputs(B, seed=seed)
