@@ -1341,49 +1341,87 @@ static int num_cu() {
   return g_num_cu;
 }
 
-// The loader / consumer kernel serves 128-column blocks from ~190 workgroups on (below that the 64-row tiles of the
-// kernel above fill the chip better); DF3D_OS_LC=0 / 1 forces it off / on.
-template <int CIN>
-static int launch_os_lc(const SplitConvArgs &a_, hipStream_t stream) {
-  SplitConvArgs a = a_;
-  // column blocks per workgroup: the split into ny workgroups per row tile with the fewest (rounds over the CUs) x (blocks
-  // walked + ~half a block of prologue and drain per workgroup); DF3D_LC_CBW overrides (tuning aid)
-  const int tiles = cdiv(a.n_out, 128), ncu = num_cu();
-  int best_ny = a.gy;
-  double best = 1e30;
-  for (int ny = 1; ny <= a.gy; ++ny) {
-    const double cost = (double)cdiv((long long)tiles * ny, ncu) * (cdiv(a.gy, ny) + 0.5);
-    if (cost < best - 1e-9) best = cost, best_ny = ny;
-  }
-  a.cbw = cdiv(a.gy, best_ny);
-  static const char *force = getenv("DF3D_LC_CBW");
-  if (force && atoi(force) > 0) a.cbw = atoi(force) < a.gy ? atoi(force) : a.gy;
-  hipLaunchKernelGGL((spconv_os_lc_kernel<CIN, 128>), dim3(tiles, cdiv(a.gy, a.cbw)), dim3(768), 0, stream, a);
-  return DF3D_OK;
+// ---- the launch plan: which instantiation a (format, shape, row count) runs on -----------------------------------------------
+// Decided HERE and nowhere else: the plan_* functions below hold every threshold, the launchers after them only turn a plan
+// into its hipLaunchKernelGGL, and df3d_conv_launch_plan answers from the same functions on the host (tests/test_conv_plan_host.py
+// pins the table, tests/test_gpu_conv_configs.py takes its row counts from it).
+struct ConvPlan {                      // = the int record of df3d_conv_launch_plan (DF3D_CONV_PLAN_* in df3d_hip.h)
+  int family;                          // 0 = spconv_os_split_kernel, 1 = spconv_os_lc_kernel
+  int rt, nw, kps, ks, masked;         // template arguments RT, NW, KPS, KS, MG (loader / consumer: 2 row tiles x 4 matrix waves)
+  int cbw;                             // loader / consumer: column blocks one workgroup walks (0 otherwise)
+  int tile_rows;                       // output rows per workgroup tile
+};
+enum { PLAN_OS = 0, PLAN_LC = 1 };
+
+// what a plan is made from: the shape, the SplitConvArgs fields the rules read, and the CU count (0 = ask the device, and
+// only when a rule needs it)
+struct PlanQuery {
+  int cin, cout, K, n_out, gy;
+  bool cols;
+  int ncu;
+  int cus() const { return ncu > 0 ? ncu : num_cu(); }
+};
+
+static ConvPlan plan_os(int rt, int nw, int kps, int ks = 1, bool masked = false) {
+  return ConvPlan{PLAN_OS, rt, nw, kps, ks, masked ? 1 : 0, 0, 16 * rt * nw};
 }
 
-static bool use_lc(const SplitConvArgs &a) {
+// The loader / consumer kernel serves 128-column blocks from ~190 workgroups on (below that the 64-row tiles of the
+// kernel above fill the chip better); DF3D_OS_LC=0 / 1 forces it off / on.
+static bool use_lc(const PlanQuery &q) {
   const char *t = getenv("DF3D_OS_LC");         // read per call: the tests switch it inside one process
-  if (a.cols) return false;
+  if (q.cols) return false;
   if (t && t[0] == '0') return false;
   if (t && t[0] == '1') return true;
   // (one offset = a linear layer over rows: the ring's fill and drain would be most of a two-step tile)
-  return a.K > 1 && (long long)cdiv(a.n_out, 128) * a.gy >= 190;
+  return q.K > 1 && (long long)cdiv(q.n_out, 128) * q.gy >= 190;
+}
+
+static ConvPlan plan_os_lc(const PlanQuery &q) {
+  // column blocks per workgroup: the split into ny workgroups per row tile with the fewest (rounds over the CUs) x (blocks
+  // walked + ~half a block of prologue and drain per workgroup); DF3D_LC_CBW overrides (tuning aid)
+  const int tiles = cdiv(q.n_out, 128), ncu = q.cus();
+  int best_ny = q.gy;
+  double best = 1e30;
+  for (int ny = 1; ny <= q.gy; ++ny) {
+    const double cost = (double)cdiv((long long)tiles * ny, ncu) * (cdiv(q.gy, ny) + 0.5);
+    if (cost < best - 1e-9) best = cost, best_ny = ny;
+  }
+  int cbw = cdiv(q.gy, best_ny);
+  static const char *force = getenv("DF3D_LC_CBW");
+  if (force && atoi(force) > 0) cbw = atoi(force) < q.gy ? atoi(force) : q.gy;
+  return ConvPlan{PLAN_LC, 2, 4, 1, 1, 0, cbw, 128};
+}
+
+template <int CIN>
+static int launch_os_lc(const SplitConvArgs &a_, const ConvPlan &p, hipStream_t stream) {
+  SplitConvArgs a = a_;
+  a.cbw = p.cbw;
+  hipLaunchKernelGGL((spconv_os_lc_kernel<CIN, 128>), dim3(cdiv(a.n_out, 128), cdiv(a.gy, a.cbw)), dim3(768), 0, stream, a);
+  return DF3D_OK;
+}
+
+static PlanQuery plan_query(int cin, int cout, const SplitConvArgs &a) {
+  return PlanQuery{cin, cout, a.K, a.n_out, a.gy, a.cols != nullptr, 0};
 }
 
 // (Round 3's staged-range and weight-stationary experiment kernels -- measured, parity-tested, never faster than the kernels
 // here -- moved out of the library in round 5: tools/ubench/attic/spconv_halo.h, spconv_ws.h)
 
-template <int CIN, int COUT>
-static int launch_os_split(const SplitConvArgs &a, hipStream_t stream) {
+// A plan's (RT, NW, KPS[, KS, MG]) as one switch label: the launchers below list the instantiations that exist, and a plan
+// that names none of them is a bug of the plan function (DF3D_EINVAL, never another kernel).
+static constexpr int plan_key(int rt, int nw, int kps, int ks = 1, int masked = 0) {
+  return (((rt * 32 + nw) * 4 + kps) * 4 + ks) * 2 + masked;
+}
+static int plan_key(const ConvPlan &p) { return plan_key(p.rt, p.nw, p.kps, p.ks, p.masked); }
+
+static ConvPlan plan_os_split(const PlanQuery &q) {
   // measured on MI355X (tools/conv_probe.py, DF3D_OS_CFG sweep): 8 waves x 1 row tile wins at the nuScenes layer
   // sizes (30k-70k rows).  The W step tiles are re-read from L2 by every workgroup (n_out/TM x 4*K*CIN*COUT
   // bytes per launch, more than the gathers), so more rows per workgroup = less L2 traffic; bigger register
   // tiles (RT 2) leave too few waves on the 256 CUs at these row counts.
-  int rt = 1, nw = a.n_out >= 16 * 1024 ? 8 : 2, kps = 1;
-  if constexpr (COUT == 128 && CIN % 32 == 0) {
-    if (use_lc(a)) return launch_os_lc<CIN>(a, stream);
-  }
+  int rt = 1, nw = q.n_out >= 16 * 1024 ? 8 : 2, kps = 1;
+  if (q.cout == 128 && q.cin % 32 == 0 && use_lc(q)) return plan_os_lc(q);
   static const char *cfg = getenv("DF3D_OS_CFG");       // tuning aid: "RT,NW[,KPS]"
   if (cfg && cfg[0] && cfg[1] == ',') {
     rt = cfg[0] - '0';
@@ -1391,46 +1429,59 @@ static int launch_os_split(const SplitConvArgs &a, hipStream_t stream) {
     const char *c2 = strchr(cfg + 2, ',');
     if (c2) kps = atoi(c2 + 1);
   }
-  constexpr int KMAX = CIN >= 64 ? 2 : 1;
-  if (kps > KMAX) kps = KMAX;
-#define DF3D_OS_LAUNCH(RT, NW, KPS)                                                                      \
-  hipLaunchKernelGGL((spconv_os_split_kernel<CIN, COUT, RT, NW, KPS>), dim3(cdiv(a.n_out, 16 * RT * NW), a.gy), \
-                     dim3(NW * 64), 0, stream, a)
-  if (kps == 2) {
-    if (rt == 2) DF3D_OS_LAUNCH(2, 4, KMAX);
-    else if (nw == 2) DF3D_OS_LAUNCH(1, 2, KMAX);
-    else if (nw == 8) DF3D_OS_LAUNCH(1, 8, KMAX);
-    else DF3D_OS_LAUNCH(1, 4, KMAX);
-  } else if (nw == 16) DF3D_OS_LAUNCH(1, 16, 1);
-  else if (rt == 2 && nw == 8) DF3D_OS_LAUNCH(2, 8, 1);
-  else if (nw == 8) {
+  const int kmax = q.cin >= 64 ? 2 : 1;
+  if (kps > kmax) kps = kmax;
+  // (what a tuning request that names no instantiation falls to: as the launch ladder always read it)
+  if (kps == 2) return rt == 2 ? plan_os(2, 4, 2) : plan_os(1, nw == 2 || nw == 8 ? nw : 4, 2);
+  if (nw == 16) return plan_os(1, 16, 1);
+  if (rt == 2 && nw == 8) return plan_os(2, 8, 1);
+  if (nw == 8) {
     // sparse 3-D rulebooks: masked gathers (DF3D_OS_MASKED=0 / 1 forces them off / on; read per call for the A/B)
     const char *mg = getenv("DF3D_OS_MASKED");
     // measured (tools/conv_probe.py, MI355X): 32 -> 32 35.3 -> 33.5 us, 64 -> 64 63.5 -> 68.5 us (the branch costs the wider
     // kernel more than the requests it saves) -- default on for 32 input channels only
-    const bool masked = mg ? mg[0] == '1' : (a.K == 27 && !a.cols && CIN == 32);
-    if (masked)
-      hipLaunchKernelGGL((spconv_os_split_kernel<CIN, COUT, 1, 8, 1, 2, 1, true>), dim3(cdiv(a.n_out, 128), a.gy), dim3(512), 0,
-                         stream, a);
-    else DF3D_OS_LAUNCH(1, 8, 1);
+    return plan_os(1, 8, 1, 1, mg ? mg[0] == '1' : (q.K == 27 && !q.cols && q.cin == 32));
   }
-  else if (rt == 2 && nw == 4) DF3D_OS_LAUNCH(2, 4, 1);
-  else if (rt == 2 && nw == 2) DF3D_OS_LAUNCH(2, 2, 1);
-  else if (rt == 1 && nw == 4) DF3D_OS_LAUNCH(1, 4, 1);
-  else DF3D_OS_LAUNCH(1, 2, 1);
+  if (rt == 2 && (nw == 4 || nw == 2)) return plan_os(2, nw, 1);
+  return plan_os(1, rt == 1 && nw == 4 ? 4 : 2, 1);
+}
+
+template <int CIN, int COUT>
+static int launch_os_split(const SplitConvArgs &a, hipStream_t stream) {
+  const ConvPlan p = plan_os_split(plan_query(CIN, COUT, a));
+  if constexpr (COUT == 128 && CIN % 32 == 0) {
+    if (p.family == PLAN_LC) return launch_os_lc<CIN>(a, p, stream);
+  }
+  if (p.family != PLAN_OS) return DF3D_EINVAL;
+  constexpr int KMAX = CIN >= 64 ? 2 : 1;                // (KPS = 2 is planned from 64 input channels on only)
+#define DF3D_OS_LAUNCH(RT, NW, KPS, MG)                                                                                    \
+  hipLaunchKernelGGL((spconv_os_split_kernel<CIN, COUT, RT, NW, KPS, 2, 1, MG>), dim3(cdiv(a.n_out, 16 * RT * NW), a.gy), \
+                     dim3(NW * 64), 0, stream, a)
+  switch (plan_key(p)) {
+    case plan_key(2, 4, 2): DF3D_OS_LAUNCH(2, 4, KMAX, false); break;
+    case plan_key(1, 2, 2): DF3D_OS_LAUNCH(1, 2, KMAX, false); break;
+    case plan_key(1, 8, 2): DF3D_OS_LAUNCH(1, 8, KMAX, false); break;
+    case plan_key(1, 4, 2): DF3D_OS_LAUNCH(1, 4, KMAX, false); break;
+    case plan_key(1, 16, 1): DF3D_OS_LAUNCH(1, 16, 1, false); break;
+    case plan_key(2, 8, 1): DF3D_OS_LAUNCH(2, 8, 1, false); break;
+    case plan_key(1, 8, 1, 1, 1): DF3D_OS_LAUNCH(1, 8, 1, true); break;
+    case plan_key(1, 8, 1): DF3D_OS_LAUNCH(1, 8, 1, false); break;
+    case plan_key(2, 4, 1): DF3D_OS_LAUNCH(2, 4, 1, false); break;
+    case plan_key(2, 2, 1): DF3D_OS_LAUNCH(2, 2, 1, false); break;
+    case plan_key(1, 4, 1): DF3D_OS_LAUNCH(1, 4, 1, false); break;
+    case plan_key(1, 2, 1): DF3D_OS_LAUNCH(1, 2, 1, false); break;
+    default: return DF3D_EINVAL;
+  }
 #undef DF3D_OS_LAUNCH
   return DF3D_OK;
 }
 
 // 256-channel shapes (dense BEV neck).  Workgroup rows by map size so that the small (90 x 90) maps still fill the
 // 256 CUs; DF3D_OS_WIDE="RT,NW" overrides (tuning aid).
-template <int CIN, int COUT>
-static int launch_os_split_wide(const SplitConvArgs &a, hipStream_t stream) {
-  const int CS = a.gy;
-  if constexpr (COUT % 128 == 0) {
-    if (use_lc(a)) return launch_os_lc<CIN>(a, stream);
-  }
-  int rt = 1, nw = (long long)a.n_out * CS >= 128 * 384 ? 8 : (long long)a.n_out * CS >= 64 * 192 ? 4 : 2;
+static ConvPlan plan_os_split_wide(const PlanQuery &q) {
+  const int CS = q.gy;
+  if (q.cout % 128 == 0 && use_lc(q)) return plan_os_lc(q);
+  int rt = 1, nw = (long long)q.n_out * CS >= 128 * 384 ? 8 : (long long)q.n_out * CS >= 64 * 192 ? 4 : 2;
   static const char *cfg = getenv("DF3D_OS_WIDE");
   if (cfg && cfg[0] && cfg[1] == ',') {
     rt = cfg[0] - '0';
@@ -1438,49 +1489,82 @@ static int launch_os_split_wide(const SplitConvArgs &a, hipStream_t stream) {
   }
   // Small maps (B = 1 at 90 x 90: 127 row tiles x 2 column halves of 4 waves = one wave per SIMD): three wave groups per
   // workgroup share the offsets of the tile (KS = 3).  DF3D_OS_KSPLIT=0 turns it off (A/B; read per call).
-  if constexpr (CIN <= 256 && COUT % 128 == 0) {
+  if (q.cin <= 256 && q.cout % 128 == 0) {
     const char *ks = getenv("DF3D_OS_KSPLIT");
-    const long long waves = (long long)cdiv(a.n_out, 64) * CS * 4;
-    if (!(cfg && cfg[0]) && nw == 4 && a.K >= 3 && !(ks && ks[0] == '0') && waves <= 6LL * num_cu()) {
-      hipLaunchKernelGGL((spconv_os_split_kernel<CIN, COUT, 1, 4, 1, 2, 3>), dim3(cdiv(a.n_out, 64), CS), dim3(768), 0,
-                         stream, a);
+    const long long waves = (long long)cdiv(q.n_out, 64) * CS * 4;
+    if (!(cfg && cfg[0]) && nw == 4 && q.K >= 3 && !(ks && ks[0] == '0') && waves <= 6LL * q.cus()) return plan_os(1, 4, 1, 3);
+  }
+  // (what a tuning request that names no instantiation falls to: as the launch ladder always read it)
+  if (rt == 2) return plan_os(2, nw == 4 ? 4 : 2, 1);
+  return plan_os(1, nw == 8 || nw == 4 ? nw : 2, 1);
+}
+
+template <int CIN, int COUT>
+static int launch_os_split_wide(const SplitConvArgs &a, hipStream_t stream) {
+  const ConvPlan p = plan_os_split_wide(plan_query(CIN, COUT, a));
+  if constexpr (COUT % 128 == 0) {
+    if (p.family == PLAN_LC) return launch_os_lc<CIN>(a, p, stream);
+  }
+  if (p.family != PLAN_OS) return DF3D_EINVAL;
+#define DF3D_OS_LAUNCH(RT, NW, KS)                                                                                 \
+  hipLaunchKernelGGL((spconv_os_split_kernel<CIN, COUT, RT, NW, 1, 2, KS>), dim3(cdiv(a.n_out, 16 * RT * NW), a.gy), \
+                     dim3(NW * KS * 64), 0, stream, a)
+  if constexpr (CIN <= 256 && COUT % 128 == 0) {
+    if (plan_key(p) == plan_key(1, 4, 1, 3)) {
+      DF3D_OS_LAUNCH(1, 4, 3);
       return DF3D_OK;
     }
   }
-#define DF3D_OS_LAUNCH(RT, NW)                                                                                  \
-  hipLaunchKernelGGL((spconv_os_split_kernel<CIN, COUT, RT, NW, 1>), dim3(cdiv(a.n_out, 16 * RT * NW), CS), \
-                     dim3(NW * 64), 0, stream, a)
-  if (rt == 2 && nw == 4) DF3D_OS_LAUNCH(2, 4);
-  else if (rt == 2) DF3D_OS_LAUNCH(2, 2);
-  else if (nw == 8) DF3D_OS_LAUNCH(1, 8);
-  else if (nw == 4) DF3D_OS_LAUNCH(1, 4);
-  else DF3D_OS_LAUNCH(1, 2);
+  switch (plan_key(p)) {
+    case plan_key(2, 4, 1): DF3D_OS_LAUNCH(2, 4, 1); break;
+    case plan_key(2, 2, 1): DF3D_OS_LAUNCH(2, 2, 1); break;
+    case plan_key(1, 8, 1): DF3D_OS_LAUNCH(1, 8, 1); break;
+    case plan_key(1, 4, 1): DF3D_OS_LAUNCH(1, 4, 1); break;
+    case plan_key(1, 2, 1): DF3D_OS_LAUNCH(1, 2, 1); break;
+    default: return DF3D_EINVAL;
+  }
 #undef DF3D_OS_LAUNCH
   return DF3D_OK;
 }
 
 // bf16 rows / bf16 weights (NP = 1): one configuration per shape (8 waves, or 2 for small row counts)
-template <int CIN, int COUT>
-static int launch_os_bf16(const SplitConvArgs &a, hipStream_t stream) {
-  if ((long long)a.n_out * a.gy >= 16 * 1024)
-    hipLaunchKernelGGL((spconv_os_split_kernel<CIN, COUT, 1, 8, 1, 1>), dim3(cdiv(a.n_out, 128), a.gy), dim3(512), 0, stream, a);
-  else
-    hipLaunchKernelGGL((spconv_os_split_kernel<CIN, COUT, 1, 2, 1, 1>), dim3(cdiv(a.n_out, 32), a.gy), dim3(128), 0, stream, a);
-  return DF3D_OK;
-}
+static ConvPlan plan_os_bf16(const PlanQuery &q) { return plan_os(1, (long long)q.n_out * q.gy >= 16 * 1024 ? 8 : 2, 1); }
 
 // three-part operands (NP = 3, six products): one configuration per shape -- 8 waves per workgroup on the large maps, 4 / 2 on
 // the small ones (the same rule as the bf16 launches); the loader / consumer kernel has no three-part form
+static ConvPlan plan_os_p3(const PlanQuery &q) {
+  const long long work = (long long)q.n_out * q.gy;
+  return plan_os(1, work >= 32 * 1024 ? 8 : work >= 12 * 1024 ? 4 : 2, 1);
+}
+
+// the one-part and three-part launches: NW of the plan, everything else fixed
+template <int CIN, int COUT, int NP>
+static int launch_os_parts(const SplitConvArgs &a, const ConvPlan &p, hipStream_t stream) {
+#define DF3D_OS_LAUNCH(NW)                                                                                                 \
+  hipLaunchKernelGGL((spconv_os_split_kernel<CIN, COUT, 1, NW, 1, NP>), dim3(cdiv(a.n_out, 16 * NW), a.gy), dim3(NW * 64), 0, \
+                     stream, a)
+  switch (plan_key(p)) {
+    case plan_key(1, 8, 1): DF3D_OS_LAUNCH(8); break;
+    case plan_key(1, 4, 1):
+      if constexpr (NP == 3) {
+        DF3D_OS_LAUNCH(4);
+        break;
+      } else return DF3D_EINVAL;
+    case plan_key(1, 2, 1): DF3D_OS_LAUNCH(2); break;
+    default: return DF3D_EINVAL;
+  }
+#undef DF3D_OS_LAUNCH
+  return DF3D_OK;
+}
+
+template <int CIN, int COUT>
+static int launch_os_bf16(const SplitConvArgs &a, hipStream_t stream) {
+  return launch_os_parts<CIN, COUT, 1>(a, plan_os_bf16(plan_query(CIN, COUT, a)), stream);
+}
+
 template <int CIN, int COUT>
 static int launch_os_p3(const SplitConvArgs &a, hipStream_t stream) {
-  const long long work = (long long)a.n_out * a.gy;
-  if (work >= 32 * 1024)
-    hipLaunchKernelGGL((spconv_os_split_kernel<CIN, COUT, 1, 8, 1, 3>), dim3(cdiv(a.n_out, 128), a.gy), dim3(512), 0, stream, a);
-  else if (work >= 12 * 1024)
-    hipLaunchKernelGGL((spconv_os_split_kernel<CIN, COUT, 1, 4, 1, 3>), dim3(cdiv(a.n_out, 64), a.gy), dim3(256), 0, stream, a);
-  else
-    hipLaunchKernelGGL((spconv_os_split_kernel<CIN, COUT, 1, 2, 1, 3>), dim3(cdiv(a.n_out, 32), a.gy), dim3(128), 0, stream, a);
-  return DF3D_OK;
+  return launch_os_parts<CIN, COUT, 3>(a, plan_os_p3(plan_query(CIN, COUT, a)), stream);
 }
 
 // ---- the shapes and the operand formats --------------------------------------------------------------------------------------
@@ -1533,6 +1617,21 @@ static int launch_any(int cin, int cout, const SplitConvArgs &a, hipStream_t str
   DF3D_CONV_SHAPES(X)
 #undef X
   return DF3D_EINVAL;
+}
+
+// gridDim.y of a launch: one column block of <= 128 columns per group (256 columns = two blocks)
+static int conv_grid_y(int groups, int cout) { return groups * (cout > 128 ? cout / 128 : 1); }
+
+// the plan function launch_shape's launcher calls for a (format, shape); false: the format does not serve the shape
+static bool conv_plan(int parts, const PlanQuery &q, ConvPlan *p) {
+  if (parts < 1 || parts > 3 || !shape_ok(parts, q.cin, q.cout)) return false;
+  int fam = FAM_os;
+#define X(CIN, COUT, FAM, B16) \
+  if (q.cin == CIN && q.cout == COUT) fam = FAM_##FAM;
+  DF3D_CONV_SHAPES(X)
+#undef X
+  *p = parts == 3 ? plan_os_p3(q) : parts == 1 ? plan_os_bf16(q) : fam == FAM_wide ? plan_os_split_wide(q) : plan_os_split(q);
+  return true;
 }
 
 // An operand format of the matrix-core kernels: how many 16-bit parts stand for one fp32 value.  Operand rows and packed
@@ -1618,7 +1717,7 @@ static int conv_launch(const ConvFormat &f, const char *entry, const ConvCall &c
   SplitConvArgs a = {(const u32x4 *)c.in, (const u32x4 *)c.packed, c.nbr, c.bias, c.scale, c.shift, (const float *)c.residual,
                      c.out, (u32x4 *)c.out_rows, c.n_in, c.n_out, c.kvol, c.relu, dbg ? atoi(dbg) : 0,
                      c.in_channels / 8 * f.parts, c.in_group_stride / 8 * f.parts, c.out_channels,
-                     c.groups * (c.cout > 128 ? c.cout / 128 : 1), c.out_cols, c.order};
+                     conv_grid_y(c.groups, c.cout), c.out_cols, c.order};
 #ifdef DF3D_OS_TRACE
   if (f.tuning) a.trace = g_os_trace;
 #endif
@@ -1685,6 +1784,20 @@ extern "C" int df3d_conv_rows_split3(const void *in_split3, int n_in, int in_cha
 }
 
 extern "C" size_t df3d_conv_packed_weight_bytes(int kvol, int cin, int cout) { return conv_format(2).packed_bytes(kvol, cin, cout); }
+
+// Host only: the launch a convolution entry of the format would make (include/df3d_hip.h).  Same functions, same per-call
+// environment switches as the launchers; a given num_cu keeps the device out of the answer.
+extern "C" int df3d_conv_launch_plan(int parts, int kvol, int cin, int cout, int groups, int n_out, int compact_cols, int num_cu,
+                                     int *plan) {
+  if (!plan || kvol <= 0 || kvol > DF3D_MAX_KVOL || groups < 1 || groups > 65535 || n_out < 1 || num_cu < 0) return DF3D_EINVAL;
+  if (compact_cols && cout != 32) return DF3D_EINVAL;
+  ConvPlan p;
+  if (!conv_plan(parts, PlanQuery{cin, cout, kvol, n_out, conv_grid_y(groups, cout), compact_cols != 0, num_cu}, &p))
+    return DF3D_EINVAL;
+  const int rec[DF3D_CONV_PLAN_FIELDS] = {p.family, p.rt, p.nw, p.kps, p.ks, p.masked, p.cbw, p.tile_rows};
+  for (int i = 0; i < DF3D_CONV_PLAN_FIELDS; ++i) plan[i] = rec[i];
+  return DF3D_OK;
+}
 
 extern "C" int df3d_conv_pack_weights(const float *filters, int kvol, int cin, int cout, void *packed, void *stream_) {
   return pack_filters(conv_format(2), "conv_pack_weights", filters, 1, kvol, cin, cout, packed, (hipStream_t)stream_);

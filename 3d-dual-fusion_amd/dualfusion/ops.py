@@ -548,6 +548,22 @@ def conv_bf16_supported(kvol, cin, cout):
     return _lib.load().df3d_conv_packed_weight_bytes_bf16(int(kvol), int(cin), int(cout)) > 0
 
 
+CONV_PLAN_FIELDS = 8    # DF3D_CONV_PLAN_FIELDS
+ConvLaunchPlan = collections.namedtuple("ConvLaunchPlan", "family rt nw kps ks masked cbw tile_rows")
+CONV_PLAN_FAMILIES = ("os", "lc")
+
+
+def conv_launch_plan(kind, kvol, cin, cout, n_out, groups=1, compact_cols=False, num_cu=0):
+    """The launch a convolution of the format `kind` ("bf16" | "split" | "split3") makes at n_out output rows
+    (df3d_conv_launch_plan: the function the launchers themselves ask) -> ConvLaunchPlan(family "os" | "lc", rt, nw, kps, ks,
+    masked, cbw, tile_rows).  num_cu = 0: the device's compute units; a given count needs no device.  Raises Df3dError where
+    the format has no kernel for the shape."""
+    rec = (ctypes.c_int * CONV_PLAN_FIELDS)()
+    _lib.load().df3d_conv_launch_plan(FORMATS[kind].parts, int(kvol), int(cin), int(cout), int(groups), int(n_out),
+                                      int(bool(compact_cols)), int(num_cu), rec)
+    return ConvLaunchPlan(CONV_PLAN_FAMILIES[rec[0]], rec[1], rec[2], rec[3], rec[4], bool(rec[5]), rec[6], rec[7])
+
+
 def grad_scaled():
     """DF3D_GRAD_SCALED=0 (an A/B switch): no block-scaled two-part gradient operands, the three-part forms instead."""
     return os.environ.get("DF3D_GRAD_SCALED", "1") != "0"

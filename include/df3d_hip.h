@@ -258,6 +258,18 @@ int df3d_conv_pack_weights_bf16(const float *filters, int kvol, int cin, int cou
 int df3d_sparse_conv_bf16(const void *features_bf16, int n_in, int cin, const void *packed_filters, int kvol, int cout,
                           const int32_t *nbr, int n_out, const float *bias, const float *scale, const float *shift,
                           const void *residual_bf16, int relu, float *out, void *out_bf16, void *stream);
+/* Host only: the launch the matrix-core convolution entries above make for a shape and a row count -- parts 1 = the bf16 entry,
+ * 2 = the two-part entries (df3d_sparse_conv_split, df3d_conv_rows_split), 3 = df3d_conv_rows_split3; `groups` and
+ * `compact_cols` (non-zero: the call passes out_cols) as the entry takes them.  The launchers take their decision from the same
+ * function, and DF3D_OS_LC / DF3D_OS_KSPLIT / DF3D_OS_MASKED are read per call here as there.  num_cu = 0: the device's compute
+ * unit count, anything else is used as given (the answer then needs no device).  Negative where the format has no kernel for
+ * the shape or the entry would refuse the arguments.  plan[DF3D_CONV_PLAN_FIELDS] =
+ *   [0] kernel family: 0 output-stationary register gathers, 1 loader / consumer (LDS-DMA)
+ *   [1] RT  [2] NW  [3] KPS  [4] KS: 16-row tiles per wave, waves (matrix waves of the loader / consumer kernel), 32-channel
+ *       blocks per step, wave groups that share a tile's offsets
+ *   [5] 1 = masked gathers  [6] loader / consumer: column blocks one workgroup walks (else 0)  [7] output rows per tile */
+#define DF3D_CONV_PLAN_FIELDS 8
+int df3d_conv_launch_plan(int parts, int kvol, int cin, int cout, int groups, int n_out, int compact_cols, int num_cu, int *plan);
 
 /* Sparse convolution backward.  Replace sparse_conv_ext.indice_conv_backward_fp32
  * (TF/mmdet3d/ops/spconv/src/all.cc:21-51, include/spconv/spconv_ops.h:363-456):

@@ -29,7 +29,7 @@ def _constants():
             ("DF3D_EHIP", _lib.DF3D_EHIP), ("DF3D_NMS_NORMAL", ops.NMS_NORMAL), ("DF3D_NMS_ROTATED", ops.NMS_ROTATED),
             ("DF3D_NMS_CIRCLE", ops.NMS_CIRCLE), ("DF3D_MAX_ANCHORS", ops.MAX_ANCHORS),
             ("DF3D_LOSS_MAX_CODES", ops.LOSS_MAX_CODES), ("DF3D_LOSS_FIELDS", ops.LOSS_FIELDS),
-            ("DF3D_HEAD_MAX_PROJ", prefetch.MAX_PROJ)]
+            ("DF3D_HEAD_MAX_PROJ", prefetch.MAX_PROJ), ("DF3D_CONV_PLAN_FIELDS", ops.CONV_PLAN_FIELDS)]
 
 
 def _host_cc():

@@ -455,12 +455,14 @@ def test_head_branch_backward_launches_what_its_two_branches_launched(dev, mode)
     assert not flag[0], flag
 
 
-@pytest.mark.parametrize("cin,cout", [(128, 128), (64, 128), (128, 256)])
+@pytest.mark.parametrize("cin,cout", [(128, 128), (64, 128), (128, 256), (256, 256), (256, 128), (512, 128)])
 def test_loader_consumer_conv_kernel_forced_on_small_and_ragged_shapes(dev, cin, cout):
     """The loader / consumer LDS-DMA kernel normally serves layers of >= 190 workgroups; forced on (DF3D_OS_LC=1) it must
     give the register-gather kernel's result BIT FOR BIT (same summation order) on every shape: a single row, row counts
     around the 128-row tile, tiles whose last rows are padding, offsets without any pair in a tile, a 1-offset rulebook
-    (fewer steps than ring stages), every epilogue combination, 256 columns as two blocks, a tiling order."""
+    (fewer steps than ring stages), every epilogue combination, 256 columns as two blocks, a tiling order.  256 and 512 input
+    channels (the BEV neck and the heads' shared convolutions: 8 and 16 channel blocks per offset) are its only other
+    instantiations; `ops.conv_launch_plan` confirms that the switch selects the kernel for the shape."""
     import os
     from dualfusion import ops
     shape, batch = [9, 48, 48], 2
@@ -474,8 +476,10 @@ def test_loader_consumer_conv_kernel_forced_on_small_and_ragged_shapes(dev, cin,
 
     def both(fn):
         os.environ["DF3D_OS_LC"] = "0"
+        assert ops.conv_launch_plan("split", 27, cin, cout, 100).family == "os"
         a = fn()
         os.environ["DF3D_OS_LC"] = "1"
+        assert ops.conv_launch_plan("split", 27, cin, cout, 100).family == "lc"
         b = fn()
         return a, b
     try:
@@ -1157,13 +1161,16 @@ def test_sparse_conv2d_and_pool2d_vs_dense_torch(dev):
 @pytest.mark.parametrize("cin,cout,K,n_in,n_out,density", [
     (128, 128, 27, 3000, 3000, 0.4), (64, 64, 27, 5000, 4100, 0.3), (32, 64, 27, 2500, 900, 0.5),
     (16, 16, 27, 20000, 20000, 0.35), (16, 32, 8, 7000, 1777, 0.9), (64, 128, 27, 1300, 300, 0.02),
-    (256, 256, 9, 2100, 2100, 0.95), (48, 20, 27, 999, 1001, 0.4), (128, 64, 1, 70, 70, 1.0), (12, 20, 27, 500, 400, 0.5)])
+    (256, 256, 9, 2100, 2100, 0.95), (48, 20, 27, 999, 1001, 0.4), (128, 64, 1, 70, 70, 1.0), (12, 20, 27, 500, 400, 0.5),
+    (128, 128, 27, 17000, 16384, 0.3), (128, 128, 27, 17000, 16383, 0.3)])
 def test_filter_gradient_kernels_against_float64(cin, cout, K, n_in, n_out, density):
     """df3d_sparse_conv_grad_filters: the LDS-staged pair-compacted kernel (channel counts that are multiples of 4) and the
     direct kernel (everything else, DF3D_WGRAD=0) against sum over pairs of features[in]^T grad_out[out] in float64:
-    ragged row counts, empty offsets, channel counts that do not fill a tile."""
+    ragged row counts, empty offsets, channel counts that do not fill a tile.  128 -> 128 at 16 384 and 16 383 rows: the two
+    sides of the rule that moves the default from the staged fp32 kernel to the matrix cores (df3d_grad_filters_kernel: 13 / 1);
+    there the default runs too."""
     import os
-    from dualfusion import ops
+    from dualfusion import _lib, ops
     dev = torch.device("cuda:0")
     gen = torch.Generator().manual_seed(cin * 1000 + cout)
     nbr = torch.randint(0, n_in, (K, n_out), generator=gen, dtype=torch.int32)
@@ -1191,6 +1198,12 @@ def test_filter_gradient_kernels_against_float64(cin, cout, K, n_in, n_out, dens
         # (round 5) mode 3 = three bf16 parts per operand on the 16-bit matrix cores, forced here on every shape with channel
         # counts that are multiples of 4 (by default it takes the layers with >= 64 channels on both sides): fp32-grade
         assert float((outs[mode] - ref).abs().max()) <= (4e-6 if mode == "3" else 2e-5) * scale, mode
+    if (cin, cout) == (128, 128) and n_out in (16384, 16383):
+        assert "DF3D_WGRAD" not in os.environ
+        kernel = _lib.load().df3d_grad_filters_kernel(0, K, cin, cout, n_out)
+        assert kernel == (13 if n_out >= 16384 else 1), kernel
+        got = ops.sparse_conv_grad_filters(feats.to(dev), gout.to(dev), nbr.to(dev)).cpu().double()
+        assert float((got - ref).abs().max()) <= (4e-6 if kernel == 13 else 2e-5) * scale, kernel
     if cin % 4 == 0 and cout % 4 == 0 and cin >= 32 and cout >= 32:
         # second half of round 5: fp16 pairs, the gradient under its power-of-two block scale (three products)
         for gs in (1.0, 1e-7, 1e+6):
