@@ -17,17 +17,6 @@ namespace df3d {
 
 DF3D_SPLIT_OVERFLOW_TU(actr)
 
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 __global__ __launch_bounds__(256) void actr_prep_kernel(const float *__restrict__ q, const float *__restrict__ qi,
                                                         const float *__restrict__ pos, size_t n4,
                                                         float *__restrict__ A, float *__restrict__ Bw) {
@@ -41,13 +30,6 @@ __global__ __launch_bounds__(256) void actr_prep_kernel(const float *__restrict_
 
 // LPR lanes per row (16 / 32 / 64: the smallest that covers C / 4 vectors, so a 64-channel row keeps a quarter wave busy and a
 // wave normalises four rows -- one wave per row left 48 of 64 lanes idle there: 113 us for 262 k rows); C <= 1024, C % 4 == 0
-template <int LPR>
-__device__ __forceinline__ float group_sum(float v) {
-#pragma unroll
-  for (int o = LPR / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 template <int LPR>
 __global__ __launch_bounds__(256) void add_layernorm_kernel(const float *__restrict__ x, const float *__restrict__ y,
                                                             const float *__restrict__ gamma,
@@ -126,8 +108,8 @@ __global__ __launch_bounds__(256) void bigate_sum_kernel(const float *__restrict
       d2 += g[0] * w2[0] + g[1] * w2[1] + g[2] * w2[2] + g[3] * w2[3];
     }
   }
-  float s1 = 1.f / (1.f + __expf(-(wave_sum(d1) + bb[0])));
-  float s2 = 1.f / (1.f + __expf(-(wave_sum(d2) + ba[0])));
+  float s1 = 1.f / (1.f + __expf(-(group_sum<64>(d1) + bb[0])));
+  float s2 = 1.f / (1.f + __expf(-(group_sum<64>(d2) + ba[0])));
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
     int c4 = lane + 64 * k;
@@ -495,7 +477,6 @@ __global__ __launch_bounds__(256) void relu_dropout_bwd_kernel(const float *__re
 }
 
 // bfloat16 rows (the bf16 mixed-precision mode): eight elements per lane
-__device__ __forceinline__ float rd_bf16_to_f32(unsigned short v) { return __uint_as_float((unsigned)v << 16); }
 __device__ __forceinline__ unsigned short rd_f32_to_bf16(float f) {       // round to nearest even (finite inputs)
   const unsigned u = __float_as_uint(f);
   return (unsigned short)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
@@ -517,9 +498,9 @@ __global__ __launch_bounds__(256) void relu_dropout_bf16_kernel(unsigned short *
 #pragma unroll
   for (int j = 0; j < 8; ++j) {
     if (BWD) {
-      ov[j] = (hv[j] & 0x7fffu) ? rd_f32_to_bf16(rd_bf16_to_f32(gv[j]) * scale) : (unsigned short)0;
+      ov[j] = (hv[j] & 0x7fffu) ? rd_f32_to_bf16(bf16lo_to_f32(gv[j]) * scale) : (unsigned short)0;
     } else {
-      const float v = rd_bf16_to_f32(hv[j]);
+      const float v = bf16lo_to_f32(hv[j]);
       ov[j] = v > 0.f && (thr == 0u || rd_keep(i8 + j, s0, s1, thr)) ? rd_f32_to_bf16(v * scale) : (unsigned short)0;
     }
   }

@@ -16,8 +16,6 @@
 
 namespace df3d {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 // Double atomics from hundreds of workgroups onto the SAME 2 x C addresses serialise (~100 ns each: 43 us of a kernel whose
 // reads take 5): the sums live in BN_REPL replicas [replica][2][C], workgroup i adds into replica i % BN_REPL, readers add
 // the replicas up.

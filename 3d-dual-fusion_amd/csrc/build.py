@@ -16,7 +16,7 @@ SOURCES = ["common.hip", "voxelize.hip", "rulebook.hip", "spconv.hip", "spconv_s
 OUT = os.path.join(HERE, "libdf3d_hip.so")
 OBJ_DIR = os.path.join(HERE, "build")
 CFLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc"]
-HEADERS = [os.path.join(HERE, "common.h"), os.path.join(HERE, "..", "..", "include", "df3d_hip.h")]
+HEADERS = sorted(os.path.join(HERE, f) for f in os.listdir(HERE) if f.endswith(".h")) + [os.path.join(HERE, "..", "..", "include", "df3d_hip.h")]
 
 
 def _newer(target, deps):
@@ -47,7 +47,9 @@ def build(force=False, verbose=False):
         r = subprocess.run(cmd, capture_output=True, text=True)
         return cmd, r.returncode, r.stdout + r.stderr
 
-    with ThreadPoolExecutor(max_workers=min(len(jobs), os.cpu_count() or 4) or 1) as pool:
+    # MAX_JOBS, else at most 16: os.cpu_count() reports the whole host where a job is given only a share of it
+    workers = int(os.environ.get("MAX_JOBS") or min(16, os.cpu_count() or 4))
+    with ThreadPoolExecutor(max_workers=max(1, min(len(jobs), workers))) as pool:
         for cmd, rc, log in pool.map(run, jobs):
             if rc != 0:
                 sys.stderr.write(log)

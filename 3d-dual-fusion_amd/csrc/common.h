@@ -63,6 +63,10 @@ typedef __bf16 df3d_bf16x2 __attribute__((ext_vector_type(2)));
 typedef _Float16 df3d_f16x2 __attribute__((ext_vector_type(2)));
 typedef float df3d_f32x2 __attribute__((ext_vector_type(2)));
 typedef _Float16 df3d_f16x8 __attribute__((ext_vector_type(8)));
+// the 16- and 8-byte vectors of global / LDS traffic and of the MFMA accumulators, for every unit
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 
 static __device__ unsigned g_split_overflow_tu;    // one per translation unit (no relocatable device code): see split_overflow_*
 
@@ -76,6 +80,26 @@ __device__ __forceinline__ unsigned rd_mix(unsigned x) {
 __device__ __forceinline__ bool rd_keep(unsigned long long i, unsigned s0, unsigned s1, unsigned thr) {
   const unsigned h = rd_mix(rd_mix((unsigned)i ^ s0) + (unsigned)(i >> 32) * 0x9E3779B9u + s1);
   return (h >> 8) >= thr;
+}
+
+__device__ __forceinline__ float hsum4(f32x4 v) { return (v[0] + v[1]) + (v[2] + v[3]); }
+__device__ __forceinline__ float sigmoidf(float x) { return 1.f / (1.f + expf(-x)); }
+// sum over each group of W adjacent lanes (W a power of two <= 64; 64 = the wave), in every lane of the group
+template <int W>
+__device__ __forceinline__ float group_sum(float v) {
+#pragma unroll
+  for (int o = W / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+// fp64 sum over the 256 threads of a workgroup through s_red[4] (LDS), in fixed order
+__device__ __forceinline__ double block_sum256(double v, double *s_red) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  __syncthreads();                                   // s_red may still be read from a previous call
+  if (lane == 0) s_red[wave] = v;
+  __syncthreads();
+  return s_red[0] + s_red[1] + s_red[2] + s_red[3];
 }
 
 // a pair of fp32 values -> packed bf16 (round to nearest even, x0 in the low 16 bits): the operand format of the bf16 mode
@@ -92,6 +116,19 @@ __device__ __forceinline__ void split_pair_bf16_ref(float x0, float x1, unsigned
   hi = __builtin_bit_cast(unsigned, h);
   lo = __builtin_bit_cast(unsigned, l);
 }
+// three-way split (round 4, "split3" precision): x = hi + mid + lo EXACTLY for finite normal x (8 + 8 + 8 significand bits),
+// every part a bf16 number; pairs packed like split_pair
+__device__ __forceinline__ void split3_pair_ref(float x0, float x1, unsigned &hi, unsigned &mid, unsigned &lo) {
+  unsigned h, m, l, unused;
+  split_pair_bf16_ref(x0, x1, h, m);                               // h = bf16(x), m = bf16(x - h)
+  const float r0 = (x0 - __uint_as_float(h << 16)) - __uint_as_float(m << 16);
+  const float r1 = (x1 - __uint_as_float(h & 0xffff0000u)) - __uint_as_float(m & 0xffff0000u);
+  split_pair_bf16_ref(r0, r1, l, unused);
+  hi = h, mid = m, lo = l;
+}
+// the fp32 values of the two bf16 halves of a packed pair
+__device__ __forceinline__ float bf16lo_to_f32(unsigned packed) { return __uint_as_float(packed << 16); }
+__device__ __forceinline__ float bf16hi_to_f32(unsigned packed) { return __uint_as_float(packed & 0xffff0000u); }
 // hi/lo fp16 split of two fp32 values scaled by `s` (a power of two); each result packs the pair (x0 in the low 16 bits)
 template <bool CHECK>
 __device__ __forceinline__ void split_pair_f16_ref(float x0, float x1, float s, unsigned &hi, unsigned &lo) {

@@ -34,8 +34,6 @@ struct TailArgs {
   int has_range;
 };
 
-__device__ __forceinline__ float sigmoidf(float x) { return 1.f / (1.f + expf(-x)); }
-
 // score = max_c sigmoid(hm[c]) (first maximum wins like torch.max), label = its index
 __device__ __forceinline__ void score_label(const float *hm, int ncls, float &score, int &label) {
   score = sigmoidf(hm[0]);

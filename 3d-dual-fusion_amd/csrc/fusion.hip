@@ -14,9 +14,6 @@
 // All are HBM/latency-bound gathers over <= ~10^5 rows.
 #include "common.h"
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
 namespace df3d {
 
 DF3D_SPLIT_OVERFLOW_TU(fusion)

@@ -16,9 +16,6 @@
 
 namespace df3d {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int HF_TILE = 8, HF_HALO = HF_TILE + 2, HF_HP = HF_HALO * HF_HALO, HF_C = 64, HF_KMAX = 4;
 constexpr int HF_LD = HF_HP + 1;                       // pixels per channel row in LDS (+1: rows of 10 shift the banks)
 

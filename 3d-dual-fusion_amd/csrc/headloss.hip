@@ -22,9 +22,6 @@
 
 namespace df3d {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
 DF3D_SPLIT_OVERFLOW_TU(headloss)
 
 constexpr int HR_SLOTS = 7;                    // slots per workgroup

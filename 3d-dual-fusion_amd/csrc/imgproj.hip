@@ -23,10 +23,6 @@
 
 namespace df3d {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-
 DF3D_SPLIT_OVERFLOW_TU(imgproj)
 
 constexpr int IP_CIN = 256;          // camera feature channels

@@ -35,24 +35,13 @@ struct LossArgs {
 };
 
 __device__ __forceinline__ float clamped_sigmoid(float x) {
-  const float s = 1.f / (1.f + expf(-x));
+  const float s = sigmoidf(x);
   return fminf(fmaxf(s, 1e-4f), 1.f - 1e-4f);
-}
-
-// sum over the 256 threads of a workgroup; result valid in thread 0
-__device__ __forceinline__ double block_sum(double v, double *s_red) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  __syncthreads();                                   // s_red may still be read from a previous call
-  if (lane == 0) s_red[wave] = v;
-  __syncthreads();
-  return s_red[0] + s_red[1] + s_red[2] + s_red[3];
 }
 
 // clamp(sigmoid(x), 1e-4, 1 - 1e-4) and d/dx of it (0 where the clamp is active, like torch.clamp's backward)
 __device__ __forceinline__ float clamped_sigmoid_grad(float x, float &dpdx) {
-  const float s = 1.f / (1.f + expf(-x));
+  const float s = sigmoidf(x);
   const bool inside = s >= 1e-4f && s <= 1.f - 1e-4f;
   const float p = fminf(fmaxf(s, 1e-4f), 1.f - 1e-4f);
   dpdx = inside ? p * (1.f - p) : 0.f;
@@ -64,7 +53,7 @@ __device__ __forceinline__ double task_positives(const LossArgs &a, int t, doubl
   double n = 0.0;
   const int slots = a.batch * a.max_objs;
   for (int s = threadIdx.x; s < slots; s += 256) n += a.target[t].mask[s] ? 1.0 : 0.0;
-  block_sum(n, s_red);
+  block_sum256(n, s_red);
   __syncthreads();
   return s_red[0] + s_red[1] + s_red[2] + s_red[3];
 }
@@ -106,7 +95,7 @@ __global__ __launch_bounds__(256) void loss_neg_kernel(LossArgs a, double *__res
     }
     acc += (double)s;
   }
-  const double tot = block_sum(acc, s_red);
+  const double tot = block_sum256(acc, s_red);
   if (threadIdx.x == 0) partial[(size_t)t * a.chunks + blockIdx.x] = tot;
 }
 
@@ -184,10 +173,10 @@ __global__ __launch_bounds__(256) void loss_finish_kernel(LossArgs a, const doub
     }
   }
   for (int i = threadIdx.x; i < a.chunks; i += 256) neg += partial[(size_t)t * a.chunks + i];
-  pos = block_sum(pos, s_red);
-  npos = block_sum(npos, s_red);
-  neg = block_sum(neg, s_red);
-  for (int j = 0; j < a.ncodes; ++j) elem[j] = block_sum(elem[j], s_red);
+  pos = block_sum256(pos, s_red);
+  npos = block_sum256(npos, s_red);
+  neg = block_sum256(neg, s_red);
+  for (int j = 0; j < a.ncodes; ++j) elem[j] = block_sum256(elem[j], s_red);
   if (threadIdx.x != 0) return;
   float *o = out + (size_t)t * DF3D_LOSS_FIELDS;
   const float hm_loss = npos == 0.0 ? (float)(-neg) : (float)(-(pos + neg) / npos);

@@ -35,10 +35,7 @@
 
 namespace df3d {
 
-typedef float lt_f32x4 __attribute__((ext_vector_type(4)));
-
 DF3D_SPLIT_OVERFLOW_TU(ltlayer)
-typedef unsigned int lt_u32x4 __attribute__((ext_vector_type(4)));
 #define LT_MFMA(A, B, C) DF3D_MFMA_F16(A, B, C)
 #define LT_U DF3D_ACC_UNSCALE       /* weights x activations */
 #define LT_AA DF3D_AA_UNSCALE       /* activations x activations */
@@ -58,7 +55,7 @@ constexpr int LT_PE_NVEC = 192;
 
 struct LtArgs {
   const float *x;          // [32][G][64] rows (sequence-first: row = token * G + group)
-  const lt_u32x4 *w;       // packed fragments [pair][hi | lo][lane]
+  const u32x4 *w;          // packed fragments [pair][hi | lo][lane]
   const float *vec;        // LT_NVEC floats
   float *out;              // [32][G][64]
   int G;
@@ -72,24 +69,22 @@ struct LtArgs {
 };
 
 struct LtOp {
-  lt_u32x4 hi, lo;
+  u32x4 hi, lo;
 };
 
 // eight fp32 values (two float4 of the lane) -> one MFMA operand, hi and lo parts
 // (range check without a branch per pair: split_pair_acc / split_range_flag, csrc/common.h)
-__device__ __forceinline__ LtOp lt_split(lt_f32x4 a, lt_f32x4 b, float &amax) {
+__device__ __forceinline__ LtOp lt_split(f32x4 a, f32x4 b, float &amax) {
   unsigned h[4], l[4];
   split_pair_acc(a[0], a[1], h[0], l[0], amax);
   split_pair_acc(a[2], a[3], h[1], l[1], amax);
   split_pair_acc(b[0], b[1], h[2], l[2], amax);
   split_pair_acc(b[2], b[3], h[3], l[3], amax);
   LtOp o;
-  o.hi = (lt_u32x4){h[0], h[1], h[2], h[3]};
-  o.lo = (lt_u32x4){l[0], l[1], l[2], l[3]};
+  o.hi = (u32x4){h[0], h[1], h[2], h[3]};
+  o.lo = (u32x4){l[0], l[1], l[2], l[3]};
   return o;
 }
-
-__device__ __forceinline__ float lt_sum4(lt_f32x4 v) { return (v[0] + v[1]) + (v[2] + v[3]); }
 
 // sum over the four lanes (n, g = 0..3) that hold one token
 __device__ __forceinline__ float lt_token_sum(float v) {
@@ -104,27 +99,27 @@ __device__ __forceinline__ float lt_token_max(float v) {
 }
 
 // LayerNorm over the 64 channels of the lane's token (layout T), two passes in registers
-__device__ __forceinline__ void lt_layernorm(lt_f32x4 (&t)[4], const float *gamma, const float *beta, float eps, int g) {
-  float s = (lt_sum4(t[0]) + lt_sum4(t[1])) + (lt_sum4(t[2]) + lt_sum4(t[3]));
+__device__ __forceinline__ void lt_layernorm(f32x4 (&t)[4], const float *gamma, const float *beta, float eps, int g) {
+  float s = (hsum4(t[0]) + hsum4(t[1])) + (hsum4(t[2]) + hsum4(t[3]));
   const float mean = lt_token_sum(s) * (1.f / 64.f);
   float q = 0.f;
 #pragma unroll
   for (int ct = 0; ct < 4; ++ct) {
     t[ct] -= mean;
-    q += lt_sum4(t[ct] * t[ct]);
+    q += hsum4(t[ct] * t[ct]);
   }
   const float rstd = rsqrtf(lt_token_sum(q) * (1.f / 64.f) + eps);
 #pragma unroll
   for (int ct = 0; ct < 4; ++ct) {
-    const lt_f32x4 ga = *(const lt_f32x4 *)(gamma + ct * 16 + 4 * g), be = *(const lt_f32x4 *)(beta + ct * 16 + 4 * g);
+    const f32x4 ga = *(const f32x4 *)(gamma + ct * 16 + 4 * g), be = *(const f32x4 *)(beta + ct * 16 + 4 * g);
     t[ct] = t[ct] * rstd * ga + be;
   }
 }
 
 // acc[tt] += W_frag(pair) . act^T  (transposed product: weights are the A operand; result in layout T)
-__device__ __forceinline__ void lt_gemm_t(const lt_u32x4 *Wl, int pair, int lane, const LtOp &b0, const LtOp &b1, lt_f32x4 &acc0,
-                                          lt_f32x4 &acc1) {
-  const lt_u32x4 wh = Wl[(pair * 2) * 64 + lane], wl = Wl[(pair * 2 + 1) * 64 + lane];
+__device__ __forceinline__ void lt_gemm_t(const u32x4 *Wl, int pair, int lane, const LtOp &b0, const LtOp &b1, f32x4 &acc0,
+                                          f32x4 &acc1) {
+  const u32x4 wh = Wl[(pair * 2) * 64 + lane], wl = Wl[(pair * 2 + 1) * 64 + lane];
   acc0 = LT_MFMA(wl, b0.hi, acc0);
   acc1 = LT_MFMA(wl, b1.hi, acc1);
   acc0 = LT_MFMA(wh, b0.lo, acc0);
@@ -138,7 +133,7 @@ __global__ __launch_bounds__(NW * 64) void lt_layer_kernel(LtArgs a) {
   constexpr int WBYTES = LT_WBYTES + (GATHER ? LT_PE_WBYTES : 0);
   constexpr int NVEC = LT_NVEC + (GATHER ? LT_PE_NVEC : 0);
   extern __shared__ __align__(16) unsigned char lt_smem[];
-  lt_u32x4 *Wl = (lt_u32x4 *)lt_smem;
+  u32x4 *Wl = (u32x4 *)lt_smem;
   float *vl = (float *)(lt_smem + WBYTES);
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -148,7 +143,7 @@ __global__ __launch_bounds__(NW * 64) void lt_layer_kernel(LtArgs a) {
     static_assert(TOT % (NW * 64) == 0, "weight image size");
 #pragma unroll 1
     for (int b = 0; b < PER; b += 8) {              // eight 16-byte loads in flight per thread
-      lt_u32x4 t[8];
+      u32x4 t[8];
 #pragma unroll
       for (int i = 0; i < 8; ++i) t[i] = a.w[tid + NW * 64 * ((b + i) < PER ? (b + i) : 0)];
 #pragma unroll
@@ -160,12 +155,12 @@ __global__ __launch_bounds__(NW * 64) void lt_layer_kernel(LtArgs a) {
   __syncthreads();
   const float *bqkv = vl, *bo = vl + 192, *b1 = vl + 256, *b2 = vl + 384;
   const float *g1 = vl + 448, *be1 = vl + 512, *g2 = vl + 576, *be2 = vl + 640;
-  const lt_f32x4 zero4 = (lt_f32x4){0.f, 0.f, 0.f, 0.f};
+  const f32x4 zero4 = (f32x4){0.f, 0.f, 0.f, 0.f};
 
 #pragma unroll 1
   for (int grp = blockIdx.x * NW + wave; grp < a.G; grp += gridDim.x * NW) {
     // ---- rows of the group in layout T, LayerNorm 1 ------------------------------------------------------------
-    lt_f32x4 xT[2][4];
+    f32x4 xT[2][4];
     float amax = 0.f;
     if constexpr (GATHER) {
       // x = flat[sel] + pe(xyz): the gathered point row plus the positional MLP 3 -> 32 (ReLU) -> 64 of the grouped coordinate
@@ -178,9 +173,9 @@ __global__ __launch_bounds__(NW * 64) void lt_layer_kernel(LtArgs a) {
         const size_t tok = (size_t)(tt * 16 + n) * a.G + grp;
         const float *row = a.x + (size_t)a.sel[tok] * 64 + 4 * g;
 #pragma unroll
-        for (int ct = 0; ct < 4; ++ct) xT[tt][ct] = *(const lt_f32x4 *)(row + ct * 16);
+        for (int ct = 0; ct < 4; ++ct) xT[tt][ct] = *(const f32x4 *)(row + ct * 16);
         const float px = a.gxyz[tok * 3], py = a.gxyz[tok * 3 + 1], pz = a.gxyz[tok * 3 + 2];
-        lt_f32x4 h[2];
+        f32x4 h[2];
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
           const int ch = (j >> 2) * 16 + 4 * g + (j & 3);
@@ -191,9 +186,9 @@ __global__ __launch_bounds__(NW * 64) void lt_layer_kernel(LtArgs a) {
       }
 #pragma unroll
       for (int ot = 0; ot < 4; ++ot) {
-        lt_f32x4 a0 = zero4, a1 = zero4;
+        f32x4 a0 = zero4, a1 = zero4;
         lt_gemm_t(Wl, LT_PAIRS + ot, lane, ho[0], ho[1], a0, a1);
-        const lt_f32x4 bb = *(const lt_f32x4 *)(b1p + ot * 16 + 4 * g);
+        const f32x4 bb = *(const f32x4 *)(b1p + ot * 16 + 4 * g);
         xT[0][ot] += a0 * LT_U + bb;
         xT[1][ot] += a1 * LT_U + bb;
       }
@@ -203,7 +198,7 @@ __global__ __launch_bounds__(NW * 64) void lt_layer_kernel(LtArgs a) {
       for (int tt = 0; tt < 2; ++tt) {
         const float *row = a.x + (size_t)(tt * 16 + n) * a.ts + (size_t)grp * a.gs + 4 * g;
 #pragma unroll
-        for (int ct = 0; ct < 4; ++ct) xT[tt][ct] = *(const lt_f32x4 *)(row + ct * 16);
+        for (int ct = 0; ct < 4; ++ct) xT[tt][ct] = *(const f32x4 *)(row + ct * 16);
       }
     }
     lt_layernorm(xT[0], g1, be1, a.eps1, g);
@@ -215,17 +210,17 @@ __global__ __launch_bounds__(NW * 64) void lt_layer_kernel(LtArgs a) {
       for (int s = 0; s < 2; ++s) xo[tt][s] = lt_split(xT[tt][2 * s], xT[tt][2 * s + 1], amax);
 
     // ---- self-attention, one head (= one 16-channel tile) at a time ---------------------------------------------
-    lt_f32x4 oT[2][4];
+    f32x4 oT[2][4];
 #pragma unroll
     for (int h = 0; h < 4; ++h) {
-      lt_f32x4 q[2] = {zero4, zero4}, k[2] = {zero4, zero4}, v[2] = {zero4, zero4};
+      f32x4 q[2] = {zero4, zero4}, k[2] = {zero4, zero4}, v[2] = {zero4, zero4};
 #pragma unroll
       for (int s = 0; s < 2; ++s) {
         lt_gemm_t(Wl, h * 2 + s, lane, xo[0][s], xo[1][s], q[0], q[1]);
         lt_gemm_t(Wl, (4 + h) * 2 + s, lane, xo[0][s], xo[1][s], k[0], k[1]);
         // V = x1 Wv^T: activations as the A operand, the weight fragment (same format) as B
         const int pv = (8 + h) * 2 + s;
-        const lt_u32x4 wh = Wl[(pv * 2) * 64 + lane], wl = Wl[(pv * 2 + 1) * 64 + lane];
+        const u32x4 wh = Wl[(pv * 2) * 64 + lane], wl = Wl[(pv * 2 + 1) * 64 + lane];
         v[0] = LT_MFMA(xo[0][s].lo, wh, v[0]);
         v[1] = LT_MFMA(xo[1][s].lo, wh, v[1]);
         v[0] = LT_MFMA(xo[0][s].hi, wl, v[0]);
@@ -234,25 +229,25 @@ __global__ __launch_bounds__(NW * 64) void lt_layer_kernel(LtArgs a) {
         v[1] = LT_MFMA(xo[1][s].hi, wh, v[1]);
         LT_FENCE();
       }
-      const lt_f32x4 bq = *(const lt_f32x4 *)(bqkv + h * 16 + 4 * g), bk = *(const lt_f32x4 *)(bqkv + 64 + h * 16 + 4 * g);
+      const f32x4 bq = *(const f32x4 *)(bqkv + h * 16 + 4 * g), bk = *(const f32x4 *)(bqkv + 64 + h * 16 + 4 * g);
       const float bv = bqkv[128 + h * 16 + n];
       // S^T[key][query] = sum_d K[key][d] Q[query][d] / 4
-      lt_u32x4 ka1[2], ka2[2], qb1[2], qb2[2];
+      u32x4 ka1[2], ka2[2], qb1[2], qb2[2];
 #pragma unroll
       for (int tt = 0; tt < 2; ++tt) {
-        const lt_f32x4 qq = (q[tt] * LT_U + bq) * 0.25f, kk = k[tt] * LT_U + bk;
+        const f32x4 qq = (q[tt] * LT_U + bq) * 0.25f, kk = k[tt] * LT_U + bk;
         unsigned h01, l01, h23, l23;
         split_pair_acc(kk[0], kk[1], h01, l01, amax);
         split_pair_acc(kk[2], kk[3], h23, l23, amax);
-        ka1[tt] = (lt_u32x4){h01, h23, l01, l23};
-        ka2[tt] = (lt_u32x4){h01, h23, 0u, 0u};
+        ka1[tt] = (u32x4){h01, h23, l01, l23};
+        ka2[tt] = (u32x4){h01, h23, 0u, 0u};
         split_pair_acc(qq[0], qq[1], h01, l01, amax);
         split_pair_acc(qq[2], qq[3], h23, l23, amax);
-        qb1[tt] = (lt_u32x4){h01, h23, h01, h23};
-        qb2[tt] = (lt_u32x4){l01, l23, 0u, 0u};
+        qb1[tt] = (u32x4){h01, h23, h01, h23};
+        qb2[tt] = (u32x4){l01, l23, 0u, 0u};
         v[tt] = v[tt] * LT_U + bv;
       }
-      lt_f32x4 sc[2][2];                            // [key tile][query tile]
+      f32x4 sc[2][2];                               // [key tile][query tile]
 #pragma unroll
       for (int kt = 0; kt < 2; ++kt)
 #pragma unroll
@@ -265,7 +260,7 @@ __global__ __launch_bounds__(NW * 64) void lt_layer_kernel(LtArgs a) {
 #pragma unroll
       for (int qt = 0; qt < 2; ++qt) {
         // softmax over the 32 keys of query 16 qt + n: 8 values here, the rest in the lanes n + 16 g'
-        lt_f32x4 p0 = sc[0][qt] * LT_AA, p1 = sc[1][qt] * LT_AA;
+        f32x4 p0 = sc[0][qt] * LT_AA, p1 = sc[1][qt] * LT_AA;
         float m = fmaxf(fmaxf(fmaxf(p0[0], p0[1]), fmaxf(p0[2], p0[3])), fmaxf(fmaxf(p1[0], p1[1]), fmaxf(p1[2], p1[3])));
         m = lt_token_max(m);
 #pragma unroll
@@ -273,9 +268,9 @@ __global__ __launch_bounds__(NW * 64) void lt_layer_kernel(LtArgs a) {
           p0[r] = __expf(p0[r] - m);
           p1[r] = __expf(p1[r] - m);
         }
-        const float inv = 1.f / lt_token_sum(lt_sum4(p0) + lt_sum4(p1));
+        const float inv = 1.f / lt_token_sum(hsum4(p0) + hsum4(p1));
         const LtOp pb = lt_split(p0 * inv, p1 * inv, amax);
-        lt_f32x4 o = LT_MFMA(va.lo, pb.hi, zero4);
+        f32x4 o = LT_MFMA(va.lo, pb.hi, zero4);
         o = LT_MFMA(va.hi, pb.lo, o);
         oT[qt][h] = LT_MFMA(va.hi, pb.hi, o) * LT_AA;
         LT_FENCE();
@@ -291,10 +286,10 @@ __global__ __launch_bounds__(NW * 64) void lt_layer_kernel(LtArgs a) {
         for (int s = 0; s < 2; ++s) oo[tt][s] = lt_split(oT[tt][2 * s], oT[tt][2 * s + 1], amax);
 #pragma unroll
       for (int ot = 0; ot < 4; ++ot) {
-        lt_f32x4 a0 = zero4, a1 = zero4;
+        f32x4 a0 = zero4, a1 = zero4;
 #pragma unroll
         for (int s = 0; s < 2; ++s) lt_gemm_t(Wl, 24 + ot * 2 + s, lane, oo[0][s], oo[1][s], a0, a1);
-        const lt_f32x4 bb = *(const lt_f32x4 *)(bo + ot * 16 + 4 * g);
+        const f32x4 bb = *(const f32x4 *)(bo + ot * 16 + 4 * g);
         xT[0][ot] += a0 * LT_U + bb;
         xT[1][ot] += a1 * LT_U + bb;
         LT_FENCE();
@@ -308,20 +303,20 @@ __global__ __launch_bounds__(NW * 64) void lt_layer_kernel(LtArgs a) {
       for (int s = 0; s < 2; ++s) xo[tt][s] = lt_split(xT[tt][2 * s], xT[tt][2 * s + 1], amax);
 
     // ---- feed-forward 64 -> 128 -> 64 in two hidden chunks of 64, + residual (x3) ---------------------------------
-    lt_f32x4 yT[2][4];
+    f32x4 yT[2][4];
 #pragma unroll
     for (int tt = 0; tt < 2; ++tt)
 #pragma unroll
       for (int ot = 0; ot < 4; ++ot) yT[tt][ot] = zero4;
 #pragma unroll
     for (int c = 0; c < 2; ++c) {
-      lt_f32x4 hT[2][4];
+      f32x4 hT[2][4];
 #pragma unroll
       for (int ht = 0; ht < 4; ++ht) {
-        lt_f32x4 a0 = zero4, a1 = zero4;
+        f32x4 a0 = zero4, a1 = zero4;
 #pragma unroll
         for (int s = 0; s < 2; ++s) lt_gemm_t(Wl, 32 + (c * 4 + ht) * 2 + s, lane, xo[0][s], xo[1][s], a0, a1);
-        const lt_f32x4 bb = *(const lt_f32x4 *)(b1 + (c * 4 + ht) * 16 + 4 * g);
+        const f32x4 bb = *(const f32x4 *)(b1 + (c * 4 + ht) * 16 + 4 * g);
         a0 = a0 * LT_U + bb;
         a1 = a1 * LT_U + bb;
 #pragma unroll
@@ -356,7 +351,7 @@ __global__ __launch_bounds__(NW * 64) void lt_layer_kernel(LtArgs a) {
       }
 #pragma unroll
       for (int ot = 0; ot < 4; ++ot)
-        *(lt_f32x4 *)(row + ot * 16) = xT[tt][ot] + yT[tt][ot] * LT_U + *(const lt_f32x4 *)(b2 + ot * 16 + 4 * g);
+        *(f32x4 *)(row + ot * 16) = xT[tt][ot] + yT[tt][ot] * LT_U + *(const f32x4 *)(b2 + ot * 16 + 4 * g);
     }
   }
 }
@@ -405,7 +400,7 @@ extern "C" int df3d_lt_layer(const float *x, int L, int G, int C, int heads, int
                  heads, ffn);
   DF3D_CHECK_ARG(G >= 0, "lt_layer: bad group count");
   if (G == 0) return DF3D_OK;
-  LtArgs a = {x, (const lt_u32x4 *)packed, vec, out, G, eps1, eps2, group_major ? 64LL : (long long)G * 64,
+  LtArgs a = {x, (const u32x4 *)packed, vec, out, G, eps1, eps2, group_major ? 64LL : (long long)G * 64,
               group_major ? 32LL * 64 : 64LL, nullptr, nullptr, nullptr};
   return lt_launch<false, false>(a, stream);
 }
@@ -415,7 +410,7 @@ extern "C" int df3d_lt_layer_gather(const float *points, const long long *sel, c
   hipStream_t stream = (hipStream_t)stream_;
   DF3D_CHECK_ARG(points && sel && gxyz && packed && vec && out && G >= 0, "lt_layer_gather: bad argument");
   if (G == 0) return DF3D_OK;
-  LtArgs a = {points, (const lt_u32x4 *)packed, vec, out, G, eps1, eps2, (long long)G * 64, 64LL, sel, gxyz, nullptr};
+  LtArgs a = {points, (const u32x4 *)packed, vec, out, G, eps1, eps2, (long long)G * 64, 64LL, sel, gxyz, nullptr};
   return lt_launch<true, false>(a, stream);
 }
 
@@ -424,6 +419,6 @@ extern "C" int df3d_lt_layer_scatter(const float *x, int G, const void *packed, 
   hipStream_t stream = (hipStream_t)stream_;
   DF3D_CHECK_ARG(x && dst && packed && vec && points && G >= 0, "lt_layer_scatter: bad argument");
   if (G == 0) return DF3D_OK;
-  LtArgs a = {x, (const lt_u32x4 *)packed, vec, points, G, eps1, eps2, (long long)G * 64, 64LL, nullptr, nullptr, dst};
+  LtArgs a = {x, (const u32x4 *)packed, vec, points, G, eps1, eps2, (long long)G * 64, 64LL, nullptr, nullptr, dst};
   return lt_launch<false, true>(a, stream);
 }

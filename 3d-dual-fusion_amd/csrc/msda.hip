@@ -19,8 +19,6 @@
 
 namespace df3d {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 struct MsdaArgs {
   const float *value;
   const int64_t *shapes, *lstart;
@@ -152,8 +150,6 @@ __device__ __forceinline__ void atomic_add4(float *p, f32x4 v) {
   unsafeAtomicAdd(p + 2, v[2]);
   unsafeAtomicAdd(p + 3, v[3]);
 }
-
-__device__ __forceinline__ float hsum4(f32x4 v) { return (v[0] + v[1]) + (v[2] + v[3]); }
 
 // BINNED: the value gradient is accumulated by msda_bin_* below (LDS tiles); this kernel then only computes the location /
 // weight gradients and notes which (query, head) groups carry a gradient at all (a.nz)

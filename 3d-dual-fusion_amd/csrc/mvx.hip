@@ -17,8 +17,6 @@
 
 namespace df3d {
 
-typedef float mv_f32x4 __attribute__((ext_vector_type(4)));
-
 struct MvxArgs {
   const int32_t *ind;       // [n, 4] (b, z, y, x)
   int n, B;
@@ -112,7 +110,7 @@ __global__ __launch_bounds__(256) void mvx_sample_kernel(MvxArgs a) {
   const bool fin = isfinite(u) && isfinite(v) && fabsf(u) < 9.0e18f && fabsf(v) < 9.0e18f;
   const long long pu = fin ? (long long)u : -1, pv = fin ? (long long)v : -1;
   const bool ok = pv >= 0 && pv < a.h && pu >= 0 && pu < a.w;
-  mv_f32x4 f = (mv_f32x4){0.f, 0.f, 0.f, 0.f};
+  f32x4 f = (f32x4){0.f, 0.f, 0.f, 0.f};
   if (ok) {
     const MvxTap ty = mvx_tap(pv, a.Hin, a.h, a.sy), tx = mvx_tap(pu, a.Win, a.w, a.sx);
     const size_t plane = (size_t)a.Hin * a.Win;
@@ -131,8 +129,8 @@ __global__ __launch_bounds__(256) void mvx_sample_kernel(MvxArgs a) {
       f[c] = r + ty.lam * bot;
     }
   }
-  if (a.add) f = *(const mv_f32x4 *)(a.add + (size_t)i * a.C + c4) + f;
-  *(mv_f32x4 *)(a.out + orow * a.C + c4) = f;
+  if (a.add) f = *(const f32x4 *)(a.add + (size_t)i * a.C + c4) + f;
+  *(f32x4 *)(a.out + orow * a.C + c4) = f;
 }
 
 }  // namespace df3d

@@ -13,115 +13,35 @@
 // results differ from its CPU path (iou3d_cpu.cpp) only through the last ulps of cosf / sinf / atan2f.
 #include "common.h"
 
-#pragma clang fp contract(off)
+#pragma clang fp contract(off)         // before the clipping code: bev_overlap.h relies on it
+#include "bev_overlap.h"
 
 namespace df3d {
 
-struct Pt {
-  float x, y;
+// box = [x, y, z, dx, dy, dz, angle] (iou3d_nms_kernel.cu:36-245)
+struct CenterBox {
+  static __device__ __forceinline__ bool contains(const float *box, BevPt p) {
+    const float margin = 1e-2f;
+    const float ca = cosf(-box[6]), sa = sinf(-box[6]);
+    const float rx = (p.x - box[0]) * ca + (p.y - box[1]) * (-sa);
+    const float ry = (p.x - box[0]) * sa + (p.y - box[1]) * ca;
+    return fabsf(rx) < box[3] / 2 + margin && fabsf(ry) < box[4] / 2 + margin;
+  }
+  static __device__ __forceinline__ void corners(const float *box, BevPt *c) {
+    const float hx = box[3] / 2, hy = box[4] / 2, ca = cosf(box[6]), sa = sinf(box[6]);
+    const float x1 = box[0] - hx, y1 = box[1] - hy, x2 = box[0] + hx, y2 = box[1] + hy;
+    const float px[4] = {x1, x2, x2, x1}, py[4] = {y1, y1, y2, y2};
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      c[k].x = (px[k] - box[0]) * ca + (py[k] - box[1]) * (-sa) + box[0];
+      c[k].y = (px[k] - box[0]) * sa + (py[k] - box[1]) * ca + box[1];
+    }
+    c[4] = c[0];
+  }
 };
 
-__device__ __forceinline__ float cross3(Pt p1, Pt p2, Pt p0) {
-  return (p1.x - p0.x) * (p2.y - p0.y) - (p2.x - p0.x) * (p1.y - p0.y);
-}
-
-__device__ __forceinline__ bool rect_cross(Pt p1, Pt p2, Pt q1, Pt q2) {
-  return fminf(p1.x, p2.x) <= fmaxf(q1.x, q2.x) && fminf(q1.x, q2.x) <= fmaxf(p1.x, p2.x) &&
-         fminf(p1.y, p2.y) <= fmaxf(q1.y, q2.y) && fminf(q1.y, q2.y) <= fmaxf(p1.y, p2.y);
-}
-
-__device__ __forceinline__ bool in_box2d(const float *box, Pt p) {
-  const float margin = 1e-2f;
-  const float ca = cosf(-box[6]), sa = sinf(-box[6]);
-  const float rx = (p.x - box[0]) * ca + (p.y - box[1]) * (-sa);
-  const float ry = (p.x - box[0]) * sa + (p.y - box[1]) * ca;
-  return fabsf(rx) < box[3] / 2 + margin && fabsf(ry) < box[4] / 2 + margin;
-}
-
-__device__ __forceinline__ bool intersection(Pt p1, Pt p0, Pt q1, Pt q0, Pt &ans) {
-  if (!rect_cross(p0, p1, q0, q1)) return false;
-  const float s1 = cross3(q0, p1, p0), s2 = cross3(p1, q1, p0);
-  const float s3 = cross3(p0, q1, q0), s4 = cross3(q1, p1, q0);
-  if (!(s1 * s2 > 0 && s3 * s4 > 0)) return false;
-  const float s5 = cross3(q1, p1, p0);
-  if (fabsf(s5 - s1) > 1e-8f) {
-    ans.x = (s5 * q0.x - s1 * q1.x) / (s5 - s1);
-    ans.y = (s5 * q0.y - s1 * q1.y) / (s5 - s1);
-  } else {
-    const float a0 = p0.y - p1.y, b0 = p1.x - p0.x, c0 = p0.x * p1.y - p1.x * p0.y;
-    const float a1 = q0.y - q1.y, b1 = q1.x - q0.x, c1 = q0.x * q1.y - q1.x * q0.y;
-    const float D = a0 * b1 - a1 * b0;
-    ans.x = (b0 * c1 - b1 * c0) / D;
-    ans.y = (a1 * c0 - a0 * c1) / D;
-  }
-  return true;
-}
-
-__device__ __forceinline__ void corners(const float *box, Pt *c) {
-  const float hx = box[3] / 2, hy = box[4] / 2, ca = cosf(box[6]), sa = sinf(box[6]);
-  const float x1 = box[0] - hx, y1 = box[1] - hy, x2 = box[0] + hx, y2 = box[1] + hy;
-  const float px[4] = {x1, x2, x2, x1}, py[4] = {y1, y1, y2, y2};
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    c[k].x = (px[k] - box[0]) * ca + (py[k] - box[1]) * (-sa) + box[0];
-    c[k].y = (px[k] - box[0]) * sa + (py[k] - box[1]) * ca + box[1];
-  }
-  c[4] = c[0];
-}
-
-__device__ float box_overlap(const float *a, const float *b) {
-  Pt ca[5], cb[5], pts[16], ctr = {0.f, 0.f};
-  int cnt = 0;
-  corners(a, ca);
-  corners(b, cb);
-  for (int i = 0; i < 4; ++i)
-    for (int j = 0; j < 4; ++j) {
-      Pt x;
-      if (intersection(ca[i + 1], ca[i], cb[j + 1], cb[j], x)) {
-        pts[cnt] = x;
-        ctr.x += x.x;
-        ctr.y += x.y;
-        cnt++;
-      }
-    }
-  for (int k = 0; k < 4; ++k) {
-    if (in_box2d(a, cb[k])) {
-      ctr.x += cb[k].x;
-      ctr.y += cb[k].y;
-      pts[cnt++] = cb[k];
-    }
-    if (in_box2d(b, ca[k])) {
-      ctr.x += ca[k].x;
-      ctr.y += ca[k].y;
-      pts[cnt++] = ca[k];
-    }
-  }
-  if (cnt < 3) return 0.f;                 // the reference's fan over fewer than three vertices is empty as well
-  ctr.x /= cnt;
-  ctr.y /= cnt;
-  float ang[16];
-  for (int i = 0; i < cnt; ++i) ang[i] = atan2f(pts[i].y - ctr.y, pts[i].x - ctr.x);
-  for (int j = 0; j < cnt - 1; ++j)        // the reference's bubble sort (same swaps: the keys do not change)
-    for (int i = 0; i < cnt - j - 1; ++i)
-      if (ang[i] > ang[i + 1]) {
-        Pt t = pts[i];
-        pts[i] = pts[i + 1];
-        pts[i + 1] = t;
-        float u = ang[i];
-        ang[i] = ang[i + 1];
-        ang[i + 1] = u;
-      }
-  float area = 0.f;
-  for (int k = 0; k < cnt - 1; ++k) {
-    const float ax = pts[k].x - pts[0].x, ay = pts[k].y - pts[0].y;
-    const float bx = pts[k + 1].x - pts[0].x, by = pts[k + 1].y - pts[0].y;
-    area += ax * by - ay * bx;
-  }
-  return fabsf(area) / 2.0f;
-}
-
 __device__ __forceinline__ float iou_rotated(const float *a, const float *b) {
-  const float sa = a[3] * a[4], sb = b[3] * b[4], so = box_overlap(a, b);
+  const float sa = a[3] * a[4], sb = b[3] * b[4], so = bev_overlap<CenterBox>(a, b);
   return so / fmaxf(sa + sb - so, 1e-8f);
 }
 
@@ -152,7 +72,7 @@ __global__ __launch_bounds__(256) void boxes_pairwise_kernel(const float *__rest
     b[e] = B[(size_t)j * 7 + e];
   }
   float v = 0.f;
-  if (!far_apart(a, b)) v = mode ? iou_rotated(a, b) : box_overlap(a, b);
+  if (!far_apart(a, b)) v = mode ? iou_rotated(a, b) : bev_overlap<CenterBox>(a, b);
   out[(size_t)i * nb + j] = v;
 }
 

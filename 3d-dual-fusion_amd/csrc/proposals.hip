@@ -183,8 +183,6 @@ struct RoiArgs {
   float score_thr;
 };
 
-__device__ __forceinline__ float sigmoid32(float x) { return 1.f / (1.f + expf(-x)); }
-
 // one thread per RoI: batch_box_preds, and the selection key of its score.  The counts of the top-k select are the
 // per-frame numbers of RoIs that pass the threshold.
 __global__ __launch_bounds__(256) void roi_decode_kernel(RoiArgs a, float *__restrict__ box_preds,
@@ -204,8 +202,8 @@ __global__ __launch_bounds__(256) void roi_decode_kernel(RoiArgs a, float *__res
 #pragma unroll
   for (int e = 0; e < 7; ++e) box_preds[i * 7 + e] = g[e];
   const float *c = a.cls + i * a.ld_cls;
-  float score = sigmoid32(c[0]);
-  for (int e = 1; e < a.C; ++e) score = fmaxf(score, sigmoid32(c[e]));
+  float score = sigmoidf(c[0]);
+  for (int e = 1; e < a.C; ++e) score = fmaxf(score, sigmoidf(c[e]));
   unsigned long long key = ~0ull;
   if (score >= a.score_thr)      // sigmoid scores lie in [0, 1]: descending score = ascending 0x3F800000 - bits
     key = ((unsigned long long)b << 56) | ((unsigned long long)(0x3F800000u - __float_as_uint(score)) << 24) | (unsigned)n;
@@ -243,8 +241,8 @@ __global__ __launch_bounds__(128) void final_compact_kernel(RoiArgs a, const flo
       float raw;
       int label;
       logit_label(a.cls + i * a.ld_cls, a.C, raw, label);          // sigmoid is monotonic: the arg-max of the logits
-      float score = sigmoid32(a.cls[i * a.ld_cls]);
-      for (int e = 1; e < a.C; ++e) score = fmaxf(score, sigmoid32(a.cls[i * a.ld_cls + e]));
+      float score = sigmoidf(a.cls[i * a.ld_cls]);
+      for (int e = 1; e < a.C; ++e) score = fmaxf(score, sigmoidf(a.cls[i * a.ld_cls + e]));
       out_scores[o] = a.raw_score ? raw : score;
       out_labels[o] = a.roi_labels ? a.roi_labels[i] : (long long)(label + 1);
     } else {

@@ -21,14 +21,11 @@
 
 namespace df3d {
 
-typedef float rl_f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int rl_u32x4 __attribute__((ext_vector_type(4)));
-
 #define RL_MFMA(A, B, C) DF3D_MFMA_F16(A, B, C)
 
 struct RowLinArgs {
   const float *x0, *x1, *x2;      // [rows, cin]; x1 / x2 may be null
-  const rl_u32x4 *w;              // packed [kb][ct][hi|lo][lane] (column ct * 16 + n, channels kb * 32 + g * 8 ..): fp16 pairs of 2^7 w
+  const u32x4 *w;                 // packed [kb][ct][hi|lo][lane] (column ct * 16 + n, channels kb * 32 + g * 8 ..): fp16 pairs of 2^7 w
   const float *bias;              // [ct * 16] or null
   float *out0, *out1;             // columns [0, n0) -> out0 (row stride ld0), [n0, n0 + n1) -> out1
   const float *ln_res, *ln_gamma, *ln_beta;   // LayerNorm(ln_res + y) over n0 == CT * 16 columns, or null
@@ -37,7 +34,7 @@ struct RowLinArgs {
   float eps;
 };
 
-__device__ __forceinline__ void rl_split8(rl_f32x4 a, rl_f32x4 b, rl_u32x4 &hi, rl_u32x4 &lo) {
+__device__ __forceinline__ void rl_split8(f32x4 a, f32x4 b, u32x4 &hi, u32x4 &lo) {
   // (unchecked: query rows beyond fp16's range leave as inf / NaN rows, which the next checked split reports)
   split_pair_nc(a[0], a[1], hi[0], lo[0]);
   split_pair_nc(a[2], a[3], hi[1], lo[1]);
@@ -50,7 +47,7 @@ __global__ __launch_bounds__(256, 2) void rows_linear_kernel(RowLinArgs a) {
   constexpr int KB = CIN / 32;
   constexpr int WQ = KB * CT * 2 * 64;
   extern __shared__ __align__(16) unsigned char rl_smem[];
-  rl_u32x4 *Wl = (rl_u32x4 *)rl_smem;
+  u32x4 *Wl = (u32x4 *)rl_smem;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int g = lane >> 4, n = lane & 15;
   {                                                // filter bank -> LDS, eight 16-byte loads in flight per thread
@@ -58,7 +55,7 @@ __global__ __launch_bounds__(256, 2) void rows_linear_kernel(RowLinArgs a) {
     static_assert(WQ % 256 == 0 && PER % 4 == 0, "filter bank size");
 #pragma unroll 1
     for (int b = 0; b < PER; b += 8) {
-      rl_u32x4 t[8];
+      u32x4 t[8];
 #pragma unroll
       for (int i = 0; i < 8; ++i) t[i] = a.w[tid + 256 * ((b + i) < PER ? (b + i) : 0)];
 #pragma unroll
@@ -74,23 +71,23 @@ __global__ __launch_bounds__(256, 2) void rows_linear_kernel(RowLinArgs a) {
     const float *p0 = a.x0 + row * CIN + g * 8;
     const float *p1 = a.x1 ? a.x1 + row * CIN + g * 8 : nullptr;
     const float *p2 = a.x2 ? a.x2 + row * CIN + g * 8 : nullptr;
-    rl_f32x4 acc[CT];
+    f32x4 acc[CT];
 #pragma unroll
-    for (int ct = 0; ct < CT; ++ct) acc[ct] = (rl_f32x4){0.f, 0.f, 0.f, 0.f};
+    for (int ct = 0; ct < CT; ++ct) acc[ct] = (f32x4){0.f, 0.f, 0.f, 0.f};
     // one 32-channel block at a time (the loads of the next block are issued before this block's matrix work; more
     // unrolling only spills: the first version held the whole row and the filter fragments in registers, 256 VGPRs + scratch)
-    rl_f32x4 u0 = *(const rl_f32x4 *)p0, u1 = *(const rl_f32x4 *)(p0 + 4), v0 = u0, v1 = u0, w0 = u0, w1 = u0;
+    f32x4 u0 = *(const f32x4 *)p0, u1 = *(const f32x4 *)(p0 + 4), v0 = u0, v1 = u0, w0 = u0, w1 = u0;
     if (p2) {
-      w0 = *(const rl_f32x4 *)p2;
-      w1 = *(const rl_f32x4 *)(p2 + 4);
+      w0 = *(const f32x4 *)p2;
+      w1 = *(const f32x4 *)(p2 + 4);
     }
     if (p1) {
-      v0 = *(const rl_f32x4 *)p1;
-      v1 = *(const rl_f32x4 *)(p1 + 4);
+      v0 = *(const f32x4 *)p1;
+      v1 = *(const f32x4 *)(p1 + 4);
     }
 #pragma unroll 1
     for (int kb = 0; kb < KB; ++kb) {
-      rl_f32x4 a00 = u0, a01 = u1, b0 = v0, b1 = v1;
+      f32x4 a00 = u0, a01 = u1, b0 = v0, b1 = v1;
       if (p2) {
         a00 += w0;
         a01 += w1;
@@ -98,27 +95,27 @@ __global__ __launch_bounds__(256, 2) void rows_linear_kernel(RowLinArgs a) {
         b1 += w1;
       }
       if (kb + 1 < KB) {                             // next block's operands
-        u0 = *(const rl_f32x4 *)(p0 + (kb + 1) * 32);
-        u1 = *(const rl_f32x4 *)(p0 + (kb + 1) * 32 + 4);
+        u0 = *(const f32x4 *)(p0 + (kb + 1) * 32);
+        u1 = *(const f32x4 *)(p0 + (kb + 1) * 32 + 4);
         if (p2) {
-          w0 = *(const rl_f32x4 *)(p2 + (kb + 1) * 32);
-          w1 = *(const rl_f32x4 *)(p2 + (kb + 1) * 32 + 4);
+          w0 = *(const f32x4 *)(p2 + (kb + 1) * 32);
+          w1 = *(const f32x4 *)(p2 + (kb + 1) * 32 + 4);
         }
         if (p1) {
-          v0 = *(const rl_f32x4 *)(p1 + (kb + 1) * 32);
-          v1 = *(const rl_f32x4 *)(p1 + (kb + 1) * 32 + 4);
+          v0 = *(const f32x4 *)(p1 + (kb + 1) * 32);
+          v1 = *(const f32x4 *)(p1 + (kb + 1) * 32 + 4);
         }
       }
-      rl_u32x4 h0, l0, h1, l1;
+      u32x4 h0, l0, h1, l1;
       rl_split8(a00, a01, h0, l0);
       h1 = h0, l1 = l0;
       if (p1) rl_split8(a00 + b0, a01 + b1, h1, l1);  // (x0 + x2) + (x1 + x2): the reference's association
-      const rl_u32x4 *wb = Wl + (size_t)kb * CT * 128 + lane;
+      const u32x4 *wb = Wl + (size_t)kb * CT * 128 + lane;
 #pragma unroll
       for (int ct = 0; ct < CT; ++ct) {
-        const rl_u32x4 bh = wb[(ct * 2) * 64], bl = wb[(ct * 2 + 1) * 64];
+        const u32x4 bh = wb[(ct * 2) * 64], bl = wb[(ct * 2 + 1) * 64];
         const bool second = ct >= a.csplit;
-        const rl_u32x4 ah = second ? h1 : h0, al = second ? l1 : l0;
+        const u32x4 ah = second ? h1 : h0, al = second ? l1 : l0;
         acc[ct] = RL_MFMA(al, bh, acc[ct]);
         acc[ct] = RL_MFMA(ah, bl, acc[ct]);
         acc[ct] = RL_MFMA(ah, bh, acc[ct]);
@@ -215,7 +212,7 @@ extern "C" int df3d_rows_linear(const float *x0, const float *x1, const float *x
   if (rows == 0) return DF3D_OK;
   const int ct = (cout + 15) / 16;
   if (ln_res) DF3D_CHECK_ARG(ln_gamma && ln_beta && n0 == ct * 16 && n1 == 0 && ld0 >= n0, "rows_linear: LayerNorm needs the full row");
-  RowLinArgs a = {x0, x1, x2, (const rl_u32x4 *)packed, bias, out0, out1, ln_res, ln_gamma, ln_beta, rows,
+  RowLinArgs a = {x0, x1, x2, (const u32x4 *)packed, bias, out0, out1, ln_res, ln_gamma, ln_beta, rows,
                   csplit_cols / 16, ld0, n0, ld1, n1, eps};
   int rc;
   if (cin == 128) {

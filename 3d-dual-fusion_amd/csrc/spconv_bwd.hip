@@ -22,8 +22,6 @@
 
 namespace df3d {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 DF3D_SPLIT_OVERFLOW_TU(spconv_bwd)
 
 __global__ __launch_bounds__(256) void invert_fill_kernel(int32_t *__restrict__ inv, size_t n) {
@@ -324,18 +322,8 @@ static void launch_wgrad(const WgradArgs &a, int kvol, hipStream_t stream) {
 // i, row i) -- the weight gradient of a linear layer over rows (df3d_rows_grad_weights).
 typedef short w3_s16x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 w3_bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned int w3_u32x2 __attribute__((ext_vector_type(2)));
 
 constexpr int W3_STAGE = 32, W3_BATCH = 256, W3_LIST = W3_BATCH + W3_STAGE;
-
-__device__ __forceinline__ void w3_split_pair(float x0, float x1, unsigned &hi, unsigned &mid, unsigned &lo) {
-  unsigned h, m, l, unused;
-  split_pair_bf16_ref(x0, x1, h, m);
-  const float r0 = (x0 - __uint_as_float(h << 16)) - __uint_as_float(m << 16);
-  const float r1 = (x1 - __uint_as_float(h & 0xffff0000u)) - __uint_as_float(m & 0xffff0000u);
-  split_pair_bf16_ref(r0, r1, l, unused);
-  hi = h, mid = m, lo = l;
-}
 
 // NP = 2 (second half of round 5): fp16 PAIRS instead of three bf16 parts -- three products, two stored parts.  Activations
 // carry the fixed scale 2^5 of every split kernel; a gradient operand carries the power-of-two block scale of its tensor
@@ -402,7 +390,7 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void wgrad_split3_kernel(WgradArgs
       unsigned h0, h1, unused;
       split_pair_bf16_ref(v[0], v[1], h0, unused);
       split_pair_bf16_ref(v[2], v[3], h1, unused);
-      *(w3_u32x2 *)d = (w3_u32x2){h0, h1};
+      *(u32x2 *)d = (u32x2){h0, h1};
     } else if constexpr (NP == 2) {
       unsigned h0, l0, h1, l1;
       v *= sc;
@@ -411,15 +399,15 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void wgrad_split3_kernel(WgradArgs
       if (nan_probe != nan_probe) amax = __builtin_inff();       // anywhere in the piece raises the flag like an overflow
       split_pair_f16_ref<false>(v[0], v[1], 1.f, h0, l0);
       split_pair_f16_ref<false>(v[2], v[3], 1.f, h1, l1);
-      *(w3_u32x2 *)d = (w3_u32x2){h0, h1};
-      *(w3_u32x2 *)(d + imb) = (w3_u32x2){l0, l1};
+      *(u32x2 *)d = (u32x2){h0, h1};
+      *(u32x2 *)(d + imb) = (u32x2){l0, l1};
     } else {
       unsigned h0, m0, l0, h1, m1, l1;
-      w3_split_pair(v[0], v[1], h0, m0, l0);
-      w3_split_pair(v[2], v[3], h1, m1, l1);
-      *(w3_u32x2 *)d = (w3_u32x2){h0, h1};
-      *(w3_u32x2 *)(d + imb) = (w3_u32x2){m0, m1};
-      *(w3_u32x2 *)(d + 2 * imb) = (w3_u32x2){l0, l1};
+      split3_pair_ref(v[0], v[1], h0, m0, l0);
+      split3_pair_ref(v[2], v[3], h1, m1, l1);
+      *(u32x2 *)d = (u32x2){h0, h1};
+      *(u32x2 *)(d + imb) = (u32x2){m0, m1};
+      *(u32x2 *)(d + 2 * imb) = (u32x2){l0, l1};
     }
   };
   auto stash = [&]() {

@@ -28,9 +28,6 @@
 
 namespace df3d {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 int timing_rec_begin(int cin, int cout, int kvol, int n_out, const int32_t *nbr, int split,
@@ -38,18 +35,6 @@ int timing_rec_begin(int cin, int cout, int kvol, int n_out, const int32_t *nbr,
 void timing_rec_end(int rec, hipStream_t stream);
 
 DF3D_SPLIT_OVERFLOW_TU(spconv_split)
-
-// three-way split (round 4, "split3" precision): x = hi + mid + lo EXACTLY for finite normal x (8 + 8 + 8 significand bits),
-// every part a bf16 number; pairs packed like split_pair
-__device__ __forceinline__ void split3_pair_ref(float x0, float x1, unsigned &hi, unsigned &mid, unsigned &lo) {
-  unsigned h, m;
-  split_pair_bf16(x0, x1, h, m);                                   // h = bf16(x), m = bf16(x - h)
-  const float r0 = (x0 - __uint_as_float(h << 16)) - __uint_as_float(m << 16);
-  const float r1 = (x1 - __uint_as_float(h & 0xffff0000u)) - __uint_as_float(m & 0xffff0000u);
-  unsigned l, unused;
-  split_pair_bf16(r0, r1, l, unused);
-  hi = h, mid = m, lo = l;
-}
 
 // (outputs may be vector elements, which cannot bind to references)
 #define split3_pair(x0, x1, HI, MID, LO)                         \
@@ -60,9 +45,6 @@ __device__ __forceinline__ void split3_pair_ref(float x0, float x1, unsigned &hi
     (MID) = s3_m__;                                              \
     (LO) = s3_l__;                                               \
   } while (0)
-
-__device__ __forceinline__ float bf16lo_to_f32(unsigned packed) { return __uint_as_float(packed << 16); }
-__device__ __forceinline__ float bf16hi_to_f32(unsigned packed) { return __uint_as_float(packed & 0xffff0000u); }
 
 // ---- fp32 rows -> bf16 rows (round to nearest even; the `hi` half of the split) --------------------------
 __global__ __launch_bounds__(256) void bf16_rows_kernel(const float *__restrict__ x, size_t nblk, u32x4 *__restrict__ out) {

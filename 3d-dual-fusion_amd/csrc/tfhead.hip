@@ -24,8 +24,6 @@
 
 namespace df3d {
 
-__device__ __forceinline__ float tf_sigmoid(float x) { return 1.f / (1.f + expf(-x)); }
-
 struct ProposalArgs {
   const float *heat;       // [B*H*W, ld] logits
   int ld, batch, C, H, W, pad;
@@ -35,13 +33,13 @@ struct ProposalArgs {
 // sigmoid(logit) if (b, c, pix) survives the local-maximum test, else 0
 __device__ __forceinline__ float suppressed_score(const ProposalArgs &a, int b, int c, int y, int x) {
   const long long row = ((long long)b * a.H + y) * a.W + x;
-  const float s = tf_sigmoid(a.heat[row * a.ld + c]);
+  const float s = sigmoidf(a.heat[row * a.ld + c]);
   if ((a.exempt >> c) & 1u) return s;
   if (y < a.pad || y >= a.H - a.pad || x < a.pad || x >= a.W - a.pad) return 0.f;
   for (int dy = -a.pad; dy <= a.pad; ++dy)
     for (int dx = -a.pad; dx <= a.pad; ++dx) {
       if (dy == 0 && dx == 0) continue;
-      const float v = tf_sigmoid(a.heat[(row + (long long)dy * a.W + dx) * a.ld + c]);
+      const float v = sigmoidf(a.heat[(row + (long long)dy * a.W + dx) * a.ld + c]);
       if (v > s) return 0.f;
     }
   return s;
@@ -128,7 +126,7 @@ __global__ __launch_bounds__(256) void tf_decode_kernel(DecodeArgs a, float *__r
       const size_t row = (size_t)b * a.K + q;
       const int ql = a.query_label[row];
       // sigmoid(heatmap) * query_heatmap_score * one_hot, max over classes (first maximum): only class ql is non-zero
-      score = tf_sigmoid(a.heat[row * a.ld_heat + ql]) * a.query_score[((size_t)b * a.C + ql) * a.K + q];
+      score = sigmoidf(a.heat[row * a.ld_heat + ql]) * a.query_score[((size_t)b * a.C + ql) * a.K + q];
       label = score > 0.f ? ql : 0;
       box[0] = a.center[row * a.ld_center] * a.osf * a.vs_x + a.pc_x;
       box[1] = a.center[row * a.ld_center + 1] * a.osf * a.vs_y + a.pc_y;

@@ -26,116 +26,36 @@
 
 #include "common.h"
 
-#pragma clang fp contract(off)
+#pragma clang fp contract(off)         // before the clipping code: bev_overlap.h relies on it
+#include "bev_overlap.h"
 
 namespace df3d {
 
-struct TPt {
-  float x, y;
+// box = [x1, y1, x2, y2, angle] (iou3d_kernel.cu:122-230 is the clipping of bev_overlap.h)
+struct XyxyrBox {
+  // the corner turned by -angle about the centre (iou3d_kernel.cu:106-114,139-168)
+  static __device__ __forceinline__ void corners(const float *box, BevPt *c) {
+    const float cx = (box[0] + box[2]) / 2, cy = (box[1] + box[3]) / 2, ca = cosf(box[4]), sa = sinf(box[4]);
+    const float px[4] = {box[0], box[2], box[2], box[0]}, py[4] = {box[1], box[1], box[3], box[3]};
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      c[k].x = (px[k] - cx) * ca + (py[k] - cy) * sa + cx;
+      c[k].y = -(px[k] - cx) * sa + (py[k] - cy) * ca + cy;
+    }
+    c[4] = c[0];
+  }
+  static __device__ __forceinline__ bool contains(const float *box, BevPt p) {   // iou3d_kernel.cu:56-79
+    const float margin = 1e-5f;
+    const float cx = (box[0] + box[2]) / 2, cy = (box[1] + box[3]) / 2;
+    const float ca = cosf(-box[4]), sa = sinf(-box[4]);
+    const float rx = (p.x - cx) * ca + (p.y - cy) * sa + cx;
+    const float ry = -(p.x - cx) * sa + (p.y - cy) * ca + cy;
+    return rx > box[0] - margin && rx < box[2] + margin && ry > box[1] - margin && ry < box[3] + margin;
+  }
 };
 
-__device__ __forceinline__ float t_cross3(TPt p1, TPt p2, TPt p0) {
-  return (p1.x - p0.x) * (p2.y - p0.y) - (p2.x - p0.x) * (p1.y - p0.y);
-}
-
-__device__ __forceinline__ bool t_rect_cross(TPt p1, TPt p2, TPt q1, TPt q2) {
-  return fminf(p1.x, p2.x) <= fmaxf(q1.x, q2.x) && fminf(q1.x, q2.x) <= fmaxf(p1.x, p2.x) &&
-         fminf(p1.y, p2.y) <= fmaxf(q1.y, q2.y) && fminf(q1.y, q2.y) <= fmaxf(p1.y, p2.y);
-}
-
-__device__ __forceinline__ bool t_intersection(TPt p1, TPt p0, TPt q1, TPt q0, TPt &ans) {
-  if (!t_rect_cross(p0, p1, q0, q1)) return false;
-  const float s1 = t_cross3(q0, p1, p0), s2 = t_cross3(p1, q1, p0);
-  const float s3 = t_cross3(p0, q1, q0), s4 = t_cross3(q1, p1, q0);
-  if (!(s1 * s2 > 0 && s3 * s4 > 0)) return false;
-  const float s5 = t_cross3(q1, p1, p0);
-  if (fabsf(s5 - s1) > 1e-8f) {
-    ans.x = (s5 * q0.x - s1 * q1.x) / (s5 - s1);
-    ans.y = (s5 * q0.y - s1 * q1.y) / (s5 - s1);
-  } else {
-    const float a0 = p0.y - p1.y, b0 = p1.x - p0.x, c0 = p0.x * p1.y - p1.x * p0.y;
-    const float a1 = q0.y - q1.y, b1 = q1.x - q0.x, c1 = q0.x * q1.y - q1.x * q0.y;
-    const float D = a0 * b1 - a1 * b0;
-    ans.x = (b0 * c1 - b1 * c0) / D;
-    ans.y = (a1 * c0 - a0 * c1) / D;
-  }
-  return true;
-}
-
-// box = [x1, y1, x2, y2, angle]; the corner turned by -angle about the centre (iou3d_kernel.cu:106-114,139-168)
-__device__ __forceinline__ void t_corners(const float *box, TPt *c) {
-  const float cx = (box[0] + box[2]) / 2, cy = (box[1] + box[3]) / 2, ca = cosf(box[4]), sa = sinf(box[4]);
-  const float px[4] = {box[0], box[2], box[2], box[0]}, py[4] = {box[1], box[1], box[3], box[3]};
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    c[k].x = (px[k] - cx) * ca + (py[k] - cy) * sa + cx;
-    c[k].y = -(px[k] - cx) * sa + (py[k] - cy) * ca + cy;
-  }
-  c[4] = c[0];
-}
-
-__device__ __forceinline__ bool t_in_box(const float *box, TPt p) {       // iou3d_kernel.cu:56-79
-  const float margin = 1e-5f;
-  const float cx = (box[0] + box[2]) / 2, cy = (box[1] + box[3]) / 2;
-  const float ca = cosf(-box[4]), sa = sinf(-box[4]);
-  const float rx = (p.x - cx) * ca + (p.y - cy) * sa + cx;
-  const float ry = -(p.x - cx) * sa + (p.y - cy) * ca + cy;
-  return rx > box[0] - margin && rx < box[2] + margin && ry > box[1] - margin && ry < box[3] + margin;
-}
-
-__device__ float t_box_overlap(const float *a, const float *b) {          // iou3d_kernel.cu:122-230
-  TPt ca[5], cb[5], pts[16], ctr = {0.f, 0.f};
-  int cnt = 0;
-  t_corners(a, ca);
-  t_corners(b, cb);
-  for (int i = 0; i < 4; ++i)
-    for (int j = 0; j < 4; ++j) {
-      TPt x;
-      if (t_intersection(ca[i + 1], ca[i], cb[j + 1], cb[j], x)) {
-        pts[cnt] = x;
-        ctr.x += x.x;
-        ctr.y += x.y;
-        cnt++;
-      }
-    }
-  for (int k = 0; k < 4; ++k) {
-    if (t_in_box(a, cb[k])) {
-      ctr.x += cb[k].x;
-      ctr.y += cb[k].y;
-      pts[cnt++] = cb[k];
-    }
-    if (t_in_box(b, ca[k])) {
-      ctr.x += ca[k].x;
-      ctr.y += ca[k].y;
-      pts[cnt++] = ca[k];
-    }
-  }
-  if (cnt < 3) return 0.f;                 // the reference's fan over fewer than three vertices is empty as well
-  ctr.x /= cnt;
-  ctr.y /= cnt;
-  float ang[16];
-  for (int i = 0; i < cnt; ++i) ang[i] = atan2f(pts[i].y - ctr.y, pts[i].x - ctr.x);
-  for (int j = 0; j < cnt - 1; ++j)        // the reference's bubble sort (same swaps: the keys do not change)
-    for (int i = 0; i < cnt - j - 1; ++i)
-      if (ang[i] > ang[i + 1]) {
-        const TPt t = pts[i];
-        pts[i] = pts[i + 1];
-        pts[i + 1] = t;
-        const float u = ang[i];
-        ang[i] = ang[i + 1];
-        ang[i + 1] = u;
-      }
-  float area = 0.f;
-  for (int k = 0; k < cnt - 1; ++k) {
-    const float ax = pts[k].x - pts[0].x, ay = pts[k].y - pts[0].y;
-    const float bx = pts[k + 1].x - pts[0].x, by = pts[k + 1].y - pts[0].y;
-    area += ax * by - ay * bx;
-  }
-  return fabsf(area) / 2.0f;
-}
-
 // overlap can only be non-zero when the centres are closer than the two half diagonals (+ margin)
-__device__ __forceinline__ bool t_far_apart(const float *a, const float *b) {
+__device__ __forceinline__ bool far_apart(const float *a, const float *b) {
   const float aw = a[2] - a[0], ah = a[3] - a[1], bw = b[2] - b[0], bh = b[3] - b[1];
   const float ra = 0.5f * sqrtf(aw * aw + ah * ah), rb = 0.5f * sqrtf(bw * bw + bh * bh);
   const float dx = (a[0] + a[2]) / 2 - (b[0] + b[2]) / 2, dy = (a[1] + a[3]) / 2 - (b[1] + b[3]) / 2;
@@ -153,7 +73,7 @@ __global__ __launch_bounds__(256) void overlap_xyxyr_kernel(const float *__restr
     a[e] = A[(size_t)i * 5 + e];
     b[e] = B[(size_t)j * 5 + e];
   }
-  out[(size_t)i * nb + j] = t_far_apart(a, b) ? 0.f : t_box_overlap(a, b);
+  out[(size_t)i * nb + j] = far_apart(a, b) ? 0.f : bev_overlap<XyxyrBox>(a, b);
 }
 
 // ---------------------------------------------------------------------------------------------- matching costs
@@ -196,7 +116,7 @@ __device__ __forceinline__ float iou3d_lidar(const float *p, const float *g) {
   float pq[5], gq[5];
   to_xyxyr(p, pq);
   to_xyxyr(g, gq);
-  const float bev = t_far_apart(pq, gq) ? 0.f : t_box_overlap(pq, gq);
+  const float bev = far_apart(pq, gq) ? 0.f : bev_overlap<XyxyrBox>(pq, gq);
   const float oh = fmaxf(fminf(p[2] + p[5], g[2] + g[5]) - fmaxf(p[2], g[2]), 0.f);
   const float o3 = bev * oh;
   const float v1 = p[3] * p[4] * p[5], v2 = g[3] * g[4] * g[5];
@@ -225,7 +145,7 @@ __global__ __launch_bounds__(256) void match_cost_kernel(MatchArgs a) {
   const int lab = a.gt_labels[g0 + gi];
   float cls = 0.f;
   if (lab >= 0 && lab < a.num_classes) {
-    const float s = 1.f / (1.f + expf(-r[a.col_cls + lab]));
+    const float s = sigmoidf(r[a.col_cls + lab]);
     const float neg = -logf(1.f - s + a.eps) * (1.f - a.alpha) * pow_e(s, a.gamma);
     const float pos = -logf(s + a.eps) * a.alpha * pow_e(1.f - s, a.gamma);
     cls = (pos - neg) * a.w_cls;
@@ -295,16 +215,6 @@ __global__ __launch_bounds__(256) void splat_kernel(SplatArgs a, int total) {
 // ---------------------------------------------------------------------------------------------- Gaussian focal loss
 constexpr int GF_CHUNK = 2048;
 
-__device__ __forceinline__ double block_sum256(double v, double *s_red) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  __syncthreads();
-  if (lane == 0) s_red[wave] = v;
-  __syncthreads();
-  return s_red[0] + s_red[1] + s_red[2] + s_red[3];
-}
-
 // logits element (b, c, pix) at b * sb + c * sc + pix * sp; target / grad contiguous [B, C, HW]
 template <bool GRAD>
 __global__ __launch_bounds__(256) void gfocal_kernel(const float *__restrict__ logits, long long sb, long long sc, long long sp,
@@ -320,7 +230,7 @@ __global__ __launch_bounds__(256) void gfocal_kernel(const float *__restrict__ l
     const long long bc = i / HW;
     const int c = (int)(bc % C), b = (int)(bc / C);
     const float x = logits[b * sb + c * sc + pix * sp], t = target[i];
-    const float s = 1.f / (1.f + expf(-x));
+    const float s = sigmoidf(x);
     const float p = fminf(fmaxf(s, 1e-4f), 1.f - 1e-4f);
     const float lp = logf(p + 1e-12f), l1p = logf(1.f - p + 1e-12f);
     const float negw = pow_e(1.f - t, gamma);
@@ -431,7 +341,7 @@ __global__ __launch_bounds__(1024) void query_loss_kernel(QueryArgs a) {
       float s = 0.f;
       for (int c = 0; c < a.num_classes; ++c) {
         const float x = row[a.col_cls + c];
-        const float pr = 1.f / (1.f + expf(-x));
+        const float pr = sigmoidf(x);
         float e, de;
         if (c == lab) {                                // -alpha (1-p)^gamma log p
           const float lg = logf(fmaxf(pr, tiny)), q = pow_e(1.f - pr, a.gamma);

@@ -21,8 +21,6 @@
 
 namespace df3d {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 struct XAttnArgs {
   const float *q, *k, *v;
   int ld_q, ld_k, ld_v;
