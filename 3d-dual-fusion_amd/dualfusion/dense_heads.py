@@ -8,7 +8,15 @@ In eval the head has two modes, chosen per call by DF3D_VR_TAIL_FUSED (default 1
             decoded here: VoxelRCNNHead.proposal_layer decodes the NMS_PRE_MAXSIZE selected ones (csrc/proposals.hip);
   composed  `batch_cls_preds`, `batch_box_preds`, `cls_preds_normalized=False` as the reference's generate_predicted_boxes
             makes them (every anchor decoded in torch).
-Target assignment and the losses are not here: forward in training mode raises NotImplementedError."""
+`forward` makes proposals and stays an eval-mode call: in training mode it raises NotImplementedError.
+
+Training of this first stage is `forward_train` + `get_loss`: AxisAlignedTargetAssigner and the RPN losses (classification focal
+loss, smooth-L1 regression, direction cross entropy), chosen per call by DF3D_ANCHOR_LOSS_FUSED (default 1):
+  fused     ops.anchor_assign + ops.anchor_loss (csrc/anchorloss.hip): one call each for all frames and anchor sets, anchors
+            from the tables, the regression target encoded only at the positives, no device-to-host read;
+  composed  the reference's formulation in torch under autograd: per-frame dense IoU matrices, one-hot targets and three
+            dense loss maps.
+TRAIN-mode proposals and the RoI head's targets and losses are not here: forward_train returns no RoIs."""
 import os
 
 import numpy as np
@@ -119,6 +127,175 @@ class AnchorTables(object):
             hit = self._device[str(device)] = (self.x_shifts.to(device).contiguous(), self.y_shifts.to(device).contiguous())
         return hit
 
+    def per_set(self):
+        """the reference's anchor list: one [H*W*A_s, 7] tensor per anchor set"""
+        flat = self.dense().view(self.H, self.W, self.num_anchors_per_location, 7)
+        slots = [[a for a, s in enumerate(self.anchor_set) if s == k] for k in range(self.x_shifts.shape[0])]
+        return [flat[:, :, idx, :].reshape(-1, 7) for idx in slots]
+
+
+def anchor_loss_fused():
+    """DF3D_ANCHOR_LOSS_FUSED, read per call (default: fused)"""
+    return os.environ.get("DF3D_ANCHOR_LOSS_FUSED", "1") != "0"
+
+
+class ResidualCoder(object):
+    """VR/pcdet/utils/box_coder_utils.py:ResidualCoder without the sin/cos variant"""
+    code_size = 7
+
+    @staticmethod
+    def encode_torch(boxes, anchors):
+        anchors = torch.cat([anchors[:, :3], torch.clamp_min(anchors[:, 3:6], 1e-5), anchors[:, 6:]], dim=-1)
+        boxes = torch.cat([boxes[:, :3], torch.clamp_min(boxes[:, 3:6], 1e-5), boxes[:, 6:]], dim=-1)
+        xa, ya, za, dxa, dya, dza, ra = torch.split(anchors[:, :7], 1, dim=-1)
+        xg, yg, zg, dxg, dyg, dzg, rg = torch.split(boxes[:, :7], 1, dim=-1)
+        diagonal = torch.sqrt(dxa ** 2 + dya ** 2)
+        return torch.cat([(xg - xa) / diagonal, (yg - ya) / diagonal, (zg - za) / dza, torch.log(dxg / dxa), torch.log(dyg / dya),
+                          torch.log(dzg / dza), rg - ra], dim=-1)
+
+    decode_torch = staticmethod(residual_decode)
+
+
+def nearest_bev_iou(boxes_a, boxes_b):
+    """boxes3d_nearest_bev_iou (VR/pcdet/utils/box_utils.py:286-335): [N, 7], [G, 7] -> [N, G]"""
+    def aligned(b):
+        rot = limit_period(b[:, 6], 0.5, np.pi).abs()
+        dims = torch.where(rot[:, None] < np.pi / 4, b[:, [3, 4]], b[:, [4, 3]])
+        return torch.cat((b[:, 0:2] - dims / 2, b[:, 0:2] + dims / 2), dim=1)
+    a, b = aligned(boxes_a), aligned(boxes_b)
+    x_len = torch.clamp_min(torch.min(a[:, 2, None], b[None, :, 2]) - torch.max(a[:, 0, None], b[None, :, 0]), 0)
+    y_len = torch.clamp_min(torch.min(a[:, 3, None], b[None, :, 3]) - torch.max(a[:, 1, None], b[None, :, 1]), 0)
+    area_a = (a[:, 2] - a[:, 0]) * (a[:, 3] - a[:, 1])
+    area_b = (b[:, 2] - b[:, 0]) * (b[:, 3] - b[:, 1])
+    inter = x_len * y_len
+    return inter / torch.clamp_min(area_a[:, None] + area_b[None, :] - inter, 1e-6)
+
+
+class AxisAlignedTargetAssigner(object):
+    """VR/pcdet/models/dense_heads/target_assigner/axis_aligned_target_assigner.py.  Fused (DF3D_ANCHOR_LOSS_FUSED=1, the
+    default): one library call for all frames and anchor sets (ops.anchor_assign), anchors read from the AnchorTables.
+    Composed (=0): the reference's formulation in torch, frame by frame with a dense IoU matrix per anchor set."""
+
+    def __init__(self, model_cfg, class_names, box_coder, match_height=False):
+        target_cfg = _get(model_cfg, "TARGET_ASSIGNER_CONFIG") or {}
+        if _get(model_cfg, "USE_MULTIHEAD", False):
+            raise NotImplementedError("USE_MULTIHEAD is not supported by the target assigner")
+        if _get(target_cfg, "NAME", "AxisAlignedTargetAssigner") != "AxisAlignedTargetAssigner":
+            raise NotImplementedError("TARGET_ASSIGNER_CONFIG.NAME: %s is not supported (ATSS has no kernel here)" % _get(target_cfg, "NAME"))
+        if match_height or _get(target_cfg, "MATCH_HEIGHT", False):
+            raise NotImplementedError("MATCH_HEIGHT is not supported: the anchors are matched by nearest-BEV IoU")
+        if _get(target_cfg, "POS_FRACTION", -1.0) >= 0:
+            raise NotImplementedError("POS_FRACTION >= 0 is not supported: the reference samples with the host's torch.randperm")
+        if _get(target_cfg, "NORM_BY_NUM_EXAMPLES", False):
+            raise NotImplementedError("NORM_BY_NUM_EXAMPLES is not supported")
+        self.box_coder = box_coder
+        self.match_height = False
+        self.class_names = list(class_names)
+        sets = list(_get(model_cfg, "ANCHOR_GENERATOR_CONFIG"))
+        self.anchor_class_names = [_get(c, "class_name") for c in sets]
+        for n in self.anchor_class_names:
+            if n not in self.class_names:
+                raise ValueError("anchor set class %r is not one of class_names %s" % (n, self.class_names))
+        self.set_class = [self.class_names.index(n) + 1 for n in self.anchor_class_names]
+        self.matched_thresholds = [float(_get(c, "matched_threshold")) for c in sets]
+        self.unmatched_thresholds = [float(_get(c, "unmatched_threshold")) for c in sets]
+
+    def assign_targets(self, all_anchors, gt_boxes_with_classes, dense=True):
+        """all_anchors: the head's AnchorTables; gt_boxes_with_classes [B, M, 8] on the device.  -> box_cls_labels [B, H*W*A]
+        int32, box_reg_targets [B, H*W*A, 7], reg_weights [B, H*W*A] float32 (the last two only with `dense`), and what the
+        fused losses read instead of the dense targets: gt_ids [B, H*W*A] int32, num_pos [B] int32."""
+        if not isinstance(all_anchors, AnchorTables):
+            raise TypeError("assign_targets takes the head's AnchorTables (head.tables): anchors are not materialised")
+        t = all_anchors
+        gt = gt_boxes_with_classes.to(torch.float32).contiguous()
+        if anchor_loss_fused():
+            x_shifts, y_shifts = t.on(gt.device)
+            out = ops.anchor_assign(x_shifts, y_shifts, gt, t.H, t.W, t.anchor_set, _table_list(t), self.set_class,
+                                    self.matched_thresholds, self.unmatched_thresholds, dense=dense)
+        else:
+            out = self._assign_composed(t, gt)
+        ret = {"box_cls_labels": out[0], "gt_ids": out[1], "num_pos": out[2]}
+        if len(out) > 3:
+            ret["box_reg_targets"], ret["reg_weights"] = out[3], out[4]
+        return ret
+
+    def _assign_composed(self, t, gt):
+        anchors_list = [a.to(gt.device) for a in t.per_set()]
+        B, A = gt.shape[0], t.num_anchors_per_location
+        labels_all, ids_all, targets_all, weights_all = [], [], [], []
+        for k in range(B):
+            cur_gt = gt[k, :, :7]
+            nz = (cur_gt.sum(dim=1) != 0).nonzero()[:, 0]
+            cnt = int(nz[-1]) if nz.numel() else 0
+            cur_gt = cur_gt[:cnt + 1]
+            cur_cls = gt[k, :cnt + 1, 7].int()
+            rows = torch.arange(cnt + 1, device=gt.device, dtype=torch.int32)
+            per_set = []
+            for s, anchors in enumerate(anchors_list):
+                mask = cur_cls == self.set_class[s]
+                per_set.append(self._assign_single(anchors, cur_gt[mask], cur_cls[mask], rows[mask], self.matched_thresholds[s],
+                                                   self.unmatched_thresholds[s]))
+            fm = (t.H, t.W)
+            labels_all.append(torch.cat([p[0].view(*fm, -1) for p in per_set], dim=-1).view(-1))
+            ids_all.append(torch.cat([p[1].view(*fm, -1) for p in per_set], dim=-1).view(-1))
+            targets_all.append(torch.cat([p[2].view(*fm, -1, 7) for p in per_set], dim=-2).view(-1, 7))
+            weights_all.append(torch.cat([p[3].view(*fm, -1) for p in per_set], dim=-1).view(-1))
+        labels = torch.stack(labels_all)
+        assert labels.shape[1] == t.H * t.W * A
+        return labels, torch.stack(ids_all), (labels > 0).sum(1).int(), torch.stack(targets_all), torch.stack(weights_all)
+
+    def _assign_single(self, anchors, gt_boxes, gt_classes, gt_rows, matched_threshold, unmatched_threshold):
+        """assign_targets_single (lines 132-210) without sampling; gt_ids name rows of the frame's gt_boxes"""
+        n, dev = anchors.shape[0], anchors.device
+        labels = torch.full((n,), -1, dtype=torch.int32, device=dev)
+        gt_ids = torch.full((n,), -1, dtype=torch.int32, device=dev)
+        targets = anchors.new_zeros((n, 7))
+        if gt_boxes.shape[0] == 0:
+            labels[:] = 0
+            return labels, gt_ids, targets, anchors.new_zeros((n,))
+        overlap = nearest_bev_iou(anchors, gt_boxes)
+        anchor_to_gt_argmax = overlap.argmax(dim=1)
+        anchor_to_gt_max = overlap[torch.arange(n, device=dev), anchor_to_gt_argmax]
+        gt_to_anchor_max = overlap.max(dim=0)[0]
+        gt_to_anchor_max = torch.where(gt_to_anchor_max == 0, torch.full_like(gt_to_anchor_max, -1), gt_to_anchor_max)
+        with_max = (overlap == gt_to_anchor_max).nonzero()[:, 0]
+        force = anchor_to_gt_argmax[with_max]
+        labels[with_max] = gt_classes[force]
+        gt_ids[with_max] = gt_rows[force]
+        pos = anchor_to_gt_max >= matched_threshold
+        labels[pos] = gt_classes[anchor_to_gt_argmax[pos]]
+        gt_ids[pos] = gt_rows[anchor_to_gt_argmax[pos]]
+        labels[(anchor_to_gt_max < unmatched_threshold).nonzero()[:, 0]] = 0
+        labels[with_max] = gt_classes[force]
+        fg = (labels > 0).nonzero()[:, 0]
+        targets[fg] = self.box_coder.encode_torch(gt_boxes[anchor_to_gt_argmax[fg]], anchors[fg])
+        weights = anchors.new_zeros((n,))
+        weights[labels > 0] = 1.0
+        return labels, gt_ids, targets, weights
+
+
+def _table_list(tables):
+    hit = tables.__dict__.get("_table_list")
+    if hit is None:
+        hit = tables.__dict__["_table_list"] = tables.table.tolist()
+    return hit
+
+
+def sigmoid_focal_loss(logits, target, weights, alpha=0.25, gamma=2.0):
+    """SigmoidFocalClassificationLoss.forward (VR/pcdet/utils/loss_utils.py:9-72)"""
+    p = torch.sigmoid(logits)
+    alpha_weight = target * alpha + (1 - target) * (1 - alpha)
+    pt = target * (1.0 - p) + (1.0 - target) * p
+    bce = torch.clamp(logits, min=0) - logits * target + torch.log1p(torch.exp(-torch.abs(logits)))
+    return alpha_weight * torch.pow(pt, gamma) * bce * weights.unsqueeze(-1)
+
+
+def weighted_smooth_l1(pred, target, code_weights, weights, beta):
+    """WeightedSmoothL1Loss.forward (loss_utils.py:75-136)"""
+    target = torch.where(torch.isnan(target), pred, target)
+    n = torch.abs((pred - target) * code_weights.view(1, 1, -1))
+    return torch.where(n < beta, 0.5 * n ** 2 / beta, n - 0.5 * beta) * weights.unsqueeze(-1)
+
 
 @DENSE_HEADS.register_module
 class AnchorHeadSingle(nn.Module):
@@ -141,6 +318,8 @@ class AnchorHeadSingle(nn.Module):
         self.tables = AnchorTables(_get(model_cfg, "ANCHOR_GENERATOR_CONFIG"), grid_size, point_cloud_range)
         self.anchors = self.tables.dense()
         self.num_anchors_per_location = self.tables.num_anchors_per_location
+        self.target_assigner = None              # made by the first training call (_training_setup)
+        self.forward_ret_dict = {}
 
         A = self.num_anchors_per_location
         self.conv_cls = nn.Conv2d(input_channels, A * self.num_class, kernel_size=1)
@@ -188,10 +367,141 @@ class AnchorHeadSingle(nn.Module):
             batch_box_preds[..., 6] = dir_rot + dir_offset + period * dir_labels.to(batch_box_preds.dtype)
         return batch_cls_preds, batch_box_preds
 
+    # ---- training: targets and RPN losses (csrc/anchorloss.hip) -------------------------------------------------------
+    def _training_setup(self):
+        """target assigner and loss weights, made on first use: an eval-only config needs neither key"""
+        if self.target_assigner is None:
+            loss_cfg = _get(self.model_cfg, "LOSS_CONFIG")
+            if loss_cfg is None:
+                raise KeyError("LOSS_CONFIG: the anchor losses need LOSS_WEIGHTS (cls_weight, loc_weight, dir_weight, code_weights)")
+            reg = _get(loss_cfg, "REG_LOSS_TYPE", None)
+            if reg not in (None, "WeightedSmoothL1Loss"):
+                raise NotImplementedError("REG_LOSS_TYPE %s is not supported" % reg)
+            w = _get(loss_cfg, "LOSS_WEIGHTS")
+            self.loss_weights = {k: float(_get(w, k)) for k in ("cls_weight", "loc_weight", "dir_weight")}
+            self.code_weights = [float(v) for v in _get(w, "code_weights")]
+            if len(self.code_weights) != self.code_size:
+                raise ValueError("code_weights must have %d entries" % self.code_size)
+            target_cfg = _get(self.model_cfg, "TARGET_ASSIGNER_CONFIG") or {}
+            self.target_assigner = AxisAlignedTargetAssigner(self.model_cfg, self.class_names, ResidualCoder(),
+                                                             match_height=_get(target_cfg, "MATCH_HEIGHT", False))
+        return self.target_assigner
+
+    def assign_targets(self, gt_boxes):
+        """gt_boxes [B, M, 8] on the device -> the targets dict of AxisAlignedTargetAssigner.assign_targets; the dense
+        regression targets are made only where something reads them (the composed losses)"""
+        return self._training_setup().assign_targets(self.tables, gt_boxes, dense=not anchor_loss_fused())
+
+    def forward_train(self, data_dict):
+        """The reference's training-mode forward: the three maps as [B, H, W, channels] views of ONE row buffer that carries
+        gradient to the live conv_* parameters, and the targets of data_dict['gt_boxes'].  Returns no RoIs."""
+        x = data_dict["spatial_features_2d"]
+        B, _, H, W = x.shape
+        if (H, W) != (self.tables.H, self.tables.W):
+            raise ValueError("AnchorHeadSingle: the map is %d x %d, the anchors were built for %d x %d" % (H, W, self.tables.H, self.tables.W))
+        convs = self._convs()
+        y = F.conv2d(x, torch.cat([c.weight for c in convs]), torch.cat([c.bias for c in convs]))
+        rows = y.permute(0, 2, 3, 1).contiguous().view(-1, y.shape[1])
+        n_cls, n_box = self.conv_cls.out_channels, self.conv_box.out_channels
+        ret = {"rows": rows, "cls_preds": rows[:, :n_cls].view(B, H, W, n_cls),
+               "box_preds": rows[:, n_cls:n_cls + n_box].view(B, H, W, n_box), "gt_boxes": data_dict["gt_boxes"]}
+        if self.conv_dir_cls is not None:
+            ret["dir_cls_preds"] = rows[:, n_cls + n_box:].view(B, H, W, -1)
+        ret.update(self.assign_targets(data_dict["gt_boxes"]))
+        self.forward_ret_dict = ret
+        return data_dict
+
+    def _fused_losses(self):
+        """[3] = rpn_loss_cls, rpn_loss_loc, rpn_loss_dir: one call per forward_train, shared by the two get_*_loss"""
+        r = self.forward_ret_dict
+        if "rpn_losses" not in r:
+            rows = r["rows"]
+            n_cls, n_box = self.conv_cls.out_channels, self.conv_box.out_channels
+            gt = r["gt_boxes"].to(torch.float32).contiguous()
+            x_shifts, y_shifts = self.tables.on(rows.device)
+            has_dir = self.conv_dir_cls is not None
+            spec = ops.AnchorLossSpec((0, n_cls, n_cls + n_box if has_dir else None), x_shifts, y_shifts, r["box_cls_labels"],
+                                      r["gt_ids"], r["num_pos"], gt, self.tables.H, self.tables.W, self.num_class, self.num_dir_bins,
+                                      self.tables.anchor_set, _table_list(self.tables), self.loss_weights["cls_weight"],
+                                      self.loss_weights["loc_weight"], self.loss_weights["dir_weight"], self.code_weights,
+                                      dir_offset=_get(self.model_cfg, "DIR_OFFSET", 0.0) if has_dir else 0.0)
+            r["rpn_losses"] = ops.anchor_loss(rows, spec)
+        return r["rpn_losses"]
+
+    def get_cls_layer_loss(self):
+        """anchor_head_template.py:101-135; tb_dict values are device tensors"""
+        self._training_setup()
+        if anchor_loss_fused():
+            cls_loss = self._fused_losses()[0]
+            return cls_loss, {"rpn_loss_cls": cls_loss.detach()}
+        r = self.forward_ret_dict
+        cls_preds, labels = r["cls_preds"], r["box_cls_labels"]
+        B = int(cls_preds.shape[0])
+        cared, positives = labels >= 0, labels > 0
+        cls_weights = ((labels == 0) * 1.0 + 1.0 * positives).float()
+        if self.num_class == 1:
+            labels = torch.where(positives, torch.ones_like(labels), labels)
+        cls_weights = cls_weights / torch.clamp(positives.sum(1, keepdim=True).float(), min=1.0)
+        cls_targets = labels * cared.type_as(labels)
+        one_hot = torch.zeros(*cls_targets.shape, self.num_class + 1, dtype=cls_preds.dtype, device=cls_preds.device)
+        one_hot.scatter_(-1, cls_targets.unsqueeze(-1).long(), 1.0)
+        loss = sigmoid_focal_loss(cls_preds.reshape(B, -1, self.num_class), one_hot[..., 1:], cls_weights)
+        cls_loss = loss.sum() / B * self.loss_weights["cls_weight"]
+        return cls_loss, {"rpn_loss_cls": cls_loss.detach()}
+
+    def get_box_reg_layer_loss(self):
+        """anchor_head_template.py:162-214; tb_dict values are device tensors"""
+        self._training_setup()
+        has_dir = self.conv_dir_cls is not None
+        if anchor_loss_fused():
+            losses = self._fused_losses()
+            tb = {"rpn_loss_loc": losses[1].detach()}
+            if has_dir:
+                tb["rpn_loss_dir"] = losses[2].detach()
+                return losses[1] + losses[2], tb
+            return losses[1], tb
+        r = self.forward_ret_dict
+        box_preds, targets, labels = r["box_preds"], r["box_reg_targets"], r["box_cls_labels"]
+        B = int(box_preds.shape[0])
+        positives = labels > 0
+        reg_weights = positives.float() / torch.clamp(positives.sum(1, keepdim=True).float(), min=1.0)
+        anchors = self.anchors.to(box_preds.device).view(1, -1, 7).repeat(B, 1, 1)
+        box_preds = box_preds.reshape(B, -1, self.code_size)
+        sin_pred = torch.sin(box_preds[..., 6:7]) * torch.cos(targets[..., 6:7])          # add_sin_difference
+        sin_tgt = torch.cos(box_preds[..., 6:7]) * torch.sin(targets[..., 6:7])
+        pred = torch.cat([box_preds[..., :6], sin_pred], dim=-1)
+        tgt = torch.cat([targets[..., :6], sin_tgt], dim=-1)
+        code_weights = ops.device_constant(self.code_weights, torch.float32, pred.device)
+        loc_loss = weighted_smooth_l1(pred, tgt, code_weights, reg_weights, 1.0 / 9.0).sum() / B * self.loss_weights["loc_weight"]
+        tb = {"rpn_loss_loc": loc_loss.detach()}
+        box_loss = loc_loss
+        if has_dir:
+            rot_gt = targets[..., 6] + anchors[..., 6]                                        # get_direction_target
+            offset_rot = limit_period(rot_gt - _get(self.model_cfg, "DIR_OFFSET"), 0, 2 * np.pi)
+            dir_targets = torch.clamp(torch.floor(offset_rot / (2 * np.pi / self.num_dir_bins)).long(), min=0, max=self.num_dir_bins - 1)
+            dir_logits = r["dir_cls_preds"].reshape(B, -1, self.num_dir_bins)
+            weights = positives.type_as(dir_logits)
+            weights = weights / torch.clamp(weights.sum(-1, keepdim=True), min=1.0)
+            dir_loss = (F.cross_entropy(dir_logits.permute(0, 2, 1), dir_targets, reduction="none") * weights).sum() / B
+            dir_loss = dir_loss * self.loss_weights["dir_weight"]
+            box_loss = box_loss + dir_loss
+            tb["rpn_loss_dir"] = dir_loss.detach()
+        return box_loss, tb
+
+    def get_loss(self):
+        """-> (rpn_loss, tb_dict): rpn_loss_cls, rpn_loss_loc, rpn_loss_dir (with direction classifier), rpn_loss"""
+        cls_loss, tb_dict = self.get_cls_layer_loss()
+        box_loss, tb_box = self.get_box_reg_layer_loss()
+        tb_dict.update(tb_box)
+        rpn_loss = cls_loss + box_loss
+        tb_dict["rpn_loss"] = rpn_loss.detach()
+        return rpn_loss, tb_dict
+
     def forward(self, data_dict):
         if self.training:
-            raise NotImplementedError("AnchorHeadSingle: target assignment and the anchor losses are not implemented; "
-                                      "this head runs in eval mode only")
+            raise NotImplementedError("AnchorHeadSingle.forward makes proposals and runs in eval mode only (TRAIN-mode proposals "
+                                      "and the RoI head's targets are not implemented); the first-stage training pass is "
+                                      "forward_train + get_loss")
         x = data_dict["spatial_features_2d"]
         B, _, H, W = x.shape
         if (H, W) != (self.tables.H, self.tables.W):

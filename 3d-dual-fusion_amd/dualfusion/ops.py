@@ -1332,6 +1332,217 @@ def roi_decode_select(rois, rcnn_cls, rcnn_reg, roi_labels, score_threshold, nms
     return box_preds, boxes, scores, labels, counts
 
 
+ANCHOR_MAX_GT = 1024       # DF3D_ANCHOR_MAX_GT
+ANCHOR_GT_CHUNK = 128      # DF3D_ANCHOR_GT_CHUNK: ground-truth rows staged in LDS at a time
+
+
+class _AnchorAssignCfg(ctypes.Structure):
+    _c_name_ = "df3d_anchor_assign_cfg"
+    _fields_ = [("anchors", _AnchorCfg), ("max_gt", ctypes.c_int), ("set_class", ctypes.c_int * MAX_ANCHORS),
+                ("matched_threshold", ctypes.c_float * MAX_ANCHORS), ("unmatched_threshold", ctypes.c_float * MAX_ANCHORS)]
+
+
+class _AnchorLossCfg(ctypes.Structure):
+    _c_name_ = "df3d_anchor_loss_cfg"
+    _fields_ = [("anchors", _AnchorCfg), ("max_gt", ctypes.c_int), ("cls_weight", ctypes.c_float), ("loc_weight", ctypes.c_float),
+                ("dir_weight", ctypes.c_float), ("code_weights", ctypes.c_float * 7), ("beta", ctypes.c_float)]
+
+
+def _anchor_tables_cfg(cfg, batch, H, W, anchor_set, anchor_table, num_sets, num_classes=1, num_dir_bins=0, dir_offset=0.0):
+    """fill the df3d_anchor_cfg embedded in an assignment / loss config"""
+    A = len(anchor_set)
+    if A > MAX_ANCHORS:
+        raise NotImplementedError("anchor targets: at most %d anchors per location (got %d)" % (MAX_ANCHORS, A))
+    c = cfg.anchors
+    c.batch, c.H, c.W = int(batch), int(H), int(W)
+    c.num_anchors, c.num_classes, c.num_dir_bins, c.num_sets = A, int(num_classes), int(num_dir_bins), int(num_sets)
+    for a in range(A):
+        c.anchor_set[a] = int(anchor_set[a])
+        for e in range(5):
+            c.anchor[a][e] = float(anchor_table[a][e])
+    c.dir_offset = float(dir_offset)
+    return cfg
+
+
+def anchor_assign_cfg(batch, H, W, max_gt, anchor_set, anchor_table, set_class, matched, unmatched):
+    """The df3d_anchor_assign_cfg of a call: per anchor set its 1-based class id and its matched / unmatched thresholds."""
+    sets = len(set_class)
+    if sets > MAX_ANCHORS or len(matched) != sets or len(unmatched) != sets:
+        raise ValueError("anchor_assign: one class id and one pair of thresholds per anchor set, at most %d sets" % MAX_ANCHORS)
+    cfg = _anchor_tables_cfg(_AnchorAssignCfg(), batch, H, W, anchor_set, anchor_table, sets)
+    cfg.max_gt = int(max_gt)
+    for s in range(sets):
+        cfg.set_class[s], cfg.matched_threshold[s], cfg.unmatched_threshold[s] = int(set_class[s]), float(matched[s]), float(unmatched[s])
+    return cfg
+
+
+def anchor_loss_cfg(batch, H, W, max_gt, num_classes, num_dir_bins, anchor_set, anchor_table, num_sets, cls_weight, loc_weight,
+                    dir_weight, code_weights, dir_offset=0.0, beta=1.0 / 9.0):
+    """The df3d_anchor_loss_cfg of a call."""
+    if len(code_weights) != 7:
+        raise ValueError("anchor_loss: code_weights must have 7 entries (got %d)" % len(code_weights))
+    cfg = _anchor_tables_cfg(_AnchorLossCfg(), batch, H, W, anchor_set, anchor_table, num_sets, num_classes, num_dir_bins, dir_offset)
+    cfg.max_gt = int(max_gt)
+    cfg.cls_weight, cfg.loc_weight, cfg.dir_weight, cfg.beta = float(cls_weight), float(loc_weight), float(dir_weight), float(beta)
+    for e in range(7):
+        cfg.code_weights[e] = float(code_weights[e])
+    return cfg
+
+
+def _shift_tables(x_shifts, y_shifts, H, W):
+    _chk(x_shifts, torch.float32, "x_shifts")
+    _chk(y_shifts, torch.float32, "y_shifts")
+    sets = int(x_shifts.shape[0])
+    if x_shifts.dim() != 2 or y_shifts.dim() != 2 or x_shifts.shape[1] != W or tuple(y_shifts.shape) != (sets, H):
+        raise ValueError("x_shifts must be [sets, W] and y_shifts [sets, H]")
+    return sets
+
+
+def _gt_boxes(gt_boxes):
+    _chk(gt_boxes, torch.float32, "gt_boxes")
+    if gt_boxes.dim() != 3 or gt_boxes.shape[2] != 8:
+        raise ValueError("gt_boxes must be [B, M, 8] = (x, y, z, dx, dy, dz, heading, class)")
+    return int(gt_boxes.shape[0]), int(gt_boxes.shape[1])
+
+
+def anchor_assign(x_shifts, y_shifts, gt_boxes, H, W, anchor_set, anchor_table, set_class, matched, unmatched, dense=False):
+    """AxisAlignedTargetAssigner.assign_targets of all frames and anchor sets in one call, nothing read back
+    (csrc/anchorloss.hip).  x_shifts [sets, W], y_shifts [sets, H] fp32; gt_boxes [B, M, 8] fp32 on the device; anchor_set [A],
+    anchor_table [A][5] host values; set_class / matched / unmatched: per anchor set the 1-based class id it serves and its
+    thresholds.  -> labels [B, H*W*A] int32 (-1, 0 or a class id), gt_ids [B, H*W*A] int32 (row of gt_boxes[b] or -1),
+    num_pos [B] int32; dense: also the reference's box_reg_targets [B, H*W*A, 7] and reg_weights [B, H*W*A]."""
+    lib = _lib.load()
+    sets = _shift_tables(x_shifts, y_shifts, H, W)
+    if sets != len(set_class):
+        raise ValueError("anchor_assign: %d shift tables for %d anchor sets" % (sets, len(set_class)))
+    B, M = _gt_boxes(gt_boxes)
+    cfg = anchor_assign_cfg(B, H, W, M, anchor_set, anchor_table, set_class, matched, unmatched)
+    dev = gt_boxes.device
+    n = int(H) * int(W) * len(anchor_set)
+    labels = torch.empty((B, n), dtype=torch.int32, device=dev)
+    gt_ids = torch.empty((B, n), dtype=torch.int32, device=dev)
+    num_pos = torch.empty((B,), dtype=torch.int32, device=dev)
+    targets = torch.empty((B, n, 7), dtype=torch.float32, device=dev) if dense else None
+    weights = torch.empty((B, n), dtype=torch.float32, device=dev) if dense else None
+    nbytes = int(lib.df3d_anchor_assign_workspace_bytes(ctypes.byref(cfg)))
+    ws = torch.empty((max(nbytes, 8),), dtype=torch.uint8, device=dev)
+    lib.df3d_anchor_assign(_ptr(x_shifts), _ptr(y_shifts), _ptr(gt_boxes), ctypes.byref(cfg), _ptr(labels), _ptr(gt_ids),
+                           _ptr(num_pos), _ptr(targets), _ptr(weights), _ptr(ws), nbytes, _stream())
+    if dense:
+        return labels, gt_ids, num_pos, targets, weights
+    return labels, gt_ids, num_pos
+
+
+class AnchorLossSpec(object):
+    """What ops.anchor_loss needs besides the rows: the column blocks of the wide row buffer, the tables, the targets of
+    ops.anchor_assign and the loss configuration."""
+
+    def __init__(self, cols, x_shifts, y_shifts, labels, gt_ids, num_pos, gt_boxes, H, W, num_classes, num_dir_bins, anchor_set,
+                 anchor_table, cls_weight, loc_weight, dir_weight, code_weights, dir_offset=0.0, beta=1.0 / 9.0):
+        """cols: (cls, box, dir) first columns of the three maps in the row buffer; dir None without direction classifier"""
+        self.cols = tuple(cols)
+        self.x_shifts, self.y_shifts = x_shifts, y_shifts
+        self.labels, self.gt_ids, self.num_pos, self.gt_boxes = labels, gt_ids, num_pos, gt_boxes
+        self.H, self.W, self.A = int(H), int(W), len(anchor_set)
+        self.C, self.NB = int(num_classes), int(num_dir_bins) if self.cols[2] is not None else 0
+        sets = _shift_tables(x_shifts, y_shifts, self.H, self.W)
+        self.B, M = _gt_boxes(gt_boxes)
+        n = self.H * self.W * self.A
+        for v, name in ((labels, "labels"), (gt_ids, "gt_ids")):
+            _chk(v, torch.int32, name)
+            if tuple(v.shape) != (self.B, n):
+                raise ValueError("%s must be [B, H*W*A] = [%d, %d]" % (name, self.B, n))
+        _chk(num_pos, torch.int32, "num_pos")
+        if tuple(num_pos.shape) != (self.B,):
+            raise ValueError("num_pos must be [B]")
+        self.cfg = anchor_loss_cfg(self.B, H, W, M, self.C, self.NB, anchor_set, anchor_table, sets, cls_weight, loc_weight,
+                                   dir_weight, code_weights, dir_offset, beta)
+        self.widths = (self.A * self.C, self.A * 7, self.A * self.NB)
+
+    def views(self, rows):
+        """the three column blocks of a [B*H*W, width] row buffer (dir: None without direction classifier)"""
+        out = []
+        for col, width, name in zip(self.cols, self.widths, ("cls_rows", "box_rows", "dir_rows")):
+            if col is None:
+                out.append(None)
+                continue
+            if col < 0 or col + width > rows.shape[1]:
+                raise ValueError("%s: columns %d..%d lie outside the %d-wide row buffer" % (name, col, col + width, rows.shape[1]))
+            out.append(_tail_rows(rows[:, col:col + width], self.B * self.H * self.W, width, name))
+        return out
+
+    def covers(self, width):
+        """do the column blocks cover the whole row?"""
+        spans = sorted((c, c + w) for c, w in zip(self.cols, self.widths) if c is not None)
+        end = 0
+        for lo, hi in spans:
+            if lo > end:
+                return False
+            end = max(end, hi)
+        return end >= width
+
+
+def _anchor_loss_args(spec, rows):
+    cls, box, dirs = spec.views(rows)
+    ld = int(rows.stride(0))
+    return (_ptr(cls), ld, _ptr(box), ld, _ptr(dirs), ld if dirs is not None else 0, _ptr(spec.x_shifts), _ptr(spec.y_shifts),
+            _ptr(spec.labels), _ptr(spec.gt_ids), _ptr(spec.num_pos), _ptr(spec.gt_boxes), ctypes.byref(spec.cfg))
+
+
+class _AnchorLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, rows, spec):
+        lib = _lib.load()
+        if rows.dim() != 2 or rows.dtype != torch.float32 or (rows.shape[1] > 1 and rows.stride(1) != 1):
+            raise ValueError("anchor_loss: rows must be an fp32 [B*H*W, width] buffer with unit column stride")
+        if not rows.is_cuda:
+            raise _lib.Df3dError("rows must live on the GPU (got %s); the MI355X path has no CPU fallback" % rows.device)
+        args = _anchor_loss_args(spec, rows)
+        losses = torch.empty((3,), dtype=torch.float32, device=rows.device)
+        nbytes = int(lib.df3d_anchor_loss_workspace_bytes(ctypes.byref(spec.cfg)))
+        ws = torch.empty((max(nbytes, 8),), dtype=torch.uint8, device=rows.device)
+        lib.df3d_anchor_loss(*args, _ptr(losses), _ptr(ws), nbytes, _stream())
+        ctx.save_for_backward(rows)
+        ctx.spec = spec
+        return losses
+
+    @staticmethod
+    def backward(ctx, grad_losses):
+        lib = _lib.load()
+        rows, = ctx.saved_tensors
+        spec = ctx.spec
+        upstream = grad_losses.to(torch.float32).contiguous()
+        # the kernel writes every element of the three blocks: only columns outside them need the zeros
+        grad = torch.empty_like(rows, memory_format=torch.contiguous_format) if spec.covers(rows.shape[1]) else \
+            torch.zeros_like(rows, memory_format=torch.contiguous_format)
+        g_cls, g_box, g_dir = spec.views(grad)
+        ld = int(grad.stride(0))
+        lib.df3d_anchor_loss_grad(*_anchor_loss_args(spec, rows), _ptr(upstream), _ptr(g_cls), ld, _ptr(g_box), ld, _ptr(g_dir),
+                                  ld if g_dir is not None else 0, _stream())
+        return grad, None
+
+
+def anchor_loss(rows, spec):
+    """The RPN losses of the anchor head, fused (csrc/anchorloss.hip): rows [B*H*W, width] fp32, the ONE wide buffer whose
+    column blocks spec.cols are the cls / box / dir maps; spec an AnchorLossSpec.  -> [3] fp32 on the device: rpn_loss_cls,
+    rpn_loss_loc, rpn_loss_dir (0 without direction classifier).  Differentiable with respect to `rows`: backward is one
+    launch that writes the gradient of all three maps into one buffer of the same layout and reads the upstream gradients on
+    the device."""
+    return _AnchorLoss.apply(rows, spec)
+
+
+def anchor_loss_grad_into(rows, spec, grad_losses, grad_rows):
+    """df3d_anchor_loss_grad into the column blocks spec.cols of a caller's buffer `grad_rows` (same row count as `rows`, any
+    width that holds the blocks); elements outside the blocks are not touched."""
+    lib = _lib.load()
+    _chk(grad_losses, torch.float32, "grad_losses")
+    g_cls, g_box, g_dir = spec.views(grad_rows)
+    ld = int(grad_rows.stride(0))
+    lib.df3d_anchor_loss_grad(*_anchor_loss_args(spec, rows), _ptr(grad_losses), _ptr(g_cls), ld, _ptr(g_box), ld, _ptr(g_dir),
+                              ld if g_dir is not None else 0, _stream())
+    return grad_rows
+
+
 class _HeadTargets(ctypes.Structure):
     _c_name_ = "df3d_head_targets"
     _fields_ = [(n, ctypes.c_void_p) for n in ("hm", "ind", "mask", "cat", "box")]

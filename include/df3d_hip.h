@@ -1478,6 +1478,74 @@ int df3d_roi_decode_select(const float *rois, const float *rcnn_cls, int ld_cls,
                            float *pred_scores, long long *pred_labels, int32_t *counts, void *workspace,
                            size_t workspace_bytes, void *stream);
 
+/* ------------------------------------------------------------------------------------
+ * Voxel-RCNN first-stage training (csrc/anchorloss.hip): anchor targets and the RPN losses, each one
+ * call for all frames and anchor sets with no device-to-host copy.  The anchors are never materialised: they are read from
+ * the tables of df3d_anchor_proposals (x_shifts [num_sets][W], y_shifts [num_sets][H], anchor_set[a], anchor[a]); of the
+ * embedded df3d_anchor_cfg the assignment reads batch, H, W, num_anchors, num_sets, anchor_set and anchor, the losses also
+ * num_classes, num_dir_bins and dir_offset.  Anchor i = (y*W + x)*A + a of a frame.
+ *
+ * df3d_anchor_assign replaces AxisAlignedTargetAssigner.assign_targets
+ * (VR/pcdet/models/dense_heads/target_assigner/axis_aligned_target_assigner.py:36-210: the Python loop over frames and
+ * anchor classes, the `while cur_gt[cnt].sum() == 0` trim that reads one row back per iteration, a dense IoU matrix and four
+ * nonzero() calls per frame and class).  gt_boxes [B, M, 8] f32 = (x, y, z, dx, dy, dz, heading, class).
+ *   Valid rows of a frame: up to the last row whose seven box values sum to non-zero in float32, at least one; rows with
+ *   class < 1 are padding.  Set s serves the 1-based class set_class[s] with matched_threshold[s] / unmatched_threshold[s].
+ *   IoU = boxes3d_nearest_bev_iou (utils/box_utils.py:286-335) in float32 in the reference's operation order.  Per anchor:
+ *   arg-max over the GTs of its set's class (first index wins ties).  Per (frame, set, GT): max over the set's anchors; every
+ *   anchor whose IoU with a GT equals that GT's max (> 0) is forced positive and takes class and id of ITS OWN arg-max GT
+ *   (lines 155-158).  max >= matched -> positive; < unmatched -> 0 unless forced (lines 184-188); otherwise -1; a frame
+ *   without a GT of the class -> 0.
+ *   labels [B, H*W*A] i32 (-1, 0 or a class id), gt_ids [B, H*W*A] i32 (row of gt_boxes[b], or -1), num_pos [B] i32;
+ *   where non-NULL the reference's dense box_reg_targets [B, H*W*A, 7] (ResidualCoder.encode_torch,
+ *   utils/box_coder_utils.py:13-43, sizes clamped at 1e-5; zeros at non-positives) and reg_weights [B, H*W*A] (1 at positives).
+ *   Limits: A <= DF3D_MAX_ANCHORS, B <= 255, H*W*A <= 2^22, M <= DF3D_ANCHOR_MAX_GT (the GTs of a frame go through LDS in
+ *   chunks of DF3D_ANCHOR_GT_CHUNK).
+ *
+ * df3d_anchor_loss / df3d_anchor_loss_grad replace AnchorHeadTemplate.get_cls_layer_loss + get_box_reg_layer_loss
+ * (dense_heads/anchor_head_template.py:101-223 over utils/loss_utils.py:9-72, 75-136, 181-206).  Head maps as for
+ * df3d_anchor_proposals: channels-last pixel rows with row strides in floats, dir NULL without direction classifier.
+ *   cls: sigmoid focal loss (alpha 0.25, gamma 2) of every anchor with label >= 0 against the one-hot of its label
+ *        (num_classes == 1: every positive is class 1);
+ *   loc: positives only: target encoded from gt_boxes[b, gt_ids] and the table anchor, add_sin_difference on code 6,
+ *        code_weights, smooth L1 (beta);
+ *   dir: positives only: bin = clamp(floor(limit_period(target6 + anchor rotation - dir_offset, 0, 2 pi) / (2 pi / NB))) in
+ *        float32, cross entropy;
+ *   each term weighted 1 / max(num_pos[b], 1).  losses[3] = (rpn_loss_cls, rpn_loss_loc, rpn_loss_dir), each summed over the
+ *   batch, divided by B, times its weight; fp64 partials at fixed positions and an ordered final sum (bit-identical runs).
+ * df3d_anchor_loss_grad writes EVERY element of the three gradient maps (rows of the same layout, own strides; zeros where
+ * nothing contributes): d(sum_j grad_losses[j] * losses[j]) / d map, grad_losses [3] f32 read from DEVICE memory. */
+#define DF3D_ANCHOR_MAX_GT 1024
+#define DF3D_ANCHOR_GT_CHUNK 128
+typedef struct df3d_anchor_assign_cfg {
+  df3d_anchor_cfg anchors;
+  int max_gt;                           /* M */
+  int set_class[DF3D_MAX_ANCHORS];      /* per anchor set: the 1-based class id it serves */
+  float matched_threshold[DF3D_MAX_ANCHORS];
+  float unmatched_threshold[DF3D_MAX_ANCHORS];
+} df3d_anchor_assign_cfg;
+typedef struct df3d_anchor_loss_cfg {
+  df3d_anchor_cfg anchors;
+  int max_gt;                           /* M */
+  float cls_weight, loc_weight, dir_weight;
+  float code_weights[7];
+  float beta;                           /* smooth L1: 1/9 */
+} df3d_anchor_loss_cfg;
+size_t df3d_anchor_assign_workspace_bytes(const df3d_anchor_assign_cfg *cfg);
+int df3d_anchor_assign(const float *x_shifts, const float *y_shifts, const float *gt_boxes, const df3d_anchor_assign_cfg *cfg,
+                       int32_t *labels, int32_t *gt_ids, int32_t *num_pos, float *box_reg_targets, float *reg_weights,
+                       void *workspace, size_t workspace_bytes, void *stream);
+size_t df3d_anchor_loss_workspace_bytes(const df3d_anchor_loss_cfg *cfg);
+int df3d_anchor_loss(const float *cls, int ld_cls, const float *box, int ld_box, const float *dir, int ld_dir,
+                     const float *x_shifts, const float *y_shifts, const int32_t *labels, const int32_t *gt_ids,
+                     const int32_t *num_pos, const float *gt_boxes, const df3d_anchor_loss_cfg *cfg, float *losses,
+                     void *workspace, size_t workspace_bytes, void *stream);
+int df3d_anchor_loss_grad(const float *cls, int ld_cls, const float *box, int ld_box, const float *dir, int ld_dir,
+                          const float *x_shifts, const float *y_shifts, const int32_t *labels, const int32_t *gt_ids,
+                          const int32_t *num_pos, const float *gt_boxes, const df3d_anchor_loss_cfg *cfg,
+                          const float *grad_losses, float *grad_cls, int ld_gcls, float *grad_box, int ld_gbox, float *grad_dir,
+                          int ld_gdir, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
