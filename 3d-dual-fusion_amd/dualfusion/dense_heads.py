@@ -16,7 +16,7 @@ loss, smooth-L1 regression, direction cross entropy), chosen per call by DF3D_AN
             from the tables, the regression target encoded only at the positives, no device-to-host read;
   composed  the reference's formulation in torch under autograd: per-frame dense IoU matrices, one-hot targets and three
             dense loss maps.
-TRAIN-mode proposals and the RoI head's targets and losses are not here: forward_train returns no RoIs."""
+TRAIN-mode proposals are not here: forward_train returns no RoIs (the RoI head's targets and losses are in roi_heads.py)."""
 import os
 
 import numpy as np

@@ -1543,6 +1543,181 @@ def anchor_loss_grad_into(rows, spec, grad_losses, grad_rows):
     return grad_rows
 
 
+ROI_MAX_ROIS = 4096        # DF3D_ROI_MAX_ROIS (= TAIL_MAX_CANDIDATES: what the proposal layer can hand over)
+ROI_MAX_SAMPLES = 1024     # DF3D_ROI_MAX_SAMPLES: ROI_PER_IMAGE
+ROI_MAX_GT = 1024          # DF3D_ROI_MAX_GT (= ANCHOR_MAX_GT)
+ROI_SCORE_TYPES = {"roi_iou": 0, "cls": 1}      # DF3D_ROI_SCORE_ROI_IOU, DF3D_ROI_SCORE_CLS
+
+
+class _RoiTargetCfg(ctypes.Structure):
+    _c_name_ = "df3d_roi_target_cfg"
+    _fields_ = [("batch", ctypes.c_int), ("num_rois", ctypes.c_int), ("max_gt", ctypes.c_int), ("roi_per_image", ctypes.c_int),
+                ("fg_per_image", ctypes.c_int), ("sample_by_class", ctypes.c_int), ("cls_score_type", ctypes.c_int),
+                ("reg_fg_thresh", ctypes.c_double), ("cls_fg_thresh", ctypes.c_double), ("cls_bg_thresh", ctypes.c_double),
+                ("cls_bg_thresh_lo", ctypes.c_double), ("hard_bg_ratio", ctypes.c_double)]
+
+
+class _RcnnLossCfg(ctypes.Structure):
+    _c_name_ = "df3d_rcnn_loss_cfg"
+    _fields_ = [("num_rows", ctypes.c_int), ("corner_loss", ctypes.c_int), ("cls_weight", ctypes.c_float), ("reg_weight", ctypes.c_float),
+                ("corner_weight", ctypes.c_float), ("code_weights", ctypes.c_float * 7), ("beta", ctypes.c_float)]
+
+
+def _node(cfg, key, default=None):
+    """config nodes are EasyDicts in pcdet and plain dicts here"""
+    if isinstance(cfg, dict):
+        return cfg.get(key, default)
+    return getattr(cfg, key, default)
+
+
+def roi_target_cfg(batch, num_rois, max_gt, sampler_cfg):
+    """The df3d_roi_target_cfg of a call from the reference's ROI_SAMPLER keys; every limit is refused by name."""
+    import numpy as np
+    for key in ("ROI_PER_IMAGE", "FG_RATIO", "REG_FG_THRESH", "CLS_FG_THRESH", "CLS_BG_THRESH", "CLS_BG_THRESH_LO", "HARD_BG_RATIO",
+                "CLS_SCORE_TYPE"):
+        if _node(sampler_cfg, key) is None:
+            raise KeyError("roi_targets: the sampler config has no %s" % key)
+    score = _node(sampler_cfg, "CLS_SCORE_TYPE")
+    if score not in ROI_SCORE_TYPES:
+        raise NotImplementedError("roi_targets: CLS_SCORE_TYPE %r is not supported (%s)" % (score, ", ".join(sorted(ROI_SCORE_TYPES))))
+    m = int(_node(sampler_cfg, "ROI_PER_IMAGE"))
+    if num_rois > ROI_MAX_ROIS:
+        raise NotImplementedError("roi_targets: %d RoIs per frame exceed %d, the cap of the proposal layer and of the target kernel"
+                                  % (num_rois, ROI_MAX_ROIS))
+    if m > ROI_MAX_SAMPLES:
+        raise NotImplementedError("roi_targets: ROI_PER_IMAGE = %d exceeds %d" % (m, ROI_MAX_SAMPLES))
+    if max_gt > ROI_MAX_GT:
+        raise NotImplementedError("roi_targets: %d ground-truth rows per frame exceed %d" % (max_gt, ROI_MAX_GT))
+    cfg = _RoiTargetCfg()
+    cfg.batch, cfg.num_rois, cfg.max_gt, cfg.roi_per_image = int(batch), int(num_rois), int(max_gt), m
+    cfg.fg_per_image = int(np.round(float(_node(sampler_cfg, "FG_RATIO")) * m))
+    cfg.sample_by_class = int(bool(_node(sampler_cfg, "SAMPLE_ROI_BY_EACH_CLASS", False)))
+    cfg.cls_score_type = ROI_SCORE_TYPES[score]
+    cfg.reg_fg_thresh, cfg.cls_fg_thresh = float(_node(sampler_cfg, "REG_FG_THRESH")), float(_node(sampler_cfg, "CLS_FG_THRESH"))
+    cfg.cls_bg_thresh, cfg.cls_bg_thresh_lo = float(_node(sampler_cfg, "CLS_BG_THRESH")), float(_node(sampler_cfg, "CLS_BG_THRESH_LO"))
+    cfg.hard_bg_ratio = float(_node(sampler_cfg, "HARD_BG_RATIO"))
+    return cfg
+
+
+def roi_targets(rois, roi_scores, roi_labels, gt_boxes, u_fg, u_slot, sampler_cfg):
+    """ProposalTargetLayer.forward + the canonical transform of RoIHeadTemplate.assign_targets of all frames in one launch,
+    nothing read back (csrc/roiloss.hip).  rois [B, R, 7], roi_scores [B, R] fp32, roi_labels [B, R] int64 (1-based), gt_boxes
+    [B, G, 8] fp32, the draws u_fg [B, R] and u_slot [B, M] fp32 in [0, 1), sampler_cfg the reference's ROI_SAMPLER keys.
+    -> the reference's targets dict on the device: rois [B, M, 7], gt_of_rois / gt_of_rois_src [B, M, 8], gt_iou_of_rois,
+    roi_scores [B, M] fp32, roi_labels [B, M] int64, reg_valid_mask [B, M] int32, rcnn_cls_labels [B, M] fp32 (CLS_SCORE_TYPE
+    'cls': 1 / 0 / -1 as floats), and two entries of this project: roi_inds [B, M] int32 (the sampled RoI of every slot) and
+    counts [B, 3] int32 (n_fg, n_hard, n_easy)."""
+    lib = _lib.load()
+    _chk(rois, torch.float32, "rois")
+    if rois.dim() != 3 or rois.shape[2] != 7:
+        raise NotImplementedError("roi_targets: rois must be [B, R, 7]; box codes wider than 7 are not supported (got %s)"
+                                  % (tuple(rois.shape),))
+    B, R = int(rois.shape[0]), int(rois.shape[1])
+    Bg, G = _gt_boxes(gt_boxes)
+    cfg = roi_target_cfg(B, R, G, sampler_cfg)
+    M = int(cfg.roi_per_image)
+    _chk(roi_scores, torch.float32, "roi_scores")
+    _chk(roi_labels, torch.int64, "roi_labels")
+    _chk(u_fg, torch.float32, "u_fg")
+    _chk(u_slot, torch.float32, "u_slot")
+    if Bg != B or tuple(roi_scores.shape) != (B, R) or tuple(roi_labels.shape) != (B, R) or tuple(u_fg.shape) != (B, R) or \
+            tuple(u_slot.shape) != (B, M):
+        raise ValueError("roi_targets: roi_scores, roi_labels and u_fg must be [B, R] = [%d, %d], u_slot [B, M] = [%d, %d] and "
+                         "gt_boxes [B, G, 8]" % (B, R, B, M))
+    dev = rois.device
+    f32 = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
+    out = {"rois": f32(B, M, 7), "roi_labels": torch.empty((B, M), dtype=torch.int64, device=dev), "roi_scores": f32(B, M),
+           "gt_iou_of_rois": f32(B, M), "roi_inds": torch.empty((B, M), dtype=torch.int32, device=dev), "gt_of_rois_src": f32(B, M, 8),
+           "gt_of_rois": f32(B, M, 8), "reg_valid_mask": torch.empty((B, M), dtype=torch.int32, device=dev),
+           "rcnn_cls_labels": f32(B, M), "counts": torch.empty((B, 3), dtype=torch.int32, device=dev)}
+    nbytes = int(lib.df3d_roi_targets_workspace_bytes(ctypes.byref(cfg)))
+    ws = torch.empty((max(nbytes, 8),), dtype=torch.uint8, device=dev)
+    lib.df3d_roi_targets(_ptr(rois), _ptr(roi_scores), _ptr(roi_labels), _ptr(gt_boxes), _ptr(u_fg), _ptr(u_slot), ctypes.byref(cfg),
+                         _ptr(out["rois"]), _ptr(out["roi_labels"]), _ptr(out["roi_scores"]), _ptr(out["gt_iou_of_rois"]),
+                         _ptr(out["roi_inds"]), _ptr(out["gt_of_rois_src"]), _ptr(out["gt_of_rois"]), _ptr(out["reg_valid_mask"]),
+                         _ptr(out["rcnn_cls_labels"]), _ptr(out["counts"]), _ptr(ws), nbytes, _stream())
+    return out
+
+
+class RcnnLossSpec(object):
+    """The loss configuration of ops.rcnn_loss: the reference's LOSS_CONFIG.LOSS_WEIGHTS and CORNER_LOSS_REGULARIZATION."""
+
+    def __init__(self, cls_weight, reg_weight, corner_weight, code_weights, corner_loss=True, beta=1.0 / 9.0):
+        if len(code_weights) != 7:
+            raise NotImplementedError("rcnn_loss: code_weights must have 7 entries, box codes wider than 7 are not supported (got %d)"
+                                      % len(code_weights))
+        self.cls_weight, self.reg_weight, self.corner_weight = float(cls_weight), float(reg_weight), float(corner_weight)
+        self.code_weights, self.corner_loss, self.beta = [float(v) for v in code_weights], bool(corner_loss), float(beta)
+
+    def cfg(self, rows):
+        cfg = _RcnnLossCfg()
+        cfg.num_rows, cfg.corner_loss = int(rows), int(self.corner_loss)
+        cfg.cls_weight, cfg.reg_weight, cfg.corner_weight, cfg.beta = self.cls_weight, self.reg_weight, self.corner_weight, self.beta
+        for e in range(7):
+            cfg.code_weights[e] = self.code_weights[e]
+        return cfg
+
+
+RCNN_TARGET_KEYS = ("rois", "gt_of_rois", "gt_of_rois_src", "reg_valid_mask", "rcnn_cls_labels")
+
+
+def _rcnn_loss_args(rcnn_cls, rcnn_reg, targets, cfg):
+    n = int(cfg.num_rows)
+    _tail_rows(rcnn_cls, n, 1, "rcnn_cls")
+    _tail_rows(rcnn_reg, n, 7, "rcnn_reg")
+    rois, gt, src, mask, labels = [targets[k] for k in RCNN_TARGET_KEYS]
+    for v, dtype, width, name in ((rois, torch.float32, 7, "rois"), (gt, torch.float32, 8, "gt_of_rois"),
+                                  (src, torch.float32, 8, "gt_of_rois_src"), (mask, torch.int32, 1, "reg_valid_mask"),
+                                  (labels, torch.float32, 1, "rcnn_cls_labels")):
+        _chk(v, dtype, name)
+        if v.numel() != n * width:
+            raise ValueError("rcnn_loss: %s must hold %d x %d values for %d rows of rcnn_cls" % (name, n, width, n))
+    return (_ptr(rcnn_cls), int(rcnn_cls.stride(0)), _ptr(rcnn_reg), int(rcnn_reg.stride(0)), _ptr(rois), _ptr(gt), _ptr(src),
+            _ptr(mask), _ptr(labels), ctypes.byref(cfg))
+
+
+class _RcnnLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, rcnn_cls, rcnn_reg, targets, spec):
+        lib = _lib.load()
+        if rcnn_cls.dim() != 2 or rcnn_reg.dim() != 2 or rcnn_cls.shape[1] != 1:
+            raise NotImplementedError("rcnn_loss: rcnn_cls must be [N, 1] (BinaryCrossEntropy on one logit) and rcnn_reg [N, 7]")
+        if rcnn_reg.shape[1] != 7:
+            raise NotImplementedError("rcnn_loss: rcnn_reg must be [N, 7]; box codes wider than 7 are not supported (got %d)"
+                                      % rcnn_reg.shape[1])
+        cfg = spec.cfg(rcnn_cls.shape[0])
+        args = _rcnn_loss_args(rcnn_cls, rcnn_reg, targets, cfg)
+        dev = rcnn_cls.device
+        losses = torch.empty((3,), dtype=torch.float32, device=dev)
+        norms = torch.empty((2,), dtype=torch.float64, device=dev)
+        nbytes = int(lib.df3d_rcnn_loss_workspace_bytes(ctypes.byref(cfg)))
+        ws = torch.empty((max(nbytes, 8),), dtype=torch.uint8, device=dev)
+        lib.df3d_rcnn_loss(*args, _ptr(losses), _ptr(norms), _ptr(ws), nbytes, _stream())
+        ctx.save_for_backward(rcnn_cls, rcnn_reg, norms)
+        ctx.targets, ctx.loss_cfg = {k: targets[k] for k in RCNN_TARGET_KEYS}, cfg
+        return losses
+
+    @staticmethod
+    def backward(ctx, grad_losses):
+        lib = _lib.load()
+        rcnn_cls, rcnn_reg, norms = ctx.saved_tensors
+        upstream = grad_losses.to(torch.float32).contiguous()
+        g_cls = torch.empty(rcnn_cls.shape, dtype=torch.float32, device=rcnn_cls.device)
+        g_reg = torch.empty(rcnn_reg.shape, dtype=torch.float32, device=rcnn_reg.device)
+        lib.df3d_rcnn_loss_grad(*_rcnn_loss_args(rcnn_cls, rcnn_reg, ctx.targets, ctx.loss_cfg), _ptr(norms), _ptr(upstream),
+                                _ptr(g_cls), int(g_cls.stride(0)), _ptr(g_reg), int(g_reg.stride(0)), _stream())
+        return g_cls, g_reg, None, None
+
+
+def rcnn_loss(rcnn_cls, rcnn_reg, targets, spec):
+    """The RCNN losses of the RoI head, fused (csrc/roiloss.hip): rcnn_cls [N, 1], rcnn_reg [N, 7] fp32 (row views with unit
+    column stride), targets the dict of ops.roi_targets (N = B * M rows), spec an RcnnLossSpec.  -> [3] fp32 on the device:
+    rcnn_loss_cls, rcnn_loss_reg, rcnn_loss_corner (0 without CORNER_LOSS_REGULARIZATION or without a foreground row).
+    Differentiable with respect to both inputs: backward is one launch that reads the upstream gradients and the two
+    normalisers (valid rows, foreground rows) on the device."""
+    return _RcnnLoss.apply(rcnn_cls, rcnn_reg, targets, spec)
+
+
 class _HeadTargets(ctypes.Structure):
     _c_name_ = "df3d_head_targets"
     _fields_ = [(n, ctypes.c_void_p) for n in ("hm", "ind", "mask", "cat", "box")]

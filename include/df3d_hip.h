@@ -1546,6 +1546,83 @@ int df3d_anchor_loss_grad(const float *cls, int ld_cls, const float *box, int ld
                           const float *grad_losses, float *grad_cls, int ld_gcls, float *grad_box, int ld_gbox, float *grad_dir,
                           int ld_gdir, void *stream);
 
+/* ---------------------------------------------------------------------------------------------------------------------
+ * Voxel-RCNN second-stage training (csrc/roiloss.hip): the proposal targets and the RCNN losses, with
+ * no device-to-host copy.
+ *
+ * df3d_roi_targets replaces ProposalTargetLayer.forward + the canonical transform of RoIHeadTemplate.assign_targets
+ * (VR/pcdet/models/roi_heads/target_assigner/proposal_target_layer.py, roi_head_template.py:104-134): one launch, one
+ * workgroup per frame.
+ *   rois [B][R][7] f32 (x, y, z, dx, dy, dz, heading), roi_scores [B][R] f32, roi_labels [B][R] int64 (1-based),
+ *   gt_boxes [B][G][8] f32 (box, class), u_fg [B][R] and u_slot [B][M] f32 draws in [0, 1).
+ *   Valid GT: trailing rows whose eight values sum to zero are dropped, row 0 always stays, interior zero rows stay.
+ *   IoU: pcdet's boxes_iou3d_gpu (BEV overlap x height overlap over max(vol_a + vol_b - overlap, 1e-6)) evaluated in
+ *   DOUBLE and rounded once to float32: the clipping of bev_overlap.h on a double box policy (containment margin 1e-8
+ *   instead of the float kernel's 1e-2, which is a float32 guard and moves the area).  Per RoI the maximum over the valid
+ *   rows (sample_by_class: over the rows of the RoI's class; none: overlap 0 and row 0), first maximum wins.
+ *   Lists in ascending RoI index: fg iou >= min(reg_fg, cls_fg); hard bg cls_bg_lo <= iou < reg_fg; easy bg iou < cls_bg_lo.
+ *   Sampling, a function of the draws:
+ *     fg and bg: F = min(fg_per_image, n_fg); the j-th fg RoI has key u_fg[b][j]; the F smallest keys in ascending key order
+ *       (ties: lower j) fill slots 0..F-1; slots F..M-1 are background: with both bg lists the first
+ *       min((int)((M - F) * hard_bg_ratio), n_hard) of them index the hard list and the rest the easy list, with one list all
+ *       index it; slot s takes element floor((double)u_slot[b][s] * n) of its list.
+ *     fg only: every slot s takes element floor((double)u_slot[b][s] * n_fg) of the fg list.  bg only: F = 0.
+ *     neither (NaN overlaps only): every slot takes RoI 0.
+ *   Outputs per slot: out_rois [B][M][7], out_labels [B][M] int64, out_scores, out_ious [B][M] f32, roi_inds [B][M] int32
+ *   (the sampled RoI), gt_of_rois_src [B][M][8] (the assigned row untouched), gt_of_rois [B][M][8] (canonical: minus the
+ *   RoI centre, heading minus roi_ry = heading mod 2 pi, rotated by -roi_ry, heading folded into [-pi/2, pi/2]),
+ *   reg_valid_mask [B][M] int32 (iou > reg_fg), rcnn_cls_labels [B][M] f32 (DF3D_ROI_SCORE_ROI_IOU: 1 above cls_fg, 0 below
+ *   cls_bg, linear between; DF3D_ROI_SCORE_CLS: 1 / 0 / -1), counts [B][3] int32 (n_fg, n_hard, n_easy).
+ *   Limits: R <= DF3D_ROI_MAX_ROIS, M <= DF3D_ROI_MAX_SAMPLES, G <= DF3D_ROI_MAX_GT, B <= 65535.  The ground truth of a
+ *   frame (32 KB at the cap) and the fg keys (16 KB) are staged in LDS; the per-RoI overlaps, assignments and lists live in
+ *   the caller's workspace.
+ *
+ * df3d_rcnn_loss / df3d_rcnn_loss_grad replace get_box_cls_layer_loss + get_box_reg_layer_loss
+ * (roi_head_template.py:136-231 over utils/loss_utils.py:75-136, 209-232) on N = B * M rows.
+ *   rcnn_cls [N][1], rcnn_reg [N][7] f32 rows with row strides in floats; rois [N][7]; gt_of_rois, gt_of_rois_src [N][8];
+ *   reg_valid_mask [N] int32; rcnn_cls_labels [N] f32.
+ *   losses [3] f32: cls = BCE-with-logits over the rows with label >= 0 / max(valid, 1); reg = smooth-L1 (beta, code weights)
+ *   against the ResidualCoder encoding of gt_of_rois against the RoI with centre and heading zeroed, over the mask rows /
+ *   max(fg_sum, 1); corner (corner_loss != 0) = Huber (beta 1) of min(distance to the GT corners, to the pi-flipped GT
+ *   corners) of the decoded box, mean over 8 corners and the mask rows; each times its weight.  fp64 partials per workgroup
+ *   at fixed positions and an ordered final sum.  norms [2] f64 (valid, fg_sum) stay on the device for the gradient.
+ * df3d_rcnn_loss_grad writes every element of grad_cls [N][1] and grad_reg [N][7] (own row strides):
+ *   d(sum_j grad_losses[j] * losses[j]) / d input, grad_losses [3] f32 read from DEVICE memory; a corner distance of exactly
+ *   zero contributes nothing. */
+#define DF3D_ROI_MAX_ROIS 4096
+#define DF3D_ROI_MAX_SAMPLES 1024
+#define DF3D_ROI_MAX_GT 1024
+#define DF3D_ROI_SCORE_ROI_IOU 0
+#define DF3D_ROI_SCORE_CLS 1
+typedef struct df3d_roi_target_cfg {
+  int batch, num_rois, max_gt, roi_per_image;   /* B, R, G, M */
+  int fg_per_image;                             /* round(FG_RATIO * M), rounded by the caller as numpy rounds */
+  int sample_by_class, cls_score_type;
+  double reg_fg_thresh, cls_fg_thresh, cls_bg_thresh, cls_bg_thresh_lo, hard_bg_ratio;
+} df3d_roi_target_cfg;
+typedef struct df3d_rcnn_loss_cfg {
+  int num_rows;                                 /* N */
+  int corner_loss;
+  float cls_weight, reg_weight, corner_weight;
+  float code_weights[7];
+  float beta;                                   /* smooth L1: 1/9 */
+} df3d_rcnn_loss_cfg;
+size_t df3d_roi_targets_workspace_bytes(const df3d_roi_target_cfg *cfg);
+int df3d_roi_targets(const float *rois, const float *roi_scores, const int64_t *roi_labels, const float *gt_boxes,
+                     const float *u_fg, const float *u_slot, const df3d_roi_target_cfg *cfg, float *out_rois,
+                     int64_t *out_labels, float *out_scores, float *out_ious, int32_t *roi_inds, float *gt_of_rois_src,
+                     float *gt_of_rois, int32_t *reg_valid_mask, float *rcnn_cls_labels, int32_t *counts, void *workspace,
+                     size_t workspace_bytes, void *stream);
+size_t df3d_rcnn_loss_workspace_bytes(const df3d_rcnn_loss_cfg *cfg);
+int df3d_rcnn_loss(const float *rcnn_cls, int ld_cls, const float *rcnn_reg, int ld_reg, const float *rois,
+                   const float *gt_of_rois, const float *gt_of_rois_src, const int32_t *reg_valid_mask,
+                   const float *rcnn_cls_labels, const df3d_rcnn_loss_cfg *cfg, float *losses, double *norms, void *workspace,
+                   size_t workspace_bytes, void *stream);
+int df3d_rcnn_loss_grad(const float *rcnn_cls, int ld_cls, const float *rcnn_reg, int ld_reg, const float *rois,
+                        const float *gt_of_rois, const float *gt_of_rois_src, const int32_t *reg_valid_mask,
+                        const float *rcnn_cls_labels, const df3d_rcnn_loss_cfg *cfg, const double *norms,
+                        const float *grad_losses, float *grad_cls, int ld_gcls, float *grad_reg, int ld_greg, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
