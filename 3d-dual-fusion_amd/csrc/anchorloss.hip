@@ -24,6 +24,8 @@
 // the reference's float expressions, evaluated operation by operation (no fused multiply-adds): both passes of the
 // assignment must give the same float for the same (anchor, GT) pair
 #pragma clang fp contract(off)
+#include "anchor_box.h"
+#include "loss_terms.h"
 
 namespace df3d {
 
@@ -32,17 +34,10 @@ constexpr float PI_F = 3.14159265358979323846f;
 constexpr float QUARTER_PI_F = (float)(3.14159265358979323846 / 4.0);
 constexpr float TWO_PI_F = (float)(2.0 * 3.14159265358979323846);
 
-struct AnchorTab {
-  const float *x_shifts, *y_shifts;
-  int batch, H, W, A, S, M;
-  int set[DF3D_MAX_ANCHORS];
-  float anchor[DF3D_MAX_ANCHORS][5];     // centre z, dx, dy, dz, rotation
-};
-
 struct AssignArgs {
   AnchorTab t;
   const float *gt;                        // [B][M][8]
-  int set_class[DF3D_MAX_ANCHORS];
+  int M, set_class[DF3D_MAX_ANCHORS];     // ground-truth rows per frame; the class an anchor set serves
   float matched[DF3D_MAX_ANCHORS], unmatched[DF3D_MAX_ANCHORS];
   float *gt_bev;                          // [B][M][5]: x1, y1, x2, y2, area
   int32_t *gt_cls;                        // [B][M]: class of the row, 0 = padding or past the valid count
@@ -76,25 +71,10 @@ __device__ __forceinline__ float bev_iou(const Bev &a, float gx1, float gy1, flo
   return inter / fmaxf(a.area + garea - inter, 1e-6f);
 }
 
-// ResidualCoder.encode_torch (box_coder_utils.py:13-43) in float32, operation by operation
-__device__ __forceinline__ void residual_encode(const float *g, float xa, float ya, float za, float dxa, float dya, float dza,
-                                                float ra, float *t) {
-  dxa = fmaxf(dxa, 1e-5f), dya = fmaxf(dya, 1e-5f), dza = fmaxf(dza, 1e-5f);
-  const float dxg = fmaxf(g[3], 1e-5f), dyg = fmaxf(g[4], 1e-5f), dzg = fmaxf(g[5], 1e-5f);
-  const float diag = sqrtf(dxa * dxa + dya * dya);
-  t[0] = (g[0] - xa) / diag;
-  t[1] = (g[1] - ya) / diag;
-  t[2] = (g[2] - za) / dza;
-  t[3] = logf(dxg / dxa);
-  t[4] = logf(dyg / dya);
-  t[5] = logf(dzg / dza);
-  t[6] = g[6] - ra;
-}
-
 // grid (batch), 256 threads
 __global__ __launch_bounds__(256) void assign_prepare_kernel(AssignArgs a) {
   __shared__ int s_last;
-  const int b = blockIdx.x, M = a.t.M;
+  const int b = blockIdx.x, M = a.M;
   const float *gt = a.gt + (size_t)b * M * 8;
   if (threadIdx.x == 0) s_last = 0;
   __syncthreads();
@@ -135,10 +115,9 @@ __global__ __launch_bounds__(256) void assign_pass_kernel(AssignArgs a) {
   __shared__ float s_bev[GT_CHUNK][5];
   __shared__ int s_cls[GT_CHUNK];
   const AnchorTab &t = a.t;
-  const int b = blockIdx.y, M = t.M, HW = t.H * t.W;
+  const int b = blockIdx.y, M = a.M, HW = t.H * t.W;
   const int pix = blockIdx.x * 256 + threadIdx.x;
   const bool live = pix < HW;
-  const int py = live ? pix / t.W : 0, px = live ? pix - py * t.W : 0;
   const int valid = a.valid[b];
   const int nchunks = (valid + GT_CHUNK - 1) / GT_CHUNK;
   const size_t per_frame = (size_t)HW * t.A;
@@ -146,8 +125,8 @@ __global__ __launch_bounds__(256) void assign_pass_kernel(AssignArgs a) {
   for (int an = 0; an < t.A; ++an) {
     const int s = t.set[an];
     const int my_class = a.set_class[s];
-    const float *an5 = t.anchor[an];
-    const float xa = t.x_shifts[s * t.W + px], ya = t.y_shifts[s * t.H + py];
+    float xa, ya;
+    const float *an5 = anchor_at(t, live ? pix : 0, an, xa, ya);    // (a thread past the map reads pixel 0 and writes nothing)
     const Bev box = aligned_bev(xa, ya, an5[1], an5[2], an5[4]);
     float best = -1.f;
     int arg = -1;
@@ -215,7 +194,7 @@ __global__ __launch_bounds__(256) void assign_pass_kernel(AssignArgs a) {
 struct LossArgs {
   AnchorTab t;
   const float *cls, *box, *dir, *gt;
-  int ld_cls, ld_box, ld_dir;
+  int M, ld_cls, ld_box, ld_dir;          // M: ground-truth rows per frame
   const int32_t *labels, *gt_ids, *num_pos;
   int C, NB;
   float dir_offset;
@@ -236,31 +215,21 @@ __device__ __forceinline__ void load_site(const LossArgs &a, long long i, Site &
   const long long per_frame = (long long)t.H * t.W * t.A;
   s.b = (int)(i / per_frame);
   const int idx = (int)(i - (long long)s.b * per_frame);
-  const int pix = idx / t.A;
-  s.an = idx - pix * t.A;
+  int pix;
+  anchor_split(t, idx, pix, s.an);
   s.row = (long long)s.b * t.H * t.W + pix;
   s.label = a.labels[i];
   const int np = a.num_pos[s.b];
   s.w = 1.0 / (double)(np > 1 ? np : 1);
   const int id = a.gt_ids[i];
-  s.positive = s.label > 0 && id >= 0 && id < t.M;
+  s.positive = s.label > 0 && id >= 0 && id < a.M;
   s.bin = 0;
   if (!s.positive) return;
-  const int y = pix / t.W, x = pix - y * t.W;
-  const int set = t.set[s.an];
-  const float *an5 = t.anchor[s.an];
-  const float xa = t.x_shifts[set * t.W + x], ya = t.y_shifts[set * t.H + y];
-  const float *g = a.gt + ((size_t)s.b * t.M + id) * 8;
+  float xa, ya;
+  const float *an5 = anchor_at(t, pix, s.an, xa, ya);
+  const float *g = a.gt + ((size_t)s.b * a.M + id) * 8;
   // the target in fp64 (the loss values), and code 6 in fp32 as the reference holds it (the direction bin is a floor)
-  const double dxa = fmax((double)an5[1], 1e-5), dya = fmax((double)an5[2], 1e-5), dza = fmax((double)an5[3], 1e-5);
-  const double diag = sqrt(dxa * dxa + dya * dya);
-  s.tg[0] = ((double)g[0] - (double)xa) / diag;
-  s.tg[1] = ((double)g[1] - (double)ya) / diag;
-  s.tg[2] = ((double)g[2] - (double)an5[0]) / dza;
-  s.tg[3] = log(fmax((double)g[3], 1e-5) / dxa);
-  s.tg[4] = log(fmax((double)g[4], 1e-5) / dya);
-  s.tg[5] = log(fmax((double)g[5], 1e-5) / dza);
-  s.tg[6] = (double)g[6] - (double)an5[4];
+  residual_encode<double>(g, xa, ya, an5[0], an5[1], an5[2], an5[3], an5[4], s.tg);
   if (a.dir) {                                                      // get_direction_target (anchor_head_template.py:146-160)
     const float t6 = g[6] - an5[4];
     const float rot_gt = t6 + an5[4];
@@ -277,10 +246,11 @@ __device__ __forceinline__ void focal(double x, double tt, double &value, double
   const double p = 1.0 / (1.0 + exp(-x));
   const double alpha_w = tt * 0.25 + (1.0 - tt) * 0.75;
   const double pt = tt * (1.0 - p) + (1.0 - tt) * p;
-  const double bce = fmax(x, 0.0) - x * tt + log1p(exp(-fabs(x)));
+  double bce, dbce;
+  bce_with_logits(x, tt, bce, dbce);
   value = alpha_w * pt * pt * bce;
   const double dpt = (1.0 - 2.0 * tt) * p * (1.0 - p);
-  dx = alpha_w * (2.0 * pt * dpt * bce + pt * pt * (p - tt));
+  dx = alpha_w * (2.0 * pt * dpt * bce + pt * pt * dbce);
 }
 
 // code-weighted difference of code e (add_sin_difference on code 6) and its derivative with respect to the prediction
@@ -315,29 +285,21 @@ __global__ __launch_bounds__(256) void anchor_loss_kernel(LossArgs a, long long 
     if (s.positive) {
       const float *p = a.box + s.row * a.ld_box + s.an * 7;
       for (int e = 0; e < 7; ++e) {
-        double d, dd;
+        double d, dd, v, slope;
         code_diff(a, p, s, e, d, dd);
-        const double n = fabs(d);
-        l_loc += (n < a.beta ? 0.5 * n * n / a.beta : n - 0.5 * a.beta) * s.w;
+        smooth_l1(d, a.beta, v, slope);                             // (beta >= 1e-5 here: check_loss_cfg)
+        l_loc += v * s.w;
       }
       if (a.dir) {
         const float *q = a.dir + s.row * a.ld_dir + s.an * a.NB;
-        double mx = (double)q[0];
-        for (int k = 1; k < a.NB; ++k) mx = fmax(mx, (double)q[k]);
-        double sum = 0.0;
-        for (int k = 0; k < a.NB; ++k) sum += exp((double)q[k] - mx);
+        double mx, sum;
+        softmax_stats(q, a.NB, mx, sum);
         l_dir = (mx + log(sum) - (double)q[s.bin]) * s.w;
       }
     }
   }
-  l_cls = block_sum256(l_cls, s_red);
-  l_loc = block_sum256(l_loc, s_red);
-  l_dir = block_sum256(l_dir, s_red);
-  if (threadIdx.x == 0) {
-    partials[(size_t)blockIdx.x * 3 + 0] = l_cls;
-    partials[(size_t)blockIdx.x * 3 + 1] = l_loc;
-    partials[(size_t)blockIdx.x * 3 + 2] = l_dir;
-  }
+  const double v[3] = {l_cls, l_loc, l_dir};
+  partials_write<3>(v, partials, s_red);
 }
 
 // one workgroup: the partials in a fixed order -> the three scalars, each sum / B * weight
@@ -345,14 +307,11 @@ __global__ __launch_bounds__(256) void anchor_loss_final_kernel(const double *__
                                                                 double w_cls, double w_loc, double w_dir,
                                                                 float *__restrict__ losses) {
   __shared__ double s_red[4];
-  double acc[3] = {0.0, 0.0, 0.0};
-  for (int k = threadIdx.x; k < nblocks; k += 256)
-    for (int j = 0; j < 3; ++j) acc[j] += partials[(size_t)k * 3 + j];
+  double tot[3];
+  partials_sum<3>(partials, nblocks, tot, s_red);
   const double w[3] = {w_cls, w_loc, w_dir};
-  for (int j = 0; j < 3; ++j) {
-    const double v = block_sum256(acc[j], s_red);
-    if (threadIdx.x == 0) losses[j] = (float)(v / (double)batch * w[j]);
-  }
+  if (threadIdx.x == 0)
+    for (int j = 0; j < 3; ++j) losses[j] = (float)(tot[j] / (double)batch * w[j]);
 }
 
 // grid (ceil(B*N / 256)): every element of the three gradient maps
@@ -382,10 +341,10 @@ __global__ __launch_bounds__(256) void anchor_loss_grad_kernel(LossArgs a, long 
   for (int e = 0; e < 7; ++e) {
     double g = 0.0;
     if (s.positive) {
-      double d, dd;
+      double d, dd, v, slope;
       code_diff(a, p, s, e, d, dd);
-      const double n = fabs(d);
-      g = (n < a.beta ? d / a.beta : (d > 0.0 ? 1.0 : (d < 0.0 ? -1.0 : 0.0))) * dd * k_loc;
+      smooth_l1(d, a.beta, v, slope);
+      g = slope * dd * k_loc;
     }
     gb[e] = (float)g;
   }
@@ -393,10 +352,8 @@ __global__ __launch_bounds__(256) void anchor_loss_grad_kernel(LossArgs a, long 
     const float *q = a.dir + s.row * a.ld_dir + s.an * a.NB;
     float *gd = g_dir + s.row * ld_gdir + s.an * a.NB;
     if (s.positive) {
-      double mx = (double)q[0];
-      for (int k = 1; k < a.NB; ++k) mx = fmax(mx, (double)q[k]);
-      double sum = 0.0;
-      for (int k = 0; k < a.NB; ++k) sum += exp((double)q[k] - mx);
+      double mx, sum;
+      softmax_stats(q, a.NB, mx, sum);
       for (int k = 0; k < a.NB; ++k) gd[k] = (float)((exp((double)q[k] - mx) / sum - (k == s.bin ? 1.0 : 0.0)) * k_dir);
     } else {
       for (int k = 0; k < a.NB; ++k) gd[k] = 0.f;
@@ -408,29 +365,13 @@ __global__ __launch_bounds__(256) void anchor_loss_grad_kernel(LossArgs a, long 
 
 using namespace df3d;
 
-// the limits the assignment and the losses share; `what` names the entry point
+// the limits the assignment and the losses share: the table's, then the ground-truth rows; `what` names the entry point
 static int check_tables(const df3d_anchor_cfg *c, int max_gt, const char *what) {
-  DF3D_CHECK_ARG(c->batch > 0 && c->H > 0 && c->W > 0, "%s: bad map size", what);
-  DF3D_CHECK_ARG(c->batch <= 255, "%s: at most 255 frames (got %d)", what, c->batch);
-  DF3D_CHECK_ARG(c->num_anchors > 0 && c->num_anchors <= DF3D_MAX_ANCHORS, "%s: 1..%d anchors per location (DF3D_MAX_ANCHORS)",
-                 what, DF3D_MAX_ANCHORS);
-  DF3D_CHECK_ARG(c->num_sets > 0 && c->num_sets <= DF3D_MAX_ANCHORS, "%s: 1..%d anchor sets", what, DF3D_MAX_ANCHORS);
-  DF3D_CHECK_ARG((long long)c->H * c->W * c->num_anchors <= (1ll << 22), "%s: at most 2^22 anchors per frame (H*W*A)", what);
+  int rc = anchor_check(c, what);
+  if (rc) return rc;
   DF3D_CHECK_ARG(max_gt > 0 && max_gt <= DF3D_ANCHOR_MAX_GT, "%s: 1..%d ground-truth rows per frame (got M = %d)", what,
                  DF3D_ANCHOR_MAX_GT, max_gt);
-  for (int a = 0; a < c->num_anchors; ++a)
-    DF3D_CHECK_ARG(c->anchor_set[a] >= 0 && c->anchor_set[a] < c->num_sets, "%s: anchor %d names set %d of %d", what, a,
-                   c->anchor_set[a], c->num_sets);
   return DF3D_OK;
-}
-
-static void fill_tables(AnchorTab &t, const df3d_anchor_cfg *c, int max_gt, const float *x_shifts, const float *y_shifts) {
-  t.x_shifts = x_shifts, t.y_shifts = y_shifts;
-  t.batch = c->batch, t.H = c->H, t.W = c->W, t.A = c->num_anchors, t.S = c->num_sets, t.M = max_gt;
-  for (int i = 0; i < c->num_anchors; ++i) {
-    t.set[i] = c->anchor_set[i];
-    for (int e = 0; e < 5; ++e) t.anchor[i][e] = c->anchor[i][e];
-  }
 }
 
 struct AssignPlan {
@@ -438,18 +379,13 @@ struct AssignPlan {
 };
 
 static void assign_plan(int batch, int sets, int M, AssignPlan &p) {
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    size_t o = align_up(off, 256);
-    off = o + bytes;
-    return o;
-  };
+  WsLayout l;
   const size_t rows = (size_t)batch * M;
-  p.gt_bev = take(rows * 5 * 4);
-  p.gt_cls = take(rows * 4);
-  p.valid = take((size_t)batch * 4);
-  p.gt_max = take(rows * sets * 4);
-  p.total = align_up(off, 256);
+  p.gt_bev = l.take(rows * 5 * 4);
+  p.gt_cls = l.take(rows * 4);
+  p.valid = l.take((size_t)batch * 4);
+  p.gt_max = l.take(rows * sets * 4);
+  p.total = l.total();
 }
 
 static int check_assign_cfg(const df3d_anchor_assign_cfg *cfg) {
@@ -487,8 +423,8 @@ extern "C" int df3d_anchor_assign(const float *x_shifts, const float *y_shifts, 
 
   AssignArgs a;
   memset(&a, 0, sizeof(a));
-  fill_tables(a.t, c, cfg->max_gt, x_shifts, y_shifts);
-  a.gt = gt_boxes;
+  anchor_fill(a.t, c, x_shifts, y_shifts);
+  a.M = cfg->max_gt, a.gt = gt_boxes;
   for (int s = 0; s < c->num_sets; ++s) {
     a.set_class[s] = cfg->set_class[s];
     a.matched[s] = cfg->matched_threshold[s];
@@ -529,12 +465,11 @@ static int fill_loss_args(LossArgs &a, const char *what, const float *cls, int l
   DF3D_CHECK_ARG(!dir || (c->num_dir_bins > 0 && ld_dir >= c->num_anchors * c->num_dir_bins),
                  "%s: direction map needs num_dir_bins > 0 and ld_dir >= anchors * bins", what);
   memset(&a, 0, sizeof(a));
-  fill_tables(a.t, c, cfg->max_gt, x_shifts, y_shifts);
-  a.cls = cls, a.box = box, a.dir = dir, a.gt = gt_boxes;
+  anchor_fill(a.t, c, x_shifts, y_shifts);
+  a.M = cfg->max_gt, a.cls = cls, a.box = box, a.dir = dir, a.gt = gt_boxes;
   a.ld_cls = ld_cls, a.ld_box = ld_box, a.ld_dir = ld_dir;
   a.labels = labels, a.gt_ids = gt_ids, a.num_pos = num_pos;
-  a.C = c->num_classes, a.NB = c->num_dir_bins;
-  a.dir_offset = c->dir_offset;
+  a.C = c->num_classes, a.NB = c->num_dir_bins, a.dir_offset = c->dir_offset;
   for (int e = 0; e < 7; ++e) a.cw[e] = (double)cfg->code_weights[e];
   a.beta = (double)cfg->beta;
   a.weight[0] = (double)cfg->cls_weight, a.weight[1] = (double)cfg->loc_weight, a.weight[2] = (double)cfg->dir_weight;
@@ -545,7 +480,7 @@ static long long loss_total(const df3d_anchor_cfg *c) { return (long long)c->bat
 
 extern "C" size_t df3d_anchor_loss_workspace_bytes(const df3d_anchor_loss_cfg *cfg) {
   if (!cfg || cfg->anchors.batch <= 0 || cfg->anchors.H <= 0 || cfg->anchors.W <= 0 || cfg->anchors.num_anchors <= 0) return 0;
-  return align_up((size_t)cdiv(loss_total(&cfg->anchors), 256) * 3 * sizeof(double), 256);
+  return partials_bytes(cdiv(loss_total(&cfg->anchors), 256), 3);
 }
 
 extern "C" int df3d_anchor_loss(const float *cls, int ld_cls, const float *box, int ld_box, const float *dir, int ld_dir,
@@ -560,7 +495,7 @@ extern "C" int df3d_anchor_loss(const float *cls, int ld_cls, const float *box, 
   DF3D_CHECK_ARG(losses && workspace, "anchor_loss: null output");
   const long long total = loss_total(&cfg->anchors);
   const int nblocks = cdiv(total, 256);
-  const size_t need = align_up((size_t)nblocks * 3 * sizeof(double), 256);
+  const size_t need = partials_bytes(nblocks, 3);
   DF3D_CHECK_ARG(workspace_bytes >= need, "anchor_loss: workspace %zu < %zu bytes", workspace_bytes, need);
   double *partials = (double *)workspace;
   hipLaunchKernelGGL(anchor_loss_kernel, dim3(nblocks), dim3(256), 0, stream, a, total, partials);

@@ -232,6 +232,13 @@ struct Arena {
   }
 };
 static inline size_t arena_need(size_t cur, size_t bytes) { return align_up(cur, 256) + bytes; }
+// The same carving before there is a pointer: byte offsets first (a ..._workspace_bytes entry needs only total()), pointers
+// later.  `off` is the raw, unaligned end of what has been taken (topk_layout clears the workspace up to it).
+struct WsLayout {
+  size_t off = 0;
+  size_t take(size_t bytes) { return (off = align_up(off, 256) + bytes) - bytes; }
+  size_t total() const { return align_up(off, 256); }
+};
 
 // ---- device-wide exclusive scan of uint32 (3 launches; n up to 2^31) -------------------
 // scan_bytes(n): scratch needed.  out may alias in.  total (device u32*, may be NULL)

@@ -157,25 +157,20 @@ struct TailPlan {
 
 static int tail_plan(int ntasks, int batch, int H, int W, int pre_max, TailPlan &p) {
   const size_t nkeys = (size_t)ntasks * batch * H * W, S = (size_t)ntasks * batch;
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    size_t o = align_up(off, 256);
-    off = o + bytes;
-    return o;
-  };
-  p.keys_in = take(nkeys * 8);
-  p.keys_out = take(S * pre_max * 8);
+  WsLayout l;
+  p.keys_in = l.take(nkeys * 8);
+  p.keys_out = l.take(S * pre_max * 8);
   p.select_bytes = topk_keys_workspace((int)S, (long long)H * W, pre_max);
-  p.select = take(p.select_bytes);
-  p.cand_boxes = take(S * pre_max * 9 * 4);
-  p.cand_scores = take(S * pre_max * 4);
-  p.cand_labels = take(S * pre_max * 4);
-  p.nms_boxes = take(S * pre_max * 7 * 4);
-  p.counts = take(S * 4);
-  p.keep = take(S * pre_max * 4);
+  p.select = l.take(p.select_bytes);
+  p.cand_boxes = l.take(S * pre_max * 9 * 4);
+  p.cand_scores = l.take(S * pre_max * 4);
+  p.cand_labels = l.take(S * pre_max * 4);
+  p.nms_boxes = l.take(S * pre_max * 7 * 4);
+  p.counts = l.take(S * 4);
+  p.keep = l.take(S * pre_max * 4);
   p.mask_bytes = df3d_nms_bev_workspace_bytes((int)S, pre_max);
-  p.mask = take(p.mask_bytes);
-  p.total = align_up(off, 256);
+  p.mask = l.take(p.mask_bytes);
+  p.total = l.total();
   return DF3D_OK;
 }
 

@@ -772,17 +772,17 @@ static MbLayout mb_layout(int N, int M, int Lq, int L, int P, const int64_t *hw,
   for (int l = 0; l < L; ++l) tiles += (size_t)cdiv((int)hw[l * 2], MB_T) * cdiv((int)hw[l * 2 + 1], MB_T);
   w.nbm = tiles * M, w.ppm = (size_t)Lq * M * L * P, w.mw = w.nbm + w.ppm / MB_CHUNK + 1;
   const size_t n = (size_t)N;
-  auto take = [&w](size_t bytes) { return (w.bytes = arena_need(w.bytes, bytes)) - bytes; };
-  w.nz = take(n * Lq * M);
-  w.count = take(n * w.nbm * 4);
-  w.cursor = take(n * w.nbm * 4);                              // (adjacent to `count`: one memset up to `offset` clears both)
-  w.offset = take(n * w.nbm * 4);
-  w.binw = take(n * (w.nbm + 1) * 4);
-  w.nwork = take(n * 4);
-  w.work = take(n * w.mw * 12);
-  w.scattered = take(n * w.ppm * 4);
-  if (ordered) w.sorted = take(n * w.ppm * 4);
-  w.bytes = align_up(w.bytes, 256);
+  WsLayout l;
+  w.nz = l.take(n * Lq * M);
+  w.count = l.take(n * w.nbm * 4);
+  w.cursor = l.take(n * w.nbm * 4);                            // (adjacent to `count`: one memset up to `offset` clears both)
+  w.offset = l.take(n * w.nbm * 4);
+  w.binw = l.take(n * (w.nbm + 1) * 4);
+  w.nwork = l.take(n * 4);
+  w.work = l.take(n * w.mw * 12);
+  w.scattered = l.take(n * w.ppm * 4);
+  if (ordered) w.sorted = l.take(n * w.ppm * 4);
+  w.bytes = l.total();
   return w;
 }
 

@@ -25,19 +25,17 @@
 
 // the reference's float expressions, evaluated operation by operation (no fused multiply-adds)
 #pragma clang fp contract(off)
+#include "anchor_box.h"
 
 namespace df3d {
 
 struct AnchorArgs {
-  const float *cls, *box, *dir, *x_shifts, *y_shifts;
+  AnchorTab t;
+  const float *cls, *box, *dir;
   int ld_cls, ld_box, ld_dir;
-  int batch, H, W, A, C, NB, k;
-  int set[DF3D_MAX_ANCHORS];
-  float anchor[DF3D_MAX_ANCHORS][5];     // centre z, dx, dy, dz, rotation
+  int C, NB, k;
   float dir_offset, dir_limit_offset, period;
 };
-
-constexpr int ANCHOR_INDEX_BITS = 22;      // 8 + 2 + 32 + 22: the select orders the low 54 bits within a segment
 
 // float -> unsigned whose order is the float order (-0 counts as +0, like the comparison torch.topk makes)
 __device__ __forceinline__ unsigned ordered_bits(float v) {
@@ -60,30 +58,18 @@ __device__ __forceinline__ void logit_label(const float *p, int C, float &score,
 }
 
 __global__ __launch_bounds__(256) void anchor_keys_kernel(AnchorArgs a, unsigned long long *__restrict__ keys) {
-  const long long per_frame = (long long)a.H * a.W * a.A;
+  const long long per_frame = (long long)a.t.H * a.t.W * a.t.A;
   const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (i >= per_frame * a.batch) return;
+  if (i >= per_frame * a.t.batch) return;
   const int b = (int)(i / per_frame);
   const int idx = (int)(i - (long long)b * per_frame);
-  const int pix = idx / a.A, an = idx - pix * a.A;
+  int pix, an;
+  anchor_split(a.t, idx, pix, an);
   float score;
   int label;
-  logit_label(a.cls + ((long long)b * a.H * a.W + pix) * a.ld_cls + an * a.C, a.C, score, label);
+  logit_label(a.cls + ((long long)b * a.t.H * a.t.W + pix) * a.ld_cls + an * a.C, a.C, score, label);
   const unsigned inv = ~ordered_bits(score);
   keys[i] = ((unsigned long long)b << 56) | ((unsigned long long)inv << ANCHOR_INDEX_BITS) | (unsigned)idx;
-}
-
-// ResidualCoder.decode_torch (box_coder_utils.py:45-77) of one box against one anchor
-__device__ __forceinline__ void residual_decode(const float *t, float xa, float ya, float za, float dxa, float dya, float dza,
-                                                float ra, float *g) {
-  const float diag = sqrtf(dxa * dxa + dya * dya);
-  g[0] = t[0] * diag + xa;
-  g[1] = t[1] * diag + ya;
-  g[2] = t[2] * dza + za;
-  g[3] = expf(t[3]) * dxa;
-  g[4] = expf(t[4]) * dya;
-  g[5] = expf(t[5]) * dza;
-  g[6] = t[6] + ra;
 }
 
 // grid (ceil(k / 256), batch)
@@ -94,17 +80,16 @@ __global__ __launch_bounds__(256) void anchor_gather_kernel(AnchorArgs a, const 
   if (r >= a.k) return;
   const size_t o = (size_t)b * a.k + r;
   const int idx = (int)(keys[o] & ((1ull << ANCHOR_INDEX_BITS) - 1));
-  const int pix = idx / a.A, an = idx - pix * a.A;
-  const int y = pix / a.W, x = pix - y * a.W;
-  const long long row = (long long)b * a.H * a.W + pix;
+  int pix, an;
+  anchor_split(a.t, idx, pix, an);
+  const long long row = (long long)b * a.t.H * a.t.W + pix;
   float score;
   int label;
   logit_label(a.cls + row * a.ld_cls + an * a.C, a.C, score, label);
-  const int s = a.set[an];
-  const float *an5 = a.anchor[an];
+  float xa, ya;
+  const float *an5 = anchor_at(a.t, pix, an, xa, ya);
   float g[7];
-  residual_decode(a.box + row * a.ld_box + an * 7, a.x_shifts[s * a.W + x], a.y_shifts[s * a.H + y], an5[0], an5[1], an5[2],
-                  an5[3], an5[4], g);
+  residual_decode(a.box + row * a.ld_box + an * 7, xa, ya, an5[0], an5[1], an5[2], an5[3], an5[4], g);
   if (a.dir) {                                        // anchor_head_template.py:254-265
     const float *d = a.dir + row * a.ld_dir + an * a.NB;
     float best = d[0];
@@ -154,25 +139,20 @@ struct ProposalPlan {
 };
 
 static void proposal_plan(int batch, long long per_frame, int pre_max, ProposalPlan &p) {
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    size_t o = align_up(off, 256);
-    off = o + bytes;
-    return o;
-  };
+  WsLayout l;
   p.k = (int)(per_frame < pre_max ? per_frame : pre_max);
   const size_t S = (size_t)batch, k = (size_t)p.k;
-  p.keys_in = take(S * per_frame * 8);
-  p.keys_out = take(S * k * 8);
+  p.keys_in = l.take(S * per_frame * 8);
+  p.keys_out = l.take(S * k * 8);
   p.select_bytes = topk_keys_workspace(batch, per_frame, p.k);
-  p.select = take(p.select_bytes);
-  p.cand_boxes = take(S * k * 7 * 4);
-  p.cand_scores = take(S * k * 4);
-  p.cand_labels = take(S * k * 4);
-  p.keep = take(S * k * 4);
+  p.select = l.take(p.select_bytes);
+  p.cand_boxes = l.take(S * k * 7 * 4);
+  p.cand_scores = l.take(S * k * 4);
+  p.cand_labels = l.take(S * k * 4);
+  p.keep = l.take(S * k * 4);
   p.mask_bytes = df3d_nms_bev_workspace_bytes(batch, p.k);
-  p.mask = take(p.mask_bytes);
-  p.total = align_up(off, 256);
+  p.mask = l.take(p.mask_bytes);
+  p.total = l.total();
 }
 
 // ---- RoI decode and final selection ------------------------------------------------------------------------------------
@@ -257,26 +237,6 @@ __global__ __launch_bounds__(128) void final_compact_kernel(RoiArgs a, const flo
 
 using namespace df3d;
 
-static int check_anchor_cfg(const df3d_anchor_cfg *cfg) {
-  DF3D_CHECK_ARG(cfg, "anchor_proposals: null config");
-  DF3D_CHECK_ARG(cfg->batch > 0 && cfg->H > 0 && cfg->W > 0, "anchor_proposals: bad map size");
-  DF3D_CHECK_ARG(cfg->batch <= 255, "anchor_proposals: at most 255 frames");
-  DF3D_CHECK_ARG(cfg->num_anchors > 0 && cfg->num_anchors <= DF3D_MAX_ANCHORS, "anchor_proposals: 1..%d anchors per location",
-                 DF3D_MAX_ANCHORS);
-  DF3D_CHECK_ARG(cfg->num_classes > 0 && cfg->num_dir_bins >= 0, "anchor_proposals: bad class / direction-bin count");
-  DF3D_CHECK_ARG(cfg->num_sets > 0 && cfg->num_sets <= DF3D_MAX_ANCHORS, "anchor_proposals: 1..%d anchor sets",
-                 DF3D_MAX_ANCHORS);
-  DF3D_CHECK_ARG((long long)cfg->H * cfg->W * cfg->num_anchors <= (1 << ANCHOR_INDEX_BITS),
-                 "anchor_proposals: at most 2^%d anchors per frame", ANCHOR_INDEX_BITS);
-  DF3D_CHECK_ARG(cfg->pre_max > 0 && cfg->pre_max <= 4096, "anchor_proposals: 0 < NMS_PRE_MAXSIZE <= 4096 (got %d)",
-                 cfg->pre_max);
-  DF3D_CHECK_ARG(cfg->post_max > 0, "anchor_proposals: NMS_POST_MAXSIZE > 0");
-  for (int a = 0; a < cfg->num_anchors; ++a)
-    DF3D_CHECK_ARG(cfg->anchor_set[a] >= 0 && cfg->anchor_set[a] < cfg->num_sets, "anchor_proposals: anchor %d names set %d of %d",
-                   a, cfg->anchor_set[a], cfg->num_sets);
-  return DF3D_OK;
-}
-
 extern "C" size_t df3d_anchor_proposals_workspace_bytes(const df3d_anchor_cfg *cfg) {
   if (!cfg || cfg->batch <= 0 || cfg->H <= 0 || cfg->W <= 0 || cfg->num_anchors <= 0 || cfg->pre_max <= 0 || cfg->pre_max > 4096)
     return 0;
@@ -290,8 +250,13 @@ extern "C" int df3d_anchor_proposals(const float *cls, int ld_cls, const float *
                                      float *roi_scores, long long *roi_labels, int32_t *num, void *workspace,
                                      size_t workspace_bytes, void *stream_) {
   hipStream_t stream = (hipStream_t)stream_;
-  int rc = check_anchor_cfg(cfg);
+  DF3D_CHECK_ARG(cfg, "anchor_proposals: null config");
+  int rc = anchor_check(cfg, "anchor_proposals");
   if (rc) return rc;
+  DF3D_CHECK_ARG(cfg->num_classes > 0 && cfg->num_dir_bins >= 0, "anchor_proposals: bad class / direction-bin count");
+  DF3D_CHECK_ARG(cfg->pre_max > 0 && cfg->pre_max <= 4096, "anchor_proposals: 0 < NMS_PRE_MAXSIZE <= 4096 (got %d)",
+                 cfg->pre_max);
+  DF3D_CHECK_ARG(cfg->post_max > 0, "anchor_proposals: NMS_POST_MAXSIZE > 0");
   DF3D_CHECK_ARG(cls && box && x_shifts && y_shifts, "anchor_proposals: null input");
   DF3D_CHECK_ARG(rois && roi_scores && roi_labels && num && workspace, "anchor_proposals: null output");
   DF3D_CHECK_ARG(ld_cls >= cfg->num_anchors * cfg->num_classes && ld_box >= cfg->num_anchors * 7,
@@ -305,16 +270,11 @@ extern "C" int df3d_anchor_proposals(const float *cls, int ld_cls, const float *
 
   AnchorArgs a;
   memset(&a, 0, sizeof(a));
-  a.cls = cls, a.box = box, a.dir = dir, a.x_shifts = x_shifts, a.y_shifts = y_shifts;
+  anchor_fill(a.t, cfg, x_shifts, y_shifts);
+  a.cls = cls, a.box = box, a.dir = dir;
   a.ld_cls = ld_cls, a.ld_box = ld_box, a.ld_dir = ld_dir;
-  a.batch = cfg->batch, a.H = cfg->H, a.W = cfg->W, a.A = cfg->num_anchors, a.C = cfg->num_classes, a.NB = cfg->num_dir_bins;
-  a.k = p.k;
-  for (int i = 0; i < cfg->num_anchors; ++i) {
-    a.set[i] = cfg->anchor_set[i];
-    for (int e = 0; e < 5; ++e) a.anchor[i][e] = cfg->anchor[i][e];
-  }
-  a.dir_offset = cfg->dir_offset;
-  a.dir_limit_offset = cfg->dir_limit_offset;
+  a.C = cfg->num_classes, a.NB = cfg->num_dir_bins, a.k = p.k;
+  a.dir_offset = cfg->dir_offset, a.dir_limit_offset = cfg->dir_limit_offset;
   a.period = cfg->num_dir_bins > 0 ? (float)(2.0 * 3.141592653589793 / cfg->num_dir_bins) : 0.f;
 
   char *ws = (char *)workspace;

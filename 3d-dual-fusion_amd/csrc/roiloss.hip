@@ -17,8 +17,10 @@
 
 #include "common.h"
 
-#pragma clang fp contract(off)         // before the clipping code: bev_overlap.h relies on it
+#pragma clang fp contract(off)         // before the shared device code: the three headers rely on it
+#include "anchor_box.h"
 #include "bev_overlap.h"
+#include "loss_terms.h"
 
 namespace df3d {
 
@@ -278,9 +280,7 @@ __device__ void row_terms(const RcnnArgs &a, int i, RowTerms &t) {
   for (int e = 0; e < 7; ++e) t.d_reg[e] = t.d_corner[e] = 0.0;
   const double label = (double)a.labels[i];
   if (label >= 0.0) {                                               // BCE with logits, stable form
-    const double x = (double)a.cls[(size_t)i * a.ld_cls];
-    t.l_cls = fmax(x, 0.0) - x * label + log1p(exp(-fabs(x)));
-    t.d_cls = 1.0 / (1.0 + exp(-x)) - label;
+    bce_with_logits((double)a.cls[(size_t)i * a.ld_cls], label, t.l_cls, t.d_cls);
     t.valid = 1.0;
   }
   if (a.mask[i] <= 0) return;
@@ -288,35 +288,22 @@ __device__ void row_terms(const RcnnArgs &a, int i, RowTerms &t) {
   const float *p = a.reg + (size_t)i * a.ld_reg;
   const float *r = a.rois + (size_t)i * 7, *g = a.gt + (size_t)i * 8, *s = a.src + (size_t)i * 8;
   {  // ResidualCoder.encode_torch against the RoI with centre and heading zeroed; smooth L1
-    const double dxa = fmax((double)r[3], 1e-5), dya = fmax((double)r[4], 1e-5), dza = fmax((double)r[5], 1e-5);
-    const double diag = sqrt(dxa * dxa + dya * dya);
     double tg[7];
-    tg[0] = (double)g[0] / diag;
-    tg[1] = (double)g[1] / diag;
-    tg[2] = (double)g[2] / dza;
-    tg[3] = log(fmax((double)g[3], 1e-5) / dxa);
-    tg[4] = log(fmax((double)g[4], 1e-5) / dya);
-    tg[5] = log(fmax((double)g[5], 1e-5) / dza);
-    tg[6] = (double)g[6];
+    residual_encode<double>(g, 0.0, 0.0, 0.0, r[3], r[4], r[5], 0.0, tg);
     for (int e = 0; e < 7; ++e) {
       if (tg[e] != tg[e]) continue;                                 // NaN targets are ignored (loss_utils.py:122)
-      const double d = a.cw[e] * ((double)p[e] - tg[e]);
-      const double n = fabs(d);
-      if (a.beta < 1e-5) {
-        t.l_reg += n;
-        t.d_reg[e] = (d > 0.0 ? 1.0 : (d < 0.0 ? -1.0 : 0.0)) * a.cw[e];
-      } else {
-        t.l_reg += n < a.beta ? 0.5 * n * n / a.beta : n - 0.5 * a.beta;
-        t.d_reg[e] = (n < a.beta ? d / a.beta : (d > 0.0 ? 1.0 : (d < 0.0 ? -1.0 : 0.0))) * a.cw[e];
-      }
+      double v, slope;
+      smooth_l1(a.cw[e] * ((double)p[e] - tg[e]), a.beta, v, slope);
+      t.l_reg += v;
+      t.d_reg[e] = slope * a.cw[e];
     }
   }
   if (!a.corner) return;
   // decode against the RoI with zero centre, rotate by the RoI heading, add the centre (roi_head_template.py:169-184)
   const double dxa = r[3], dya = r[4], dza = r[5];
-  const double diag = sqrt(dxa * dxa + dya * dya);
-  const double x = (double)p[0] * diag, y = (double)p[1] * diag, z = (double)p[2] * dza;
-  const double dx = exp((double)p[3]) * dxa, dy = exp((double)p[4]) * dya, dz = exp((double)p[5]) * dza;
+  double q[6];
+  const double diag = residual_decode_local(p, dxa, dya, dza, q);  // (no zero centre added: a -0 offset stays -0)
+  const double x = q[0], y = q[1], z = q[2], dx = q[3], dy = q[4], dz = q[5];
   const double rg = (double)p[6] + (double)r[6];
   const double c0 = cos((double)r[6]), s0 = sin((double)r[6]);
   const double X = x * c0 - y * s0 + (double)r[0], Y = x * s0 + y * c0 + (double)r[1], Z = z + (double)r[2];
@@ -362,10 +349,7 @@ __global__ __launch_bounds__(256) void rcnn_loss_kernel(RcnnArgs a, double *__re
   t.l_cls = t.valid = t.l_reg = t.fg = t.l_corner = 0.0;
   if (i < a.N) row_terms(a, i, t);
   const double v[5] = {t.l_cls, t.valid, t.l_reg, t.fg, t.l_corner};
-  for (int j = 0; j < 5; ++j) {
-    const double sum = block_sum256(v[j], s_red);
-    if (threadIdx.x == 0) partials[(size_t)blockIdx.x * 5 + j] = sum;
-  }
+  partials_write<5>(v, partials, s_red);
 }
 
 // one workgroup: the partials in a fixed order -> the three scalars and the two normalisers
@@ -373,10 +357,8 @@ __global__ __launch_bounds__(256) void rcnn_loss_final_kernel(const double *__re
                                                               double w_reg, double w_corner, float *__restrict__ losses,
                                                               double *__restrict__ norms) {
   __shared__ double s_red[4];
-  double acc[5] = {0.0, 0.0, 0.0, 0.0, 0.0}, tot[5];
-  for (int k = threadIdx.x; k < nblocks; k += 256)
-    for (int j = 0; j < 5; ++j) acc[j] += partials[(size_t)k * 5 + j];
-  for (int j = 0; j < 5; ++j) tot[j] = block_sum256(acc[j], s_red);
+  double tot[5];
+  partials_sum<5>(partials, nblocks, tot, s_red);
   if (threadIdx.x == 0) {
     const double valid = tot[1], fg = tot[3];
     losses[0] = (float)(tot[0] / fmax(valid, 1.0) * w_cls);
@@ -427,15 +409,10 @@ struct TargetPlan {
 };
 
 static void target_plan(int batch, int R, TargetPlan &p) {
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    size_t o = align_up(off, 256);
-    off = o + bytes;
-    return o;
-  };
+  WsLayout l;
   const size_t n = (size_t)batch * R * 4;
-  p.iou = take(n), p.asg = take(n), p.fg = take(n), p.bg = take(n);
-  p.total = align_up(off, 256);
+  p.iou = l.take(n), p.asg = l.take(n), p.fg = l.take(n), p.bg = l.take(n);
+  p.total = l.total();
 }
 
 extern "C" size_t df3d_roi_targets_workspace_bytes(const df3d_roi_target_cfg *cfg) {
@@ -493,7 +470,7 @@ static int fill_rcnn_args(RcnnArgs &a, const char *what, const float *rcnn_cls, 
 
 extern "C" size_t df3d_rcnn_loss_workspace_bytes(const df3d_rcnn_loss_cfg *cfg) {
   if (!cfg || cfg->num_rows <= 0) return 0;
-  return align_up((size_t)cdiv(cfg->num_rows, 256) * 5 * sizeof(double), 256);
+  return partials_bytes(cdiv(cfg->num_rows, 256), 5);
 }
 
 extern "C" int df3d_rcnn_loss(const float *rcnn_cls, int ld_cls, const float *rcnn_reg, int ld_reg, const float *rois,
@@ -507,7 +484,7 @@ extern "C" int df3d_rcnn_loss(const float *rcnn_cls, int ld_cls, const float *rc
   if (rc) return rc;
   DF3D_CHECK_ARG(losses && norms && workspace, "rcnn_loss: null output");
   const int nblocks = cdiv(a.N, 256);
-  const size_t need = align_up((size_t)nblocks * 5 * sizeof(double), 256);
+  const size_t need = partials_bytes(nblocks, 5);
   DF3D_CHECK_ARG(workspace_bytes >= need, "rcnn_loss: workspace %zu < %zu bytes", workspace_bytes, need);
   double *partials = (double *)workspace;
   hipLaunchKernelGGL(rcnn_loss_kernel, dim3(nblocks), dim3(256), 0, stream, a, partials);

@@ -171,17 +171,12 @@ constexpr int TF_MAX_PROPOSALS = 4096;
 
 static int topk_plan(int batch, int C, int H, int W, TopkPlan &p) {
   const size_t n = (size_t)C * H * W;
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    size_t o = align_up(off, 256);
-    off = o + bytes;
-    return o;
-  };
-  p.keys = take((size_t)batch * n * 8);
-  p.top = take((size_t)batch * TF_MAX_PROPOSALS * 8);
+  WsLayout l;
+  p.keys = l.take((size_t)batch * n * 8);
+  p.top = l.take((size_t)batch * TF_MAX_PROPOSALS * 8);
   p.select_bytes = topk_keys_workspace(batch, (long long)n, TF_MAX_PROPOSALS);
-  p.select = take(p.select_bytes);
-  p.total = align_up(off, 256);
+  p.select = l.take(p.select_bytes);
+  p.total = l.total();
   return p.select_bytes ? DF3D_OK : DF3D_EINVAL;
 }
 

@@ -28,6 +28,7 @@
 
 #pragma clang fp contract(off)         // before the clipping code: bev_overlap.h relies on it
 #include "bev_overlap.h"
+#include "loss_terms.h"
 
 namespace df3d {
 
@@ -247,24 +248,17 @@ __global__ __launch_bounds__(256) void gfocal_kernel(const float *__restrict__ l
       grad[i] = (dpos + dneg) * dpdx;
     }
   }
-  const double tot = block_sum256(acc, s_red);
-  const double cnt = block_sum256(ones, s_red);
-  if (threadIdx.x == 0) {
-    partial[2 * (size_t)blockIdx.x] = tot;
-    partial[2 * (size_t)blockIdx.x + 1] = cnt;
-  }
+  const double v[2] = {acc, ones};
+  partials_write<2>(v, partial, s_red);
 }
 
 // out[0] = loss_weight * sum / max(#ones, 1), out[1] = #ones, out[2] = loss_weight / max(#ones, 1) (gradient scale)
 __global__ __launch_bounds__(256) void gfocal_finish_kernel(const double *__restrict__ partial, int chunks, float loss_weight,
                                                             float *__restrict__ out) {
   __shared__ double s_red[4];
-  double s = 0.0, c = 0.0;
-  for (int i = threadIdx.x; i < chunks; i += 256) {
-    s += partial[2 * (size_t)i];
-    c += partial[2 * (size_t)i + 1];
-  }
-  const double S = block_sum256(s, s_red), Cn = block_sum256(c, s_red);
+  double tot[2];
+  partials_sum<2>(partial, chunks, tot, s_red);
+  const double S = tot[0], Cn = tot[1];
   if (threadIdx.x == 0) {
     const double avg = Cn > 1.0 ? Cn : 1.0;
     out[0] = (float)((double)loss_weight * S / avg);

@@ -338,20 +338,15 @@ struct TopkWs {
 };
 
 static void topk_layout(int S, int K, TopkWs &w) {
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    size_t o = align_up(off, 256);
-    off = o + bytes;
-    return o;
-  };
-  w.hist1 = take((size_t)S * TK_BINS * 4);
-  w.hist2 = take((size_t)S * TK_BINS * 4);
-  w.cnt = take((size_t)S * 2 * 4);
-  w.thr = take((size_t)S * 4);
-  w.zero_bytes = off;                              // everything up to here is cleared per call
-  w.region0 = take((size_t)S * K * 8);
-  w.region1 = take((size_t)S * TK_TIE_CAP * 8);
-  w.total = align_up(off, 256);
+  WsLayout l;
+  w.hist1 = l.take((size_t)S * TK_BINS * 4);
+  w.hist2 = l.take((size_t)S * TK_BINS * 4);
+  w.cnt = l.take((size_t)S * 2 * 4);
+  w.thr = l.take((size_t)S * 4);
+  w.zero_bytes = l.off;                            // everything up to here (the raw end) is cleared per call
+  w.region0 = l.take((size_t)S * K * 8);
+  w.region1 = l.take((size_t)S * TK_TIE_CAP * 8);
+  w.total = l.total();
 }
 
 size_t topk_keys_workspace(int S, long long n, int K) {

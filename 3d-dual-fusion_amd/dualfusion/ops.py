@@ -48,6 +48,11 @@ def _chk(t, dtype, name):
     return t
 
 
+def _workspace(nbytes, device):
+    """the scratch buffer of a detection-tail or loss call (at least 8 bytes: the entries refuse a null pointer)"""
+    return torch.empty((max(int(nbytes), 8),), dtype=torch.uint8, device=device)
+
+
 # ------------------------------------------------------------------------- small host constants on the device
 _CONST_CACHE = {}
 
@@ -1141,7 +1146,7 @@ def nms_bev(boxes, thresh, mode=NMS_ROTATED, counts=None, max_keep=0):
     keep = torch.empty((S, cap), dtype=torch.int32, device=boxes.device)
     num = torch.zeros((S,), dtype=torch.int32, device=boxes.device)
     nbytes = lib.df3d_nms_bev_workspace_bytes(S, cap)
-    ws = torch.empty((max(int(nbytes), 8),), dtype=torch.uint8, device=boxes.device)
+    ws = _workspace(nbytes, boxes.device)
     lib.df3d_nms_bev(_ptr(boxes), _ptr(counts) if counts is not None else None, S, cap, float(thresh), int(mode),
                      int(max_keep), _ptr(keep), _ptr(num), _ptr(ws), int(nbytes), _stream())
     return (keep[0], num[0]) if single else (keep, num)
@@ -1241,21 +1246,27 @@ def _tail_rows(v, rows, cols, name):
     return v
 
 
+def _fill_anchor_cfg(c, what, batch, H, W, anchor_set, anchor_table, num_sets, num_classes=1, num_dir_bins=0, dir_offset=0.0):
+    """fill a df3d_anchor_cfg (a call's own, or the one embedded in an assignment / loss config); `what` names the refusal"""
+    A = len(anchor_set)
+    if A > MAX_ANCHORS:
+        raise NotImplementedError("%s: at most %d anchors per location (got %d)" % (what, MAX_ANCHORS, A))
+    c.batch, c.H, c.W = int(batch), int(H), int(W)
+    c.num_anchors, c.num_classes, c.num_dir_bins, c.num_sets = A, int(num_classes), int(num_dir_bins), int(num_sets)
+    for a in range(A):
+        c.anchor_set[a] = int(anchor_set[a])
+        for e in range(5):
+            c.anchor[a][e] = float(anchor_table[a][e])
+    c.dir_offset = float(dir_offset)
+    return c
+
+
 def anchor_cfg(batch, H, W, num_classes, num_dir_bins, anchor_set, anchor_table, num_sets, dir_offset, dir_limit_offset,
                nms_threshold, pre_max, post_max):
     """The df3d_anchor_cfg of a call: anchor_set [A] ints, anchor_table [A][5] = (centre z, dx, dy, dz, rotation)."""
-    A = len(anchor_set)
-    if A > MAX_ANCHORS:
-        raise NotImplementedError("anchor proposals: at most %d anchors per location (got %d)" % (MAX_ANCHORS, A))
-    cfg = _AnchorCfg()
-    cfg.batch, cfg.H, cfg.W = int(batch), int(H), int(W)
-    cfg.num_anchors, cfg.num_classes, cfg.num_dir_bins, cfg.num_sets = A, int(num_classes), int(num_dir_bins), int(num_sets)
-    for a in range(A):
-        cfg.anchor_set[a] = int(anchor_set[a])
-        for e in range(5):
-            cfg.anchor[a][e] = float(anchor_table[a][e])
-    cfg.dir_offset, cfg.dir_limit_offset = float(dir_offset), float(dir_limit_offset)
-    cfg.nms_threshold, cfg.pre_max, cfg.post_max = float(nms_threshold), int(pre_max), int(post_max)
+    cfg = _fill_anchor_cfg(_AnchorCfg(), "anchor proposals", batch, H, W, anchor_set, anchor_table, num_sets, num_classes, num_dir_bins, dir_offset)
+    cfg.dir_limit_offset, cfg.nms_threshold = float(dir_limit_offset), float(nms_threshold)
+    cfg.pre_max, cfg.post_max = int(pre_max), int(post_max)
     return cfg
 
 
@@ -1275,11 +1286,7 @@ def anchor_proposals(cls_rows, box_rows, dir_rows, x_shifts, y_shifts, batch, H,
             raise ValueError("dir_rows must be [B*H*W, A*NB]")
         nb = dir_rows.shape[1] // A
         _tail_rows(dir_rows, rows, A * nb, "dir_rows")
-    _chk(x_shifts, torch.float32, "x_shifts")
-    _chk(y_shifts, torch.float32, "y_shifts")
-    sets = int(x_shifts.shape[0])
-    if x_shifts.dim() != 2 or y_shifts.dim() != 2 or x_shifts.shape[1] != W or tuple(y_shifts.shape) != (sets, H):
-        raise ValueError("x_shifts must be [sets, W] and y_shifts [sets, H]")
+    sets = _shift_tables(x_shifts, y_shifts, H, W)
     cfg = anchor_cfg(batch, H, W, num_classes, nb, anchor_set, anchor_table, sets, dir_offset, dir_limit_offset, nms_threshold,
                      pre_max, post_max)
     dev = cls_rows.device
@@ -1288,7 +1295,7 @@ def anchor_proposals(cls_rows, box_rows, dir_rows, x_shifts, y_shifts, batch, H,
     labels = torch.empty((cfg.batch, cfg.post_max), dtype=torch.int64, device=dev)
     num = torch.empty((cfg.batch,), dtype=torch.int32, device=dev)
     nbytes = int(lib.df3d_anchor_proposals_workspace_bytes(ctypes.byref(cfg)))
-    ws = torch.empty((max(nbytes, 8),), dtype=torch.uint8, device=dev)
+    ws = _workspace(nbytes, dev)
     lib.df3d_anchor_proposals(_ptr(cls_rows), int(cls_rows.stride(0)), _ptr(box_rows), int(box_rows.stride(0)),
                               _ptr(dir_rows), int(dir_rows.stride(0)) if dir_rows is not None else 0, _ptr(x_shifts),
                               _ptr(y_shifts), ctypes.byref(cfg), _ptr(rois), _ptr(scores), _ptr(labels), _ptr(num),
@@ -1325,7 +1332,7 @@ def roi_decode_select(rois, rcnn_cls, rcnn_reg, roi_labels, score_threshold, nms
     labels = torch.empty((B, cfg.post_max), dtype=torch.int64, device=dev)
     counts = torch.empty((B,), dtype=torch.int32, device=dev)
     nbytes = int(lib.df3d_roi_decode_select_workspace_bytes(ctypes.byref(cfg)))
-    ws = torch.empty((max(nbytes, 8),), dtype=torch.uint8, device=dev)
+    ws = _workspace(nbytes, dev)
     lib.df3d_roi_decode_select(_ptr(rois), _ptr(rcnn_cls), int(rcnn_cls.stride(0)), _ptr(rcnn_reg), int(rcnn_reg.stride(0)),
                                _ptr(roi_labels), ctypes.byref(cfg), _ptr(box_preds), _ptr(boxes), _ptr(scores),
                                _ptr(labels), _ptr(counts), _ptr(ws), nbytes, _stream())
@@ -1348,28 +1355,13 @@ class _AnchorLossCfg(ctypes.Structure):
                 ("dir_weight", ctypes.c_float), ("code_weights", ctypes.c_float * 7), ("beta", ctypes.c_float)]
 
 
-def _anchor_tables_cfg(cfg, batch, H, W, anchor_set, anchor_table, num_sets, num_classes=1, num_dir_bins=0, dir_offset=0.0):
-    """fill the df3d_anchor_cfg embedded in an assignment / loss config"""
-    A = len(anchor_set)
-    if A > MAX_ANCHORS:
-        raise NotImplementedError("anchor targets: at most %d anchors per location (got %d)" % (MAX_ANCHORS, A))
-    c = cfg.anchors
-    c.batch, c.H, c.W = int(batch), int(H), int(W)
-    c.num_anchors, c.num_classes, c.num_dir_bins, c.num_sets = A, int(num_classes), int(num_dir_bins), int(num_sets)
-    for a in range(A):
-        c.anchor_set[a] = int(anchor_set[a])
-        for e in range(5):
-            c.anchor[a][e] = float(anchor_table[a][e])
-    c.dir_offset = float(dir_offset)
-    return cfg
-
-
 def anchor_assign_cfg(batch, H, W, max_gt, anchor_set, anchor_table, set_class, matched, unmatched):
     """The df3d_anchor_assign_cfg of a call: per anchor set its 1-based class id and its matched / unmatched thresholds."""
     sets = len(set_class)
     if sets > MAX_ANCHORS or len(matched) != sets or len(unmatched) != sets:
         raise ValueError("anchor_assign: one class id and one pair of thresholds per anchor set, at most %d sets" % MAX_ANCHORS)
-    cfg = _anchor_tables_cfg(_AnchorAssignCfg(), batch, H, W, anchor_set, anchor_table, sets)
+    cfg = _AnchorAssignCfg()
+    _fill_anchor_cfg(cfg.anchors, "anchor targets", batch, H, W, anchor_set, anchor_table, sets)
     cfg.max_gt = int(max_gt)
     for s in range(sets):
         cfg.set_class[s], cfg.matched_threshold[s], cfg.unmatched_threshold[s] = int(set_class[s]), float(matched[s]), float(unmatched[s])
@@ -1381,7 +1373,8 @@ def anchor_loss_cfg(batch, H, W, max_gt, num_classes, num_dir_bins, anchor_set, 
     """The df3d_anchor_loss_cfg of a call."""
     if len(code_weights) != 7:
         raise ValueError("anchor_loss: code_weights must have 7 entries (got %d)" % len(code_weights))
-    cfg = _anchor_tables_cfg(_AnchorLossCfg(), batch, H, W, anchor_set, anchor_table, num_sets, num_classes, num_dir_bins, dir_offset)
+    cfg = _AnchorLossCfg()
+    _fill_anchor_cfg(cfg.anchors, "anchor targets", batch, H, W, anchor_set, anchor_table, num_sets, num_classes, num_dir_bins, dir_offset)
     cfg.max_gt = int(max_gt)
     cfg.cls_weight, cfg.loc_weight, cfg.dir_weight, cfg.beta = float(cls_weight), float(loc_weight), float(dir_weight), float(beta)
     for e in range(7):
@@ -1425,7 +1418,7 @@ def anchor_assign(x_shifts, y_shifts, gt_boxes, H, W, anchor_set, anchor_table, 
     targets = torch.empty((B, n, 7), dtype=torch.float32, device=dev) if dense else None
     weights = torch.empty((B, n), dtype=torch.float32, device=dev) if dense else None
     nbytes = int(lib.df3d_anchor_assign_workspace_bytes(ctypes.byref(cfg)))
-    ws = torch.empty((max(nbytes, 8),), dtype=torch.uint8, device=dev)
+    ws = _workspace(nbytes, dev)
     lib.df3d_anchor_assign(_ptr(x_shifts), _ptr(y_shifts), _ptr(gt_boxes), ctypes.byref(cfg), _ptr(labels), _ptr(gt_ids),
                            _ptr(num_pos), _ptr(targets), _ptr(weights), _ptr(ws), nbytes, _stream())
     if dense:
@@ -1500,7 +1493,7 @@ class _AnchorLoss(torch.autograd.Function):
         args = _anchor_loss_args(spec, rows)
         losses = torch.empty((3,), dtype=torch.float32, device=rows.device)
         nbytes = int(lib.df3d_anchor_loss_workspace_bytes(ctypes.byref(spec.cfg)))
-        ws = torch.empty((max(nbytes, 8),), dtype=torch.uint8, device=rows.device)
+        ws = _workspace(nbytes, rows.device)
         lib.df3d_anchor_loss(*args, _ptr(losses), _ptr(ws), nbytes, _stream())
         ctx.save_for_backward(rows)
         ctx.spec = spec
@@ -1631,7 +1624,7 @@ def roi_targets(rois, roi_scores, roi_labels, gt_boxes, u_fg, u_slot, sampler_cf
            "gt_of_rois": f32(B, M, 8), "reg_valid_mask": torch.empty((B, M), dtype=torch.int32, device=dev),
            "rcnn_cls_labels": f32(B, M), "counts": torch.empty((B, 3), dtype=torch.int32, device=dev)}
     nbytes = int(lib.df3d_roi_targets_workspace_bytes(ctypes.byref(cfg)))
-    ws = torch.empty((max(nbytes, 8),), dtype=torch.uint8, device=dev)
+    ws = _workspace(nbytes, dev)
     lib.df3d_roi_targets(_ptr(rois), _ptr(roi_scores), _ptr(roi_labels), _ptr(gt_boxes), _ptr(u_fg), _ptr(u_slot), ctypes.byref(cfg),
                          _ptr(out["rois"]), _ptr(out["roi_labels"]), _ptr(out["roi_scores"]), _ptr(out["gt_iou_of_rois"]),
                          _ptr(out["roi_inds"]), _ptr(out["gt_of_rois_src"]), _ptr(out["gt_of_rois"]), _ptr(out["reg_valid_mask"]),
@@ -1691,7 +1684,7 @@ class _RcnnLoss(torch.autograd.Function):
         losses = torch.empty((3,), dtype=torch.float32, device=dev)
         norms = torch.empty((2,), dtype=torch.float64, device=dev)
         nbytes = int(lib.df3d_rcnn_loss_workspace_bytes(ctypes.byref(cfg)))
-        ws = torch.empty((max(nbytes, 8),), dtype=torch.uint8, device=dev)
+        ws = _workspace(nbytes, dev)
         lib.df3d_rcnn_loss(*args, _ptr(losses), _ptr(norms), _ptr(ws), nbytes, _stream())
         ctx.save_for_backward(rcnn_cls, rcnn_reg, norms)
         ctx.targets, ctx.loss_cfg = {k: targets[k] for k in RCNN_TARGET_KEYS}, cfg
@@ -2150,7 +2143,7 @@ def gaussian_focal_loss(logits, target, alpha=2.0, gamma=4.0, loss_weight=1.0, w
             or logits.stride(2) != W * logits.stride(3)):
         raise ValueError("logits must be a CUDA fp32 [B, C, H, W] view whose pixels are evenly strided")
     n = B * C * H * W
-    ws = torch.empty((max(int(lib.df3d_gaussian_focal_loss_workspace_bytes(n)), 8),), dtype=torch.uint8, device=target.device)
+    ws = _workspace(lib.df3d_gaussian_focal_loss_workspace_bytes(n), target.device)
     out = torch.empty((3,), dtype=torch.float32, device=target.device)
     grad = torch.empty((B, C, H, W), dtype=torch.float32, device=target.device) if want_grad else None
     lib.df3d_gaussian_focal_loss(_ptr(logits), logits.stride(0), logits.stride(1), logits.stride(3), _ptr(target), B, C,
