@@ -1,7 +1,7 @@
-"""`pointnet2_stack_cuda` (VR/pcdet/ops/pointnet2/pointnet2_stack/src/pointnet2_api.cpp:12-31): the three entry points the
-voxel RoI pooling uses, in the argument order of voxel_query.cpp:28-30 and group_points.cpp:31-54, outputs allocated by
-the caller.  The other entry points of that module (ball query, sampling, three_nn / interpolate, vector pool) are not
-provided."""
+"""`pointnet2_stack_cuda` (VR/pcdet/ops/pointnet2/pointnet2_stack/src/pointnet2_api.cpp:12-31): the entry points the voxel
+RoI pooling and the PV-RCNN point branch use -- voxel query, stack grouping with its gradient, and the stacked ball query --
+in the argument order of voxel_query.cpp:28-30, group_points.cpp:31-54 and ball_query.cpp, outputs allocated by the caller.
+The other entry points of that module (sampling, three_nn / interpolate, vector pool) are not provided."""
 import torch
 
 from .. import _lib
@@ -35,6 +35,23 @@ def voxel_query_wrapper(M, R1, R2, R3, nsample, radius, z_range, y_range, x_rang
     _lib.load().df3d_voxel_query_dense(
         _ptr(point_indices_tensor), point_indices_tensor.shape[0], shp_p, _ptr(xyz_tensor), xyz_tensor.shape[0],
         _ptr(new_xyz_tensor), _ptr(new_coords_tensor), int(M), rng_p, float(radius), int(nsample), _ptr(idx_tensor), _stream())
+    return 1
+
+
+@runtime_errors
+def ball_query_wrapper(B, M, radius, nsample, new_xyz_tensor, new_xyz_batch_cnt_tensor, xyz_tensor, xyz_batch_cnt_tensor,
+                       idx_tensor):
+    """ball_query.cpp:31-47.  idx int32 [M, nsample] (zeroed by the caller, as pointnet2_utils.py:33 does), local to the
+    frame: idx[m, 0] = -1 for an empty ball, whose other slots stay as they are."""
+    for t, nm in ((new_xyz_tensor, "new_xyz"), (new_xyz_batch_cnt_tensor, "new_xyz_batch_cnt"), (xyz_tensor, "xyz"),
+                  (xyz_batch_cnt_tensor, "xyz_batch_cnt"), (idx_tensor, "idx")):
+        need_cuda_contiguous(t, nm)
+    if tuple(new_xyz_tensor.shape) != (M, 3) or tuple(idx_tensor.shape) != (M, nsample) \
+            or tuple(xyz_batch_cnt_tensor.shape) != (B,) or tuple(new_xyz_batch_cnt_tensor.shape) != (B,):
+        raise RuntimeError("ball_query: new_xyz [M, 3], idx [M, nsample], counts [B]")
+    from .. import ops
+    ops.ball_query_stack(float(radius), int(nsample), xyz_tensor, xyz_batch_cnt_tensor, new_xyz_tensor,
+                         new_xyz_batch_cnt_tensor, out=idx_tensor)
     return 1
 
 

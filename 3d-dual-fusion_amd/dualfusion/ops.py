@@ -3811,3 +3811,142 @@ def voxel_pool_fused(rows_in, xyz, grid, new_xyz, new_coords, max_range, radius,
     if want_idx:
         return pooled, idx, empty.bool()
     return pooled
+
+
+# ------------------------------------------------------------------------- PV-RCNN point branch (csrc/stackpool.hip)
+BALL_QUERY_STACK_MAX_NSAMPLE = 64    # SP_MAX_NSAMPLE
+BALL_QUERY_STACK_MAX_BATCH = 255     # SP_MAX_BATCH
+
+
+def _ball_args(radius, nsample, xyz, xyz_batch_cnt, new_xyz, new_xyz_batch_cnt):
+    # the limits first: they are refused by name whatever the tensors are
+    if not 1 <= int(nsample) <= BALL_QUERY_STACK_MAX_NSAMPLE:
+        raise _lib.Df3dError("ball_query_stack: nsample %d is above the limit of %d" % (nsample, BALL_QUERY_STACK_MAX_NSAMPLE))
+    if xyz_batch_cnt.dim() != 1 or xyz_batch_cnt.shape != new_xyz_batch_cnt.shape or xyz_batch_cnt.shape[0] < 1:
+        raise _lib.Df3dError("xyz_batch_cnt and new_xyz_batch_cnt must both be [B]")
+    if xyz_batch_cnt.shape[0] > BALL_QUERY_STACK_MAX_BATCH:
+        raise _lib.Df3dError("ball_query_stack: B = %d is above the limit of %d frames"
+                             % (xyz_batch_cnt.shape[0], BALL_QUERY_STACK_MAX_BATCH))
+    _chk(xyz, torch.float32, "xyz")
+    _chk(new_xyz, torch.float32, "new_xyz")
+    _chk(xyz_batch_cnt, torch.int32, "xyz_batch_cnt")
+    _chk(new_xyz_batch_cnt, torch.int32, "new_xyz_batch_cnt")
+    if xyz.dim() != 2 or xyz.shape[1] != 3 or new_xyz.dim() != 2 or new_xyz.shape[1] != 3:
+        raise _lib.Df3dError("xyz must be [N, 3] and new_xyz [M, 3]")
+    if float(radius) < 0:
+        raise _lib.Df3dError("ball_query_stack: negative radius")
+
+
+def ball_query_stack(radius, nsample, xyz, xyz_batch_cnt, new_xyz, new_xyz_batch_cnt, out=None):
+    """ball_query_kernel_stack: xyz [N1 + N2 .., 3], new_xyz [M1 + M2 .., 3], counts int32 [B] on the device (never read
+    back) -> idx int32 [M, nsample] local to the frame, idx[m, 0] = -1 for an empty ball over the zeros of the allocation.
+    `out` (optional, [M, nsample]) is written in place, the slots an empty ball does not touch stay as they are."""
+    _ball_args(radius, nsample, xyz, xyz_batch_cnt, new_xyz, new_xyz_batch_cnt)
+    M = new_xyz.shape[0]
+    if out is None:
+        out = torch.zeros((M, int(nsample)), dtype=torch.int32, device=xyz.device)
+    else:
+        _chk(out, torch.int32, "idx")
+        if tuple(out.shape) != (M, int(nsample)):
+            raise _lib.Df3dError("idx must be [M, nsample]")
+    _lib.load().df3d_ball_query_stack(_ptr(xyz), _ptr(xyz_batch_cnt), xyz.shape[0], _ptr(new_xyz), _ptr(new_xyz_batch_cnt), M,
+                                      xyz_batch_cnt.shape[0], float(radius), int(nsample), _ptr(out), _stream())
+    return out
+
+
+def stack_sa_fused_supported(c1, c2, nsample, pool_method="max_pool"):
+    """Shapes `stack_sa_fused` serves (hidden and output channels of a 2-layer MLP, samples per ball); everything else takes
+    the composed path."""
+    return (int(c1) in (16, 32, 64) and int(c2) in (16, 32, 64) and int(nsample) in (16, 32) and pool_method == "max_pool")
+
+
+def stack_sa_fused(rows_in, xyz, xyz_batch_cnt, new_xyz, new_xyz_batch_cnt, radius, nsample, w_pos, w2, b2, want_idx=False):
+    """One scale of StackSAModuleMSG in eval mode (2-layer MLP, max pool) as one kernel: ball query, gather, first layer's
+    position term and ReLU, second layer on the matrix cores (fp32), ReLU, max over the ball.  rows_in [N, C1] = the features
+    through the first layer's feature columns (None: a source with no features); w_pos [C1, 4] = (xyz columns | shift),
+    w2 [C2, C1], b2 [C2], BatchNorms folded.  Returns pooled [M, C2], and with want_idx also (idx int32 [M, nsample] with the
+    rows of empty balls 0, empty bool [M])."""
+    if w_pos.dim() != 2 or w_pos.shape[1] != 4 or w2.dim() != 2 or w2.shape[1] != w_pos.shape[0] or tuple(b2.shape) != (w2.shape[0],):
+        raise _lib.Df3dError("w_pos must be [C1, 4], w2 [C2, C1] and b2 [C2]")
+    C1, C2 = w_pos.shape[0], w2.shape[0]
+    if not stack_sa_fused_supported(C1, C2, nsample):
+        raise _lib.Df3dError("stack_sa_fused does not serve C1 = %d, C2 = %d, nsample = %d (channels in 16/32/64, nsample 16 "
+                             "or 32): use the composed path" % (C1, C2, nsample))
+    _ball_args(radius, nsample, xyz, xyz_batch_cnt, new_xyz, new_xyz_batch_cnt)
+    _chk(w_pos, torch.float32, "w_pos")
+    _chk(w2, torch.float32, "w2")
+    _chk(b2, torch.float32, "b2")
+    if rows_in is not None:
+        _chk(rows_in, torch.float32, "rows_in")
+        if tuple(rows_in.shape) != (xyz.shape[0], C1):
+            raise _lib.Df3dError("rows_in must be [N, C1] with one row per row of xyz")
+    M, dev = new_xyz.shape[0], xyz.device
+    pooled = torch.empty((M, C2), dtype=torch.float32, device=dev)
+    idx = torch.empty((M, int(nsample)), dtype=torch.int32, device=dev) if want_idx else None
+    empty = torch.empty((M,), dtype=torch.uint8, device=dev) if want_idx else None
+    _lib.load().df3d_stack_sa_fused(_ptr(rows_in), _ptr(xyz), _ptr(xyz_batch_cnt), xyz.shape[0], _ptr(new_xyz),
+                                    _ptr(new_xyz_batch_cnt), M, xyz_batch_cnt.shape[0], float(radius), int(nsample), C1, C2,
+                                    _ptr(w_pos), _ptr(w2), _ptr(b2), _ptr(pooled), _ptr(idx), _ptr(empty), _stream())
+    if want_idx:
+        return pooled, idx, empty.bool()
+    return pooled
+
+
+def _bev_geom(keypoints, bev_shape, point_cloud_range, voxel_size, stride):
+    _chk(keypoints, torch.float32, "keypoints")
+    if keypoints.dim() != 2 or keypoints.shape[1] != 4 or len(bev_shape) != 4:
+        raise _lib.Df3dError("keypoints must be [M, 4] (b, x, y, z) and bev [B, C, H, W]")
+    return (float(point_cloud_range[0]), float(point_cloud_range[1]), float(voxel_size[0]), float(voxel_size[1]), float(stride))
+
+
+def _bev_interpolate(keypoints, bev, geom):
+    B, C, H, W = bev.shape
+    out = torch.empty((keypoints.shape[0], C), dtype=torch.float32, device=bev.device)
+    _lib.load().df3d_bev_interpolate(_ptr(keypoints), keypoints.shape[0], _ptr(bev), B, C, H, W, *geom, _ptr(out), _stream())
+    return out
+
+
+def bev_interpolate_backward(grad_out, keypoints, bev_shape, point_cloud_range, voxel_size, stride):
+    """grad_bev [B, C, H, W] of `bev_interpolate`: every pixel the sum of its contributions in ascending keypoint order (no
+    float atomics, the same bits on every run)."""
+    geom = _bev_geom(keypoints, bev_shape, point_cloud_range, voxel_size, stride)
+    grad_out = _chk(grad_out, torch.float32, "grad_out")
+    B, C, H, W = (int(v) for v in bev_shape)
+    M = keypoints.shape[0]
+    if tuple(grad_out.shape) != (M, C):
+        raise _lib.Df3dError("grad_out must be [M, C]")
+    lib, stream = _lib.load(), _stream()
+    grad_bev = torch.empty((B, C, H, W), dtype=torch.float32, device=grad_out.device)
+    ws, wsb = None, 0
+    if M > 0:
+        wsb = lib.df3d_bev_interpolate_grad_workspace_bytes(M, stream)
+        if wsb == 0:
+            raise _lib.Df3dError("bev_interpolate backward: no workspace size for 4 * M = %d (limit 2^31 - 1)" % (4 * M))
+        ws = torch.empty((wsb,), dtype=torch.uint8, device=grad_out.device)
+    lib.df3d_bev_interpolate_grad(_ptr(grad_out), _ptr(keypoints), M, B, C, H, W, *geom, _ptr(grad_bev), _ptr(ws), wsb, stream)
+    return grad_bev
+
+
+class _BevInterpolate(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, bev, keypoints, geom):
+        ctx.save_for_backward(keypoints)
+        ctx.geom, ctx.bev_shape = geom, tuple(bev.shape)
+        return _bev_interpolate(keypoints, bev, geom)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad):
+        keypoints, = ctx.saved_tensors
+        g = ctx.geom
+        return bev_interpolate_backward(grad.contiguous(), keypoints, ctx.bev_shape, g[0:2], g[2:4], g[4]), None, None
+
+
+def bev_interpolate(keypoints, bev, point_cloud_range, voxel_size, stride):
+    """bilinear_interpolate_torch of VoxelSetAbstraction.interpolate_from_bev_features for all frames in one launch:
+    keypoints [M, 4] (b, x, y, z), bev [B, C, H, W] read in place -> [M, C]; differentiable in `bev`."""
+    geom = _bev_geom(keypoints, bev.shape, point_cloud_range, voxel_size, stride)
+    _chk(bev, torch.float32, "bev")
+    if torch.is_grad_enabled() and bev.requires_grad:
+        return _BevInterpolate.apply(bev, keypoints, geom)
+    return _bev_interpolate(keypoints, bev, geom)

@@ -177,3 +177,162 @@ class NeighborVoxelSAModuleMSG(nn.Module):
                 new_features_list.append(self._composed(k, xyz, xyz_batch_cnt, new_xyz, new_xyz_batch_cnt, new_coords,
                                                         features, voxel2point_indices))
         return torch.cat(new_features_list, dim=1)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# The ball-query part (pointnet2_utils.py:8-155, pointnet2_modules.py:10-112) on csrc/stackpool.hip: the point side of
+# PV-RCNN (VoxelSetAbstraction in dualfusion/pfe.py, PVRCNNHead.roi_grid_pool).  `StackSAModuleMSG` runs one fused kernel per
+# scale in eval mode without autograd (ball query, gather, both MLP layers, max; nothing of size M * C * nsample is stored)
+# and the reference's formulation on the query and grouping ops otherwise (the composed path: it trains, and it serves
+# avg_pool, MLPs of another depth and channel counts the kernel does not); `DF3D_STACK_SA_FUSED=0` keeps the composed path
+# everywhere.  Not provided: `VectorPoolAggregationModuleMSG` (refused by name), stacked FPS, three_nn / interpolate.
+def ball_query_stack(radius, nsample, xyz, xyz_batch_cnt, new_xyz, new_xyz_batch_cnt):
+    """`BallQuery.apply` of the reference: idx int32 [M, nsample] local to the frame with the rows of empty balls set to 0,
+    and empty_ball_mask bool [M].  The counts stay on the device."""
+    with torch.no_grad():
+        idx = ops.ball_query_stack(radius, nsample, xyz, xyz_batch_cnt, new_xyz, new_xyz_batch_cnt)
+        empty_ball_mask = idx[:, 0] == -1
+        idx.masked_fill_(empty_ball_mask[:, None], 0)
+    return idx, empty_ball_mask
+
+
+ball_query = ball_query_stack
+
+
+class QueryAndGroup(nn.Module):
+    def __init__(self, radius: float, nsample: int, use_xyz: bool = True):
+        super().__init__()
+        self.radius, self.nsample, self.use_xyz = radius, nsample, use_xyz
+
+    def forward(self, xyz, xyz_batch_cnt, new_xyz, new_xyz_batch_cnt, features=None):
+        """Returns new_features [M, (3 +) C, nsample] (relative xyz first) and idx [M, nsample]; the entries of an empty ball
+        are zero.  The counts are not summed on the host (the reference's two asserts cost a device-to-host read each)."""
+        idx, empty_ball_mask = ball_query_stack(self.radius, self.nsample, xyz, xyz_batch_cnt, new_xyz, new_xyz_batch_cnt)
+        keep = (~empty_ball_mask)[:, None, None].to(xyz.dtype)
+        grouped_xyz = (grouping_operation(xyz, xyz_batch_cnt, idx, new_xyz_batch_cnt) - new_xyz.unsqueeze(-1)) * keep
+        if features is not None:
+            grouped_features = grouping_operation(features, xyz_batch_cnt, idx, new_xyz_batch_cnt) * keep
+            new_features = torch.cat([grouped_xyz, grouped_features], dim=1) if self.use_xyz else grouped_features
+        else:
+            assert self.use_xyz, "Cannot have not features and not use xyz as a feature!"
+            new_features = grouped_xyz
+        return new_features, idx
+
+
+def frame_counts(batch_idx, batch_size):
+    """int32 [B]: rows per frame, counted on the device without a read-back"""
+    ones = torch.ones(batch_idx.shape[0], dtype=torch.int32, device=batch_idx.device)
+    return torch.zeros(batch_size, dtype=torch.int32, device=batch_idx.device).index_add_(0, batch_idx.long(), ones)
+
+
+def stack_sa_fused_enabled():
+    return os.environ.get("DF3D_STACK_SA_FUSED", "1") != "0"
+
+
+class StackSAModuleMSG(nn.Module):
+    def __init__(self, *, radii: List[float], nsamples: List[int], mlps: List[List[int]], use_xyz: bool = True,
+                 pool_method="max_pool"):
+        super().__init__()
+        assert len(radii) == len(nsamples) == len(mlps)
+        self.groupers = nn.ModuleList()
+        self.mlps = nn.ModuleList()
+        for i in range(len(radii)):
+            self.groupers.append(QueryAndGroup(radii[i], nsamples[i], use_xyz=use_xyz))
+            mlp_spec = list(mlps[i])                         # (the reference adds the 3 to its caller's list)
+            if use_xyz:
+                mlp_spec[0] += 3
+            shared_mlps = []
+            for k in range(len(mlp_spec) - 1):
+                shared_mlps.extend([nn.Conv2d(mlp_spec[k], mlp_spec[k + 1], kernel_size=1, bias=False),
+                                    nn.BatchNorm2d(mlp_spec[k + 1]), nn.ReLU()])
+            self.mlps.append(nn.Sequential(*shared_mlps))
+        self.use_xyz = use_xyz
+        self.pool_method = pool_method
+        self.init_weights()
+
+    def init_weights(self):
+        for m in self.modules():
+            if isinstance(m, nn.Conv2d):
+                nn.init.kaiming_normal_(m.weight)
+                if m.bias is not None:
+                    nn.init.constant_(m.bias, 0)
+            if isinstance(m, nn.BatchNorm2d):
+                nn.init.constant_(m.weight, 1.0)
+                nn.init.constant_(m.bias, 0)
+
+    def takes_fused(self, k, xyz):
+        """The fused kernel serves scale k of this call (eval mode, no autograd, on the device, a served shape)."""
+        mlp = self.mlps[k]
+        if self.training or torch.is_grad_enabled() or not xyz.is_cuda or not stack_sa_fused_enabled() or len(mlp) != 6:
+            return False
+        return (self.use_xyz and mlp[1].running_var is not None and mlp[4].running_var is not None
+                and ops.stack_sa_fused_supported(mlp[0].out_channels, mlp[3].out_channels, self.groupers[k].nsample,
+                                                 self.pool_method))
+
+    def fused_operands(self, k, features):
+        """The operands of ops.stack_sa_fused for scale k, BatchNorms folded: rows_in [N, C1] = the features through the first
+        layer's feature columns (one GEMM over the N source rows instead of over M * nsample; None for a source without
+        features), w_pos [C1, 4] = (its xyz columns | shift), w2 [C2, C1], b2 [C2]."""
+        conv, bn = self.mlps[k][0], self.mlps[k][1]
+        scale, shift = _bn_fold(bn)
+        w1 = conv.weight[:, :, 0, 0] * scale[:, None]                                      # [C1, 3 + C_in]
+        w_pos = torch.cat([w1[:, :3], shift[:, None]], 1).contiguous()
+        rows_in = F.linear(features, w1[:, 3:]).contiguous() if features is not None and w1.shape[1] > 3 else None
+        conv, bn = self.mlps[k][3], self.mlps[k][4]
+        scale, shift = _bn_fold(bn)
+        return rows_in, w_pos, (conv.weight[:, :, 0, 0] * scale[:, None]).contiguous(), shift.contiguous()
+
+    def _fused(self, k, xyz, xyz_batch_cnt, new_xyz, new_xyz_batch_cnt, features):
+        g = self.groupers[k]
+        rows_in, w_pos, w2, b2 = self.fused_operands(k, features)
+        return ops.stack_sa_fused(rows_in, xyz, xyz_batch_cnt, new_xyz, new_xyz_batch_cnt, g.radius, g.nsample, w_pos, w2, b2)
+
+    def _composed(self, k, xyz, xyz_batch_cnt, new_xyz, new_xyz_batch_cnt, features):
+        grouped, _ = self.groupers[k](xyz, xyz_batch_cnt, new_xyz, new_xyz_batch_cnt, features)  # [M, C, nsample]
+        M, C, nsample = grouped.shape
+        # the 1 x 1 Conv2d + BatchNorm2d layers see every (m, s) entry as one row: linears over channels-last rows and the row
+        # BatchNorm kernels (ops.batch_norm_rows: batch statistics in train mode), no [1, C, M, nsample] round trips
+        rows = grouped.permute(0, 2, 1).reshape(M * nsample, C)
+        mlp = self.mlps[k]
+        for i in range(0, len(mlp), 3):
+            rows = ops.batch_norm_rows(mlp[i + 1], F.linear(rows, mlp[i].weight[:, :, 0, 0]), relu=True)
+        rows = rows.view(M, nsample, rows.shape[1])
+        if self.pool_method == "max_pool":
+            return rows.max(dim=1)[0]
+        if self.pool_method == "avg_pool":
+            return rows.mean(dim=1)
+        raise NotImplementedError
+
+    def forward(self, xyz, xyz_batch_cnt, new_xyz, new_xyz_batch_cnt, features=None, empty_voxel_set_zeros=True):
+        """xyz [N1 + N2 .., 3] with counts [B]; new_xyz [M1 + M2 .., 3] with counts [B]; features [N, C] or None.
+        Returns new_xyz and new_features [M, sum_k mlps[k][-1]]."""
+        xyz, new_xyz = xyz.contiguous(), new_xyz.contiguous()
+        xyz_batch_cnt, new_xyz_batch_cnt = xyz_batch_cnt.int().contiguous(), new_xyz_batch_cnt.int().contiguous()
+        features = features.contiguous() if features is not None else None
+        new_features_list = []
+        for k in range(len(self.groupers)):
+            if self.takes_fused(k, xyz):
+                new_features_list.append(self._fused(k, xyz, xyz_batch_cnt, new_xyz, new_xyz_batch_cnt, features))
+            else:
+                new_features_list.append(self._composed(k, xyz, xyz_batch_cnt, new_xyz, new_xyz_batch_cnt, features))
+        return new_xyz, torch.cat(new_features_list, dim=1)
+
+
+def _cfg_get(config, key, default=None):
+    if hasattr(config, "get"):
+        return config.get(key, default)
+    return getattr(config, key, default)
+
+
+def build_local_aggregation_module(input_channels, config):
+    """pointnet2_modules.py:10-27; `config` (a dict or an EasyDict) is not edited (the reference prepends to its MLPS)."""
+    name = _cfg_get(config, "NAME", "StackSAModuleMSG")
+    if name == "StackSAModuleMSG":
+        mlps = [[input_channels] + list(m) for m in _cfg_get(config, "MLPS")]
+        layer = StackSAModuleMSG(radii=list(_cfg_get(config, "POOL_RADIUS")), nsamples=list(_cfg_get(config, "NSAMPLE")),
+                                 mlps=mlps, use_xyz=True, pool_method="max_pool")
+        return layer, sum(m[-1] for m in mlps)
+    if name == "VectorPoolAggregationModuleMSG":
+        raise NotImplementedError("VectorPoolAggregationModuleMSG (the vector-pool aggregation of PV-RCNN++) is not provided: "
+                                  "StackSAModuleMSG is the aggregation of every shipped PV-RCNN + 3D-DF config")
+    raise NotImplementedError("local aggregation module %r" % (name,))

@@ -87,6 +87,7 @@ DENSE_HEADS = Registry("pcdet dense_head")     # pcdet.models.dense_heads.__all_
 BACKBONES_2D = Registry("pcdet backbone_2d")   # pcdet.models.backbones_2d.__all__ (BaseBEVBackbone)
 MAP_TO_BEV = Registry("pcdet map_to_bev")      # pcdet.models.backbones_2d.map_to_bev.__all__ (HeightCompression)
 DETECTORS_PCDET = Registry("pcdet detector")   # pcdet.models.detectors.__all__ (VoxelRCNN)
+PFE = Registry("pcdet pfe")                    # pcdet.models.backbones_3d.pfe.__all__ (VoxelSetAbstraction)
 
 
 def late_register():
@@ -94,7 +95,7 @@ def late_register():
     reference configs resolve `type=` / `NAME:` strings to the MI355X modules unchanged."""
     import importlib
     for m in ("spconv", "voxel", "backbones", "fusion", "fusion_tf", "necks", "heads", "transfusion_head", "transfusion",
-              "roi_heads", "dense_heads", "vr_detector"):
+              "roi_heads", "dense_heads", "vr_detector", "pfe"):
         importlib.import_module("." + m, __package__)          # every module that registers classes (some import lazily)
     done = []
     try:
@@ -149,7 +150,8 @@ def late_register():
     except Exception:
         pass
     for src, path in ((DENSE_HEADS, "pcdet.models.dense_heads"), (BACKBONES_2D, "pcdet.models.backbones_2d"),
-                      (MAP_TO_BEV, "pcdet.models.backbones_2d.map_to_bev"), (DETECTORS_PCDET, "pcdet.models.detectors")):
+                      (MAP_TO_BEV, "pcdet.models.backbones_2d.map_to_bev"), (DETECTORS_PCDET, "pcdet.models.detectors"),
+                      (PFE, "pcdet.models.backbones_3d.pfe")):
         try:
             dst = importlib.import_module(path)
             for k, v in src.module_dict.items():

@@ -18,7 +18,11 @@ with no host round trip (ops.anchor_proposals, csrc/proposals.hip, DESIGN sectio
 
 `roi_grid_pool` never builds the reference's dense voxel-to-point tensor (`generate_voxel2pinds`: B * Z * Y * X int32 per
 level and step): every source level is looked up through its occupancy directory, the one its sparse tensor already
-carries where a convolution built it."""
+carries where a convolution built it.
+
+`RoIHeadTemplate` holds what is not specific to that pooling -- the grid points, the proposal layer, the decoding, the
+proposal targets and the RCNN losses -- for VoxelRCNNHead and for PVRCNNHead (VR/pcdet/models/roi_heads/pvrcnn_head.py,
+DESIGN section 7.16), which pools the keypoints of VoxelSetAbstraction through one StackSAModuleMSG instead."""
 import os
 
 import numpy as np
@@ -28,7 +32,7 @@ import torch.nn.functional as F
 
 from . import iou3d_nms, ops
 from .dense_heads import residual_decode, tail_fused
-from .pointnet2_stack import NeighborVoxelSAModuleMSG
+from .pointnet2_stack import NeighborVoxelSAModuleMSG, build_local_aggregation_module, frame_counts
 from .registry import ROI_HEADS
 
 BOX_CODE_SIZE = 7          # ResidualCoder (VR/pcdet/utils/box_coder_utils.py): x, y, z, dx, dy, dz, heading
@@ -52,14 +56,14 @@ def rotate_points_along_z(points, angle):
     """VR/pcdet/utils/common_utils.py:rotate_points_along_z: points [B, N, 3 + C], angle [B]."""
     cosa, sina = torch.cos(angle), torch.sin(angle)
     zeros, ones = angle.new_zeros(points.shape[0]), angle.new_ones(points.shape[0])
-    rot = torch.stack((cosa, sina, zeros, -sina, cosa, zeros, zeros, zeros, ones), dim=1).view(-1, 3, 3).float()
+    rot = torch.stack((cosa, sina, zeros, -sina, cosa, zeros, zeros, zeros, ones), dim=1).view(-1, 3, 3).to(points.dtype)
     points_rot = torch.matmul(points[:, :, 0:3], rot)
     return torch.cat((points_rot, points[:, :, 3:]), dim=-1)
 
 
 def get_voxel_centers(voxel_coords, downsample_times, voxel_size, point_cloud_range):
     """VR/pcdet/utils/common_utils.py:get_voxel_centers: voxel_coords [N, 3] (z, y, x) -> centres [N, 3] (x, y, z)."""
-    centers = voxel_coords[:, [2, 1, 0]].float()
+    centers = voxel_coords[:, 0:3].flip(1).float()            # (a list index would be copied to the device on every call)
     size = ops.device_constant([float(v) for v in voxel_size], torch.float32, centers.device) * downsample_times
     low = ops.device_constant([float(v) for v in point_cloud_range[0:3]], torch.float32, centers.device)
     return (centers + 0.5) * size + low
@@ -320,8 +324,189 @@ class ProposalTargetLayer(nn.Module):
         return composed_roi_targets(rois, scores, labels, gt_boxes, u_fg, u_slot, self.roi_sampler_cfg)
 
 
+class RoIHeadTemplate(nn.Module):
+    """What the RoI heads of this tree share (VR/pcdet/models/roi_heads/roi_head_template.py): the grid points of a RoI, the
+    proposal layer, the decoding of the refinement outputs, the proposal targets and the RCNN losses.  A head supplies
+    `roi_grid_pool(batch_dict)` and `rcnn_outputs(batch_dict) -> (rcnn_cls [N, num_class], rcnn_reg [N, 7 * num_class])`."""
+
+    # ---- grid points
+    @staticmethod
+    def get_dense_grid_points(rois, batch_size_rcnn, grid_size):
+        faked_features = rois.new_ones((grid_size, grid_size, grid_size))
+        dense_idx = faked_features.nonzero()                                   # [g^3, 3] (x_idx, y_idx, z_idx)
+        dense_idx = dense_idx.repeat(batch_size_rcnn, 1, 1).float()
+        local_roi_size = rois.view(batch_size_rcnn, -1)[:, 3:6]
+        return (dense_idx + 0.5) / grid_size * local_roi_size.unsqueeze(dim=1) - (local_roi_size.unsqueeze(dim=1) / 2)
+
+    def get_global_grid_points_of_roi(self, rois, grid_size):
+        rois = rois.view(-1, rois.shape[-1])
+        batch_size_rcnn = rois.shape[0]
+        local_roi_grid_points = self.get_dense_grid_points(rois, batch_size_rcnn, grid_size)
+        global_roi_grid_points = rotate_points_along_z(local_roi_grid_points.clone(), rois[:, 6]).squeeze(dim=1)
+        global_roi_grid_points = global_roi_grid_points + rois[:, 0:3].clone().unsqueeze(dim=1)
+        return global_roi_grid_points, local_roi_grid_points
+
+    # ---- proposals and decoding
+    @staticmethod
+    def check_nms_config(nms_config, what):
+        """The limits of both modes, each refused by name (never a wrong result)."""
+        if _get(nms_config, "MULTI_CLASSES_NMS", False):
+            raise NotImplementedError("%s: MULTI_CLASSES_NMS is not supported" % what)
+        if _get(nms_config, "NMS_TYPE", "nms_gpu") != "nms_gpu":
+            raise NotImplementedError("%s: NMS_TYPE %s is not supported (nms_gpu only)" % (what, _get(nms_config, "NMS_TYPE")))
+        pre = int(_need(nms_config, "NMS_PRE_MAXSIZE"))
+        if pre > ops.TAIL_MAX_CANDIDATES:
+            raise NotImplementedError("%s: NMS_PRE_MAXSIZE = %d exceeds %d, the cap of the top-k select and the NMS "
+                                      "(the TRAIN value of the shipped configs is not supported)" % (what, pre, ops.TAIL_MAX_CANDIDATES))
+        return pre, int(_need(nms_config, "NMS_POST_MAXSIZE")), float(_need(nms_config, "NMS_THRESH"))
+
+    @torch.no_grad()
+    def proposal_layer(self, batch_dict, nms_config):
+        """roi_head_template.py:45-102: rois [B, POST, 7], roi_scores [B, POST] (raw logits), roi_labels [B, POST] (1-based;
+        unused slots hold zeros and label 1, as the reference leaves them)."""
+        if batch_dict.get("rois", None) is not None:
+            return batch_dict
+        pre, post, thresh = self.check_nms_config(nms_config, "%s.proposal_layer" % type(self).__name__)
+        batch_size = batch_dict["batch_size"]
+        if "dense_cls_rows" in batch_dict:                                    # AnchorHeadSingle, fused mode
+            meta = batch_dict["dense_anchor_tables"]
+            tables = meta["tables"]
+            x_shifts, y_shifts = tables.on(batch_dict["dense_cls_rows"].device)
+            rois, roi_scores, roi_labels, num = ops.anchor_proposals(
+                batch_dict["dense_cls_rows"], batch_dict["dense_box_rows"], batch_dict["dense_dir_rows"], x_shifts, y_shifts,
+                batch_size, meta["H"], meta["W"], meta["num_class"], tables.anchor_set, tables.table.tolist(), thresh, pre, post,
+                dir_offset=meta["dir_offset"], dir_limit_offset=meta["dir_limit_offset"])
+            batch_dict["roi_counts"] = num
+            has_class_labels = meta["num_class"] > 1
+        else:                                                                  # the reference's per-frame loop
+            if batch_dict.get("batch_index", None) is not None:
+                raise NotImplementedError("%s.proposal_layer: stacked predictions (batch_index) are not supported" % type(self).__name__)
+            batch_box_preds, batch_cls_preds = batch_dict["batch_box_preds"], batch_dict["batch_cls_preds"]
+            rois = batch_box_preds.new_zeros((batch_size, post, batch_box_preds.shape[-1]))
+            roi_scores = batch_box_preds.new_zeros((batch_size, post))
+            roi_labels = batch_box_preds.new_zeros((batch_size, post), dtype=torch.long)
+            for index in range(batch_size):
+                box_preds = batch_box_preds[index]
+                cur_roi_scores, cur_roi_labels = torch.max(batch_cls_preds[index], dim=1)
+                selected = class_agnostic_nms(cur_roi_scores, box_preds, pre, post, thresh)
+                rois[index, :len(selected), :] = box_preds[selected]
+                roi_scores[index, :len(selected)] = cur_roi_scores[selected]
+                roi_labels[index, :len(selected)] = cur_roi_labels[selected]
+            roi_labels = roi_labels + 1
+            has_class_labels = batch_cls_preds.shape[-1] > 1
+        batch_dict["rois"] = rois
+        batch_dict["roi_scores"] = roi_scores
+        batch_dict["roi_labels"] = roi_labels
+        batch_dict["has_class_labels"] = has_class_labels
+        return batch_dict
+
+    def generate_predicted_boxes(self, batch_size, rois, cls_preds, box_preds):
+        """roi_head_template.py:233-261 in torch: decode against the RoI with its centre zeroed, rotate about z by the RoI
+        heading, add the RoI centre."""
+        batch_cls_preds = cls_preds.view(batch_size, -1, cls_preds.shape[-1])
+        batch_box_preds = box_preds.view(batch_size, -1, BOX_CODE_SIZE)
+        roi_ry = rois[:, :, 6].reshape(-1)
+        roi_xyz = rois[:, :, 0:3].reshape(-1, 3)
+        local_rois = rois.clone().detach()
+        local_rois[:, :, 0:3] = 0
+        batch_box_preds = residual_decode(batch_box_preds, local_rois).view(-1, BOX_CODE_SIZE)
+        batch_box_preds = rotate_points_along_z(batch_box_preds.unsqueeze(dim=1), roi_ry).squeeze(dim=1)
+        batch_box_preds[:, 0:3] += roi_xyz
+        return batch_cls_preds, batch_box_preds.view(batch_size, -1, BOX_CODE_SIZE)
+
+    # ---- training (DESIGN section 7.14)
+    def _training_setup(self):
+        """the target layer and the loss configuration, made on first use; every limit is refused by name"""
+        if getattr(self, "loss_spec", None) is not None:
+            return
+        loss_cfg = _need(self.model_cfg, "LOSS_CONFIG")
+        if _get(loss_cfg, "CLS_LOSS", "BinaryCrossEntropy") != "BinaryCrossEntropy":
+            raise NotImplementedError("%s: CLS_LOSS %s is not supported (BinaryCrossEntropy only)" % (type(self).__name__, _get(loss_cfg, "CLS_LOSS")))
+        if _get(loss_cfg, "REG_LOSS", "smooth-l1") != "smooth-l1":
+            raise NotImplementedError("%s: REG_LOSS %s is not supported (smooth-l1 only)" % (type(self).__name__, _get(loss_cfg, "REG_LOSS")))
+        if self.num_class != 1:
+            raise NotImplementedError("%s: the RCNN losses need CLASS_AGNOSTIC (one logit and one box per RoI)" % type(self).__name__)
+        w = _need(loss_cfg, "LOSS_WEIGHTS")
+        spec = ops.RcnnLossSpec(_need(w, "rcnn_cls_weight"), _need(w, "rcnn_reg_weight"), _get(w, "rcnn_corner_weight", 0.0),
+                                list(_need(w, "code_weights")), corner_loss=bool(_get(loss_cfg, "CORNER_LOSS_REGULARIZATION", False)))
+        if getattr(self, "proposal_target_layer", None) is None:
+            self.proposal_target_layer = ProposalTargetLayer(_need(self.model_cfg, "TARGET_CONFIG"))
+        self.loss_spec = spec
+
+    def assign_targets(self, batch_dict, u_fg=None, u_slot=None):
+        """roi_head_template.py:104-134: batch_dict with rois, roi_scores, roi_labels, gt_boxes -> the targets dict
+        (ProposalTargetLayer.forward; the draws are made by the layer unless given)."""
+        self._training_setup()
+        return self.proposal_target_layer(batch_dict, u_fg=u_fg, u_slot=u_slot)
+
+    def forward_train(self, batch_dict, u_fg=None, u_slot=None):
+        """The reference's training-mode forward: RoIs as `forward` takes them (given, or made by proposal_layer from
+        NMS_CONFIG['TRAIN'] inside the candidate cap), sampled; batch_dict['rois'] / ['roi_labels'] replaced by the sampled
+        ones; pooling and the FC layers; `forward_ret_dict` keeps the targets with rcnn_cls and rcnn_reg for get_loss."""
+        self._training_setup()
+        if "rois" not in batch_dict:
+            nms_cfg = _get(self.model_cfg, "NMS_CONFIG")
+            if nms_cfg is None or ("dense_cls_rows" not in batch_dict and "batch_box_preds" not in batch_dict):
+                raise KeyError("%s.forward_train needs batch_dict['rois'] [B, num_rois, 7], or a dense head's outputs "
+                               "(AnchorHeadSingle) and the config's NMS_CONFIG to make them from" % type(self).__name__)
+            self.proposal_layer(batch_dict, _need(nms_cfg, "TRAIN"))
+        rois = batch_dict["rois"]
+        if rois.shape[-1] != BOX_CODE_SIZE:
+            raise NotImplementedError("%s.forward_train: box codes wider than 7 are not supported (rois %s)" % (type(self).__name__, tuple(rois.shape)))
+        if "gt_boxes" not in batch_dict:
+            raise KeyError("%s.forward_train needs batch_dict['gt_boxes'] [B, G, 8]" % type(self).__name__)
+        if batch_dict.get("roi_scores", None) is None:
+            batch_dict["roi_scores"] = rois.new_zeros(rois.shape[:2])
+        if batch_dict.get("roi_labels", None) is None:
+            batch_dict["roi_labels"] = torch.ones(rois.shape[:2], dtype=torch.long, device=rois.device)
+        targets_dict = self.assign_targets(batch_dict, u_fg=u_fg, u_slot=u_slot)
+        batch_dict["rois"] = targets_dict["rois"]
+        batch_dict["roi_labels"] = targets_dict["roi_labels"]
+        targets_dict["rcnn_cls"], targets_dict["rcnn_reg"] = self.rcnn_outputs(batch_dict)
+        batch_dict["rcnn_cls"], batch_dict["rcnn_reg"] = targets_dict["rcnn_cls"], targets_dict["rcnn_reg"]
+        self.forward_ret_dict = targets_dict
+        return batch_dict
+
+    def get_loss(self, tb_dict=None):
+        """roi_head_template.py:220-231 -> (rcnn_loss, tb_dict) with rcnn_loss_cls, rcnn_loss_reg, rcnn_loss_corner and
+        rcnn_loss; the tb_dict values are detached device tensors (nothing is read back)."""
+        self._training_setup()
+        tb_dict = {} if tb_dict is None else tb_dict
+        r = self.forward_ret_dict
+        if roi_loss_fused():
+            losses = ops.rcnn_loss(r["rcnn_cls"], r["rcnn_reg"], r, self.loss_spec)
+        else:
+            losses = composed_rcnn_losses(r["rcnn_cls"], r["rcnn_reg"], r, self.loss_spec)
+        rcnn_loss = losses[0] + losses[1] + losses[2]
+        tb_dict.update(rcnn_loss_cls=losses[0].detach(), rcnn_loss_reg=losses[1].detach(), rcnn_loss_corner=losses[2].detach(),
+                       rcnn_loss=rcnn_loss.detach())
+        return rcnn_loss, tb_dict
+
+    @torch.no_grad()
+    def predict(self, batch_dict):
+        """The eval outputs of the reference's forward: batch_cls_preds [B, N, 1 or C], batch_box_preds [B, N, 7],
+        cls_preds_normalized=False.  In the fused mode, with the detector's POST_PROCESSING config in `post_process_cfg`, the
+        decode AND the final selection are one call (ops.roi_decode_select); its results wait in batch_dict['final_selection']
+        for vr_detector.post_processing."""
+        rois, rcnn_cls, rcnn_reg = batch_dict["rois"], batch_dict["rcnn_cls"], batch_dict["rcnn_reg"]
+        if rois.shape[-1] != BOX_CODE_SIZE:
+            return batch_dict                                                   # RoIs with extra columns: pooled, not decoded
+        batch_size = batch_dict["batch_size"]
+        cfg = getattr(self, "post_process_cfg", None)
+        if tail_fused() and cfg is not None and rcnn_cls.is_cuda:
+            from .vr_detector import final_selection
+            batch_box_preds = final_selection(batch_dict, cfg)
+            batch_cls_preds = rcnn_cls.view(batch_size, -1, rcnn_cls.shape[-1])
+        else:
+            batch_cls_preds, batch_box_preds = self.generate_predicted_boxes(batch_size, rois, rcnn_cls, rcnn_reg)
+        batch_dict["batch_cls_preds"] = batch_cls_preds
+        batch_dict["batch_box_preds"] = batch_box_preds
+        batch_dict["cls_preds_normalized"] = False
+        return batch_dict
+
+
 @ROI_HEADS.register_module
-class VoxelRCNNHead(nn.Module):
+class VoxelRCNNHead(RoIHeadTemplate):
     def __init__(self, backbone_channels, model_cfg, point_cloud_range, voxel_size, num_class=1, **kwargs):
         super().__init__()
         self.model_cfg = model_cfg
@@ -364,23 +549,6 @@ class VoxelRCNNHead(nn.Module):
         nn.init.normal_(self.reg_pred_layer.weight, mean=0, std=0.001)
         nn.init.constant_(self.reg_pred_layer.bias, 0)
 
-    # ---- grid points
-    @staticmethod
-    def get_dense_grid_points(rois, batch_size_rcnn, grid_size):
-        faked_features = rois.new_ones((grid_size, grid_size, grid_size))
-        dense_idx = faked_features.nonzero()                                   # [g^3, 3] (x_idx, y_idx, z_idx)
-        dense_idx = dense_idx.repeat(batch_size_rcnn, 1, 1).float()
-        local_roi_size = rois.view(batch_size_rcnn, -1)[:, 3:6]
-        return (dense_idx + 0.5) / grid_size * local_roi_size.unsqueeze(dim=1) - (local_roi_size.unsqueeze(dim=1) / 2)
-
-    def get_global_grid_points_of_roi(self, rois, grid_size):
-        rois = rois.view(-1, rois.shape[-1])
-        batch_size_rcnn = rois.shape[0]
-        local_roi_grid_points = self.get_dense_grid_points(rois, batch_size_rcnn, grid_size)
-        global_roi_grid_points = rotate_points_along_z(local_roi_grid_points.clone(), rois[:, 6]).squeeze(dim=1)
-        global_roi_grid_points = global_roi_grid_points + rois[:, 0:3].clone().unsqueeze(dim=1)
-        return global_roi_grid_points, local_roi_grid_points
-
     # ---- pooling
     def roi_grid_pool(self, batch_dict):
         """rois [B, num_rois, 7 + C]; multi_scale_3d_features / _strides of the backbone -> [B * num_rois, g^3, C_out]."""
@@ -416,73 +584,11 @@ class VoxelRCNNHead(nn.Module):
             pooled_features_list.append(pooled_features.reshape(-1, g ** 3, pooled_features.shape[-1]))
         return torch.cat(pooled_features_list, dim=-1)
 
-    # ---- proposals and decoding
-    @staticmethod
-    def check_nms_config(nms_config, what):
-        """The limits of both modes, each refused by name (never a wrong result)."""
-        if _get(nms_config, "MULTI_CLASSES_NMS", False):
-            raise NotImplementedError("%s: MULTI_CLASSES_NMS is not supported" % what)
-        if _get(nms_config, "NMS_TYPE", "nms_gpu") != "nms_gpu":
-            raise NotImplementedError("%s: NMS_TYPE %s is not supported (nms_gpu only)" % (what, _get(nms_config, "NMS_TYPE")))
-        pre = int(_need(nms_config, "NMS_PRE_MAXSIZE"))
-        if pre > ops.TAIL_MAX_CANDIDATES:
-            raise NotImplementedError("%s: NMS_PRE_MAXSIZE = %d exceeds %d, the cap of the top-k select and the NMS "
-                                      "(the TRAIN value of the shipped configs is not supported)" % (what, pre, ops.TAIL_MAX_CANDIDATES))
-        return pre, int(_need(nms_config, "NMS_POST_MAXSIZE")), float(_need(nms_config, "NMS_THRESH"))
-
-    @torch.no_grad()
-    def proposal_layer(self, batch_dict, nms_config):
-        """roi_head_template.py:45-102: rois [B, POST, 7], roi_scores [B, POST] (raw logits), roi_labels [B, POST] (1-based;
-        unused slots hold zeros and label 1, as the reference leaves them)."""
-        if batch_dict.get("rois", None) is not None:
-            return batch_dict
-        pre, post, thresh = self.check_nms_config(nms_config, "VoxelRCNNHead.proposal_layer")
-        batch_size = batch_dict["batch_size"]
-        if "dense_cls_rows" in batch_dict:                                    # AnchorHeadSingle, fused mode
-            meta = batch_dict["dense_anchor_tables"]
-            tables = meta["tables"]
-            x_shifts, y_shifts = tables.on(batch_dict["dense_cls_rows"].device)
-            rois, roi_scores, roi_labels, num = ops.anchor_proposals(
-                batch_dict["dense_cls_rows"], batch_dict["dense_box_rows"], batch_dict["dense_dir_rows"], x_shifts, y_shifts,
-                batch_size, meta["H"], meta["W"], meta["num_class"], tables.anchor_set, tables.table.tolist(), thresh, pre, post,
-                dir_offset=meta["dir_offset"], dir_limit_offset=meta["dir_limit_offset"])
-            batch_dict["roi_counts"] = num
-            has_class_labels = meta["num_class"] > 1
-        else:                                                                  # the reference's per-frame loop
-            if batch_dict.get("batch_index", None) is not None:
-                raise NotImplementedError("VoxelRCNNHead.proposal_layer: stacked predictions (batch_index) are not supported")
-            batch_box_preds, batch_cls_preds = batch_dict["batch_box_preds"], batch_dict["batch_cls_preds"]
-            rois = batch_box_preds.new_zeros((batch_size, post, batch_box_preds.shape[-1]))
-            roi_scores = batch_box_preds.new_zeros((batch_size, post))
-            roi_labels = batch_box_preds.new_zeros((batch_size, post), dtype=torch.long)
-            for index in range(batch_size):
-                box_preds = batch_box_preds[index]
-                cur_roi_scores, cur_roi_labels = torch.max(batch_cls_preds[index], dim=1)
-                selected = class_agnostic_nms(cur_roi_scores, box_preds, pre, post, thresh)
-                rois[index, :len(selected), :] = box_preds[selected]
-                roi_scores[index, :len(selected)] = cur_roi_scores[selected]
-                roi_labels[index, :len(selected)] = cur_roi_labels[selected]
-            roi_labels = roi_labels + 1
-            has_class_labels = batch_cls_preds.shape[-1] > 1
-        batch_dict["rois"] = rois
-        batch_dict["roi_scores"] = roi_scores
-        batch_dict["roi_labels"] = roi_labels
-        batch_dict["has_class_labels"] = has_class_labels
-        return batch_dict
-
-    def generate_predicted_boxes(self, batch_size, rois, cls_preds, box_preds):
-        """roi_head_template.py:233-261 in torch: decode against the RoI with its centre zeroed, rotate about z by the RoI
-        heading, add the RoI centre."""
-        batch_cls_preds = cls_preds.view(batch_size, -1, cls_preds.shape[-1])
-        batch_box_preds = box_preds.view(batch_size, -1, BOX_CODE_SIZE)
-        roi_ry = rois[:, :, 6].reshape(-1)
-        roi_xyz = rois[:, :, 0:3].reshape(-1, 3)
-        local_rois = rois.clone().detach()
-        local_rois[:, :, 0:3] = 0
-        batch_box_preds = residual_decode(batch_box_preds, local_rois).view(-1, BOX_CODE_SIZE)
-        batch_box_preds = rotate_points_along_z(batch_box_preds.unsqueeze(dim=1), roi_ry).squeeze(dim=1)
-        batch_box_preds[:, 0:3] += roi_xyz
-        return batch_cls_preds, batch_box_preds.view(batch_size, -1, BOX_CODE_SIZE)
+    def rcnn_outputs(self, batch_dict):
+        pooled_features = self.roi_grid_pool(batch_dict)
+        pooled_features = pooled_features.reshape(pooled_features.size(0), -1)
+        shared_features = self.shared_fc_layer(pooled_features)
+        return self.cls_pred_layer(self.cls_fc_layers(shared_features)), self.reg_pred_layer(self.reg_fc_layers(shared_features))
 
     def forward(self, batch_dict):
         if "rois" not in batch_dict:
@@ -491,107 +597,106 @@ class VoxelRCNNHead(nn.Module):
                 raise KeyError("VoxelRCNNHead.forward needs batch_dict['rois'] [B, num_rois, 7 + C], or a dense head's outputs "
                                "(AnchorHeadSingle) and the config's NMS_CONFIG to make them from")
             self.proposal_layer(batch_dict, _need(nms_cfg, "TRAIN" if self.training else "TEST"))
-        pooled_features = self.roi_grid_pool(batch_dict)
-        pooled_features = pooled_features.reshape(pooled_features.size(0), -1)
-        shared_features = self.shared_fc_layer(pooled_features)
-        batch_dict["rcnn_cls"] = self.cls_pred_layer(self.cls_fc_layers(shared_features))
-        batch_dict["rcnn_reg"] = self.reg_pred_layer(self.reg_fc_layers(shared_features))
+        batch_dict["rcnn_cls"], batch_dict["rcnn_reg"] = self.rcnn_outputs(batch_dict)
         if not self.training:
             self.predict(batch_dict)
         return batch_dict
 
-    # ---- training
-    def _training_setup(self):
-        """the target layer and the loss configuration, made on first use; every limit is refused by name"""
-        if getattr(self, "loss_spec", None) is not None:
-            return
-        loss_cfg = _need(self.model_cfg, "LOSS_CONFIG")
-        if _get(loss_cfg, "CLS_LOSS", "BinaryCrossEntropy") != "BinaryCrossEntropy":
-            raise NotImplementedError("VoxelRCNNHead: CLS_LOSS %s is not supported (BinaryCrossEntropy only)" % _get(loss_cfg, "CLS_LOSS"))
-        if _get(loss_cfg, "REG_LOSS", "smooth-l1") != "smooth-l1":
-            raise NotImplementedError("VoxelRCNNHead: REG_LOSS %s is not supported (smooth-l1 only)" % _get(loss_cfg, "REG_LOSS"))
-        if self.num_class != 1:
-            raise NotImplementedError("VoxelRCNNHead: the RCNN losses need CLASS_AGNOSTIC (one logit and one box per RoI)")
-        w = _need(loss_cfg, "LOSS_WEIGHTS")
-        spec = ops.RcnnLossSpec(_need(w, "rcnn_cls_weight"), _need(w, "rcnn_reg_weight"), _get(w, "rcnn_corner_weight", 0.0),
-                                list(_need(w, "code_weights")), corner_loss=bool(_get(loss_cfg, "CORNER_LOSS_REGULARIZATION", False)))
-        if getattr(self, "proposal_target_layer", None) is None:
-            self.proposal_target_layer = ProposalTargetLayer(_need(self.model_cfg, "TARGET_CONFIG"))
-        self.loss_spec = spec
 
-    def assign_targets(self, batch_dict, u_fg=None, u_slot=None):
-        """roi_head_template.py:104-134: batch_dict with rois, roi_scores, roi_labels, gt_boxes -> the targets dict
-        (ProposalTargetLayer.forward; the draws are made by the layer unless given)."""
-        self._training_setup()
-        return self.proposal_target_layer(batch_dict, u_fg=u_fg, u_slot=u_slot)
+@ROI_HEADS.register_module
+class PVRCNNHead(RoIHeadTemplate):
+    """VR/pcdet/models/roi_heads/pvrcnn_head.py: the RoI head of the PV-RCNN + 3D-DF tree.  The grid points of every RoI pool
+    the keypoints of VoxelSetAbstraction (dualfusion/pfe.py) through one StackSAModuleMSG -- one fused kernel per scale in
+    eval mode (dualfusion/pointnet2_stack.py) -- and the reference's Conv1d layers refine them.  The proposal layer, the
+    decoding, `forward_train` and `get_loss` are RoIHeadTemplate's, shared with VoxelRCNNHead (and with its limits: the
+    9000-candidate TRAIN proposals stay refused).  `point_cls_scores` comes from the caller: PointHeadSimple and the PVRCNN
+    detector class are not provided."""
 
-    def forward_train(self, batch_dict, u_fg=None, u_slot=None):
-        """The reference's training-mode forward: RoIs as `forward` takes them (given, or made by proposal_layer from
-        NMS_CONFIG['TRAIN'] inside the candidate cap), sampled; batch_dict['rois'] / ['roi_labels'] replaced by the sampled
-        ones; pooling and the FC layers; `forward_ret_dict` keeps the targets with rcnn_cls and rcnn_reg for get_loss."""
-        self._training_setup()
+    def __init__(self, input_channels, model_cfg, num_class=1, **kwargs):
+        super().__init__()
+        self.model_cfg = model_cfg
+        self.num_class = 1 if _get(model_cfg, "CLASS_AGNOSTIC", True) else num_class
+        self.pool_cfg = _need(model_cfg, "ROI_GRID_POOL")
+        self.grid_size = int(_need(self.pool_cfg, "GRID_SIZE"))
+        self.roi_grid_pool_layer, num_c_out = build_local_aggregation_module(input_channels=input_channels, config=self.pool_cfg)
+
+        dp = float(_get(model_cfg, "DP_RATIO", 0))
+        pre_channel = self.grid_size ** 3 * num_c_out
+        shared_fc_list = []
+        widths = list(_need(model_cfg, "SHARED_FC"))
+        for k, width in enumerate(widths):
+            shared_fc_list.extend([nn.Conv1d(pre_channel, width, kernel_size=1, bias=False), nn.BatchNorm1d(width), nn.ReLU()])
+            pre_channel = width
+            if k != len(widths) - 1 and dp > 0:
+                shared_fc_list.append(nn.Dropout(dp))
+        self.shared_fc_layer = nn.Sequential(*shared_fc_list)
+        self.cls_layers = self.make_fc_layers(pre_channel, self.num_class, list(_need(model_cfg, "CLS_FC")), dp)
+        self.reg_layers = self.make_fc_layers(pre_channel, BOX_CODE_SIZE * self.num_class, list(_need(model_cfg, "REG_FC")), dp)
+        self.init_weights()
+
+    @staticmethod
+    def make_fc_layers(input_channels, output_channels, fc_list, dp_ratio):
+        """roi_head_template.py:29-43 (the dropout follows the first layer whenever DP_RATIO >= 0)"""
+        fc_layers = []
+        pre_channel = input_channels
+        for k, width in enumerate(fc_list):
+            fc_layers.extend([nn.Conv1d(pre_channel, width, kernel_size=1, bias=False), nn.BatchNorm1d(width), nn.ReLU()])
+            pre_channel = width
+            if dp_ratio >= 0 and k == 0:
+                fc_layers.append(nn.Dropout(dp_ratio))
+        fc_layers.append(nn.Conv1d(pre_channel, output_channels, kernel_size=1, bias=True))
+        return nn.Sequential(*fc_layers)
+
+    def init_weights(self):
+        """pvrcnn_head.py:44-62 with weight_init='xavier' (every Conv2d / Conv1d of the head, the pooling layer's included)"""
+        for m in self.modules():
+            if isinstance(m, (nn.Conv2d, nn.Conv1d)):
+                nn.init.xavier_normal_(m.weight)
+                if m.bias is not None:
+                    nn.init.constant_(m.bias, 0)
+        nn.init.normal_(self.reg_layers[-1].weight, mean=0, std=0.001)
+
+    def roi_grid_pool(self, batch_dict):
+        """rois [B, num_rois, 7 + C], point_coords [P, 4] (b, x, y, z) stacked frame after frame, point_features [P, C],
+        point_cls_scores [P] -> [B * num_rois, g^3, C_out]."""
+        if "point_cls_scores" not in batch_dict:
+            raise KeyError("PVRCNNHead.roi_grid_pool needs batch_dict['point_cls_scores'] [P] (the keypoint scores of the "
+                           "point head, which is not provided: the caller supplies them)")
+        batch_size = batch_dict["batch_size"]
+        rois = batch_dict["rois"]
+        point_coords = batch_dict["point_coords"]
+        point_features = batch_dict["point_features"] * batch_dict["point_cls_scores"].view(-1, 1)
+        g = self.grid_size
+        global_roi_grid_points, _ = self.get_global_grid_points_of_roi(rois, grid_size=g)
+        global_roi_grid_points = global_roi_grid_points.view(batch_size, -1, 3)
+        xyz = point_coords[:, 1:4]
+        xyz_batch_cnt = frame_counts(point_coords[:, 0], batch_size)
+        new_xyz = global_roi_grid_points.reshape(-1, 3)
+        new_xyz_batch_cnt = torch.full((batch_size,), global_roi_grid_points.shape[1], dtype=torch.int32, device=xyz.device)
+        _, pooled_features = self.roi_grid_pool_layer(xyz=xyz.contiguous(), xyz_batch_cnt=xyz_batch_cnt, new_xyz=new_xyz,
+                                                      new_xyz_batch_cnt=new_xyz_batch_cnt, features=point_features.contiguous())
+        return pooled_features.view(-1, g ** 3, pooled_features.shape[-1])
+
+    def rcnn_outputs(self, batch_dict):
+        pooled_features = self.roi_grid_pool(batch_dict)                       # [B * N, g^3, C]
+        batch_size_rcnn = pooled_features.shape[0]
+        pooled_features = pooled_features.permute(0, 2, 1).contiguous().view(batch_size_rcnn, -1, 1)
+        shared_features = self.shared_fc_layer(pooled_features)
+        rcnn_cls = self.cls_layers(shared_features).transpose(1, 2).contiguous().squeeze(dim=1)
+        rcnn_reg = self.reg_layers(shared_features).transpose(1, 2).contiguous().squeeze(dim=1)
+        return rcnn_cls, rcnn_reg
+
+    def forward(self, batch_dict):
+        if self.training:
+            return self.forward_train(batch_dict)
         if "rois" not in batch_dict:
             nms_cfg = _get(self.model_cfg, "NMS_CONFIG")
             if nms_cfg is None or ("dense_cls_rows" not in batch_dict and "batch_box_preds" not in batch_dict):
-                raise KeyError("VoxelRCNNHead.forward_train needs batch_dict['rois'] [B, num_rois, 7], or a dense head's outputs "
+                raise KeyError("PVRCNNHead.forward needs batch_dict['rois'] [B, num_rois, 7 + C], or a dense head's outputs "
                                "(AnchorHeadSingle) and the config's NMS_CONFIG to make them from")
-            self.proposal_layer(batch_dict, _need(nms_cfg, "TRAIN"))
-        rois = batch_dict["rois"]
-        if rois.shape[-1] != BOX_CODE_SIZE:
-            raise NotImplementedError("VoxelRCNNHead.forward_train: box codes wider than 7 are not supported (rois %s)" % (tuple(rois.shape),))
-        if "gt_boxes" not in batch_dict:
-            raise KeyError("VoxelRCNNHead.forward_train needs batch_dict['gt_boxes'] [B, G, 8]")
-        if batch_dict.get("roi_scores", None) is None:
-            batch_dict["roi_scores"] = rois.new_zeros(rois.shape[:2])
-        if batch_dict.get("roi_labels", None) is None:
-            batch_dict["roi_labels"] = torch.ones(rois.shape[:2], dtype=torch.long, device=rois.device)
-        targets_dict = self.assign_targets(batch_dict, u_fg=u_fg, u_slot=u_slot)
-        batch_dict["rois"] = targets_dict["rois"]
-        batch_dict["roi_labels"] = targets_dict["roi_labels"]
-        pooled_features = self.roi_grid_pool(batch_dict)
-        pooled_features = pooled_features.reshape(pooled_features.size(0), -1)
-        shared_features = self.shared_fc_layer(pooled_features)
-        targets_dict["rcnn_cls"] = self.cls_pred_layer(self.cls_fc_layers(shared_features))
-        targets_dict["rcnn_reg"] = self.reg_pred_layer(self.reg_fc_layers(shared_features))
-        batch_dict["rcnn_cls"], batch_dict["rcnn_reg"] = targets_dict["rcnn_cls"], targets_dict["rcnn_reg"]
-        self.forward_ret_dict = targets_dict
-        return batch_dict
-
-    def get_loss(self, tb_dict=None):
-        """roi_head_template.py:220-231 -> (rcnn_loss, tb_dict) with rcnn_loss_cls, rcnn_loss_reg, rcnn_loss_corner and
-        rcnn_loss; the tb_dict values are detached device tensors (nothing is read back)."""
-        self._training_setup()
-        tb_dict = {} if tb_dict is None else tb_dict
-        r = self.forward_ret_dict
-        if roi_loss_fused():
-            losses = ops.rcnn_loss(r["rcnn_cls"], r["rcnn_reg"], r, self.loss_spec)
-        else:
-            losses = composed_rcnn_losses(r["rcnn_cls"], r["rcnn_reg"], r, self.loss_spec)
-        rcnn_loss = losses[0] + losses[1] + losses[2]
-        tb_dict.update(rcnn_loss_cls=losses[0].detach(), rcnn_loss_reg=losses[1].detach(), rcnn_loss_corner=losses[2].detach(),
-                       rcnn_loss=rcnn_loss.detach())
-        return rcnn_loss, tb_dict
-
-    @torch.no_grad()
-    def predict(self, batch_dict):
-        """The eval outputs of the reference's forward: batch_cls_preds [B, N, 1 or C], batch_box_preds [B, N, 7],
-        cls_preds_normalized=False.  In the fused mode, with the detector's POST_PROCESSING config in `post_process_cfg`, the
-        decode AND the final selection are one call (ops.roi_decode_select); its results wait in batch_dict['final_selection']
-        for vr_detector.post_processing."""
-        rois, rcnn_cls, rcnn_reg = batch_dict["rois"], batch_dict["rcnn_cls"], batch_dict["rcnn_reg"]
-        if rois.shape[-1] != BOX_CODE_SIZE:
-            return batch_dict                                                   # RoIs with extra columns: pooled, not decoded
-        batch_size = batch_dict["batch_size"]
-        cfg = getattr(self, "post_process_cfg", None)
-        if tail_fused() and cfg is not None and rcnn_cls.is_cuda:
-            from .vr_detector import final_selection
-            batch_box_preds = final_selection(batch_dict, cfg)
-            batch_cls_preds = rcnn_cls.view(batch_size, -1, rcnn_cls.shape[-1])
-        else:
-            batch_cls_preds, batch_box_preds = self.generate_predicted_boxes(batch_size, rois, rcnn_cls, rcnn_reg)
-        batch_dict["batch_cls_preds"] = batch_cls_preds
-        batch_dict["batch_box_preds"] = batch_box_preds
-        batch_dict["cls_preds_normalized"] = False
+            self.proposal_layer(batch_dict, _need(nms_cfg, "TEST"))
+        batch_dict["rcnn_cls"], batch_dict["rcnn_reg"] = self.rcnn_outputs(batch_dict)
+        self.predict(batch_dict)
         return batch_dict
 
 

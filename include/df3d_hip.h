@@ -1425,6 +1425,44 @@ int df3d_voxel_pool_fused(const float *rows_in, const float *xyz, long long n_ro
                           void *stream);
 
 /* ------------------------------------------------------------------------------------
+ * PV-RCNN point branch (csrc/stackpool.hip): the stacked ball query, one scale of StackSAModuleMSG in
+ * eval mode, and the bilinear BEV sample of VoxelSetAbstraction.
+ *
+ * df3d_ball_query_stack = ball_query_kernel_stack (VR/pcdet/ops/pointnet2/pointnet2_stack/src/ball_query_gpu.cu:16-66).
+ * xyz [N, 3] and new_xyz [M, 3] are stacked frame after frame; the counts are DEVICE int32 [B] and are not read back.
+ * idx int32 [M, nsample], local to the frame: the centre's frame is scanned in ascending row order, a row is a hit when
+ * ((dx*dx) + (dy*dy)) + (dz*dz) < radius * radius in float32 (every operation rounded on its own); the first hit fills all
+ * slots, later hits overwrite slots 1, 2, ..; an empty ball writes idx[m, 0] = -1 and nothing else.  nsample <= 64, B <= 255.
+ *
+ * df3d_stack_sa_fused: pooled[m, :] = max_s relu(w2 . relu(rows_in[idx[m, s]] + w_pos[:, :3] . (xyz[idx[m, s]] - new_xyz[m])
+ * + w_pos[:, 3]) + b2) with the ball query of the same call.  rows_in [N, C1] (NULL = zero rows), w_pos [C1, 4], w2 [C2, C1],
+ * b2 [C2], pooled [M, C2]; an empty ball runs on zero features and zero offsets.  Optional idx [M, nsample] (the rows of empty
+ * balls are 0) and empty [M] (1 = empty ball).  The second layer runs on v_mfma_f32_16x16x4_f32 (fp32 products, fp32
+ * accumulation).  Served: C1, C2 in {16, 32, 64}, nsample in {16, 32} (df3d_stack_sa_fused_supported returns 1); anything
+ * else is refused.
+ *
+ * df3d_bev_interpolate = bilinear_interpolate_torch per keypoint (VR/pcdet/models/backbones_3d/pfe/voxel_set_abstraction.py:
+ * 11-42, 176-204): keypoints [M, 4] (b, x, y, z), bev [B, C, H, W] read in place, out [M, C]; x = (px - range_x) / voxel_x /
+ * stride in float32 in that order; floor(x) and floor(x) + 1 are clamped to the map and the weights are taken from the CLAMPED
+ * corners, as the reference's lines 27-40 do (outside the map the two corners coincide and their weights cancel); a keypoint whose b is none
+ * of 0 .. B-1 gives a zero row.  df3d_bev_interpolate_grad: grad_bev [B, C, H, W] is OVERWRITTEN; every pixel is the sum of
+ * its contributions in ascending keypoint order (no float atomics, the same bits on every run). */
+int df3d_ball_query_stack(const float *xyz, const int32_t *xyz_batch_cnt, long long N, const float *new_xyz,
+                          const int32_t *new_xyz_batch_cnt, long long M, int B, float radius, int nsample, int32_t *idx,
+                          void *stream);
+int df3d_stack_sa_fused_supported(int C1, int C2, int nsample);
+int df3d_stack_sa_fused(const float *rows_in, const float *xyz, const int32_t *xyz_batch_cnt, long long N,
+                        const float *new_xyz, const int32_t *new_xyz_batch_cnt, long long M, int B, float radius,
+                        int nsample, int C1, int C2, const float *w_pos, const float *w2, const float *b2, float *pooled,
+                        int32_t *idx, uint8_t *empty, void *stream);
+int df3d_bev_interpolate(const float *keypoints, long long M, const float *bev, int B, int C, int H, int W, float range_x,
+                         float range_y, float voxel_x, float voxel_y, float stride, float *out, void *stream);
+size_t df3d_bev_interpolate_grad_workspace_bytes(long long M, void *stream);
+int df3d_bev_interpolate_grad(const float *grad_out, const float *keypoints, long long M, int B, int C, int H, int W,
+                              float range_x, float range_y, float voxel_x, float voxel_y, float stride, float *grad_bev,
+                              void *workspace, size_t workspace_bytes, void *stream);
+
+/* ------------------------------------------------------------------------------------
  * Voxel-RCNN tail (csrc/proposals.hip): anchor head maps -> RoIs, and RoIs + RCNN outputs -> final boxes,
  * each one call for all frames with no device-to-host copy.
  *
