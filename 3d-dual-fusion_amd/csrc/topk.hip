@@ -7,17 +7,27 @@
 // [segment 8 | 0x3F800000 - score bits 32 | index 24], so "descending score, ties by ascending index" = ascending key.
 //
 // A full device sort of 194 k / 324 k keys per sample (rocPRIM: block sort + 9 merge passes, ~120 us) is replaced by a
-// two-level radix SELECT on the 24 leading bits of the 54 significant key bits, four launches over the keys (the all-ones
-// key means "masked" -- below the score threshold / outside the range: it is never a candidate, the output is padded
-// with it):
-//   topk_hist1     4096-bin histogram of bits [53:42] per segment (LDS-privatised)
-//   topk_hist2     every workgroup re-derives the level-1 threshold bin from hist1, histograms bits [41:30] inside it
+// two-level radix SELECT on 24 leading key bits, four launches over the keys (the all-ones key means "masked" -- below the
+// score threshold / outside the range: it is never a candidate, the output is padded with it):
+//   topk_hist1     4096-bin histogram of prefix bits [23:12] per segment (LDS-privatised)
+//   topk_hist2     every workgroup re-derives the level-1 threshold bin from hist1, histograms prefix bits [11:0] inside it
 //   topk_compact   re-derives both thresholds; keys whose 24-bit prefix is BELOW the threshold (fewer than K) go to
 //                  region 0, keys that TIE with it to region 1 (bounded; the total is still counted)
 //   topk_final     one workgroup per segment: bitonic sort of region 0 + region 1 in LDS, first K written out.  If more
 //                  keys tie on the 24-bit prefix than region 1 holds (near-constant, saturated or all-zero score maps:
 //                  thousands of equal scores, only the index decides), it continues the radix select by itself on
-//                  key bits [29:18], [17:6], [5:0] (one pass over the segment per level) -- exact for any input.
+//                  key bits [29:18], [17:6], [5:0] (one pass over the segment per level); more than a buffer of
+//                  IDENTICAL keys are streamed through the buffer.
+//
+// Key contract: bits 63:56 are equal within a segment, bits 55:0 are ordered, ANY value (the all-ones key excepted: it is
+// the mask).  The 24-bit prefix is the 26-bit value of key bits [55:30] clamped to 0xFFFFFF: the heads' keys have bits
+// 55:54 = 0 (0x3F800000 - score bits < 2^30), so for them the prefix is bits [53:30] and the first two levels resolve the
+// score to 6 bits above its last place.  Every key with bit 54 or 55 set (-1 - x for small x, read as an int64, among
+// them) shares the prefix 0xFFFFFF with the keys whose bits [53:30] are all ones.  The prefix is monotonic in the key, so
+// the select stays exact: region 1 is sorted by the whole key, and when the tie group of the CLAMP prefix overflows region
+// 1, topk_final first re-derives the group's exact 26-bit threshold (three more passes: key bits [55:54], [53:42], [41:30])
+// and then goes on as for any other prefix.  Tie-group membership is everywhere decided by tk_prefix24, the function the
+// histograms and the compaction use.
 #include <cstring>
 
 #include "common.h"
@@ -30,6 +40,7 @@ constexpr int TK_BINS = 4096;
 constexpr int TK_TIE_CAP = 4096;     // region 1 capacity per segment
 constexpr int TK_BUF = 8192;         // LDS sort buffer (keys)
 constexpr int TK_KEYS_PER_BLOCK = 256 * 16;
+constexpr long long TK_MAX_N = 0x7FFFFFFFll;   // keys per segment: histogram bins, region counts and fill counts are 32-bit
 
 __device__ __forceinline__ unsigned tk_prefix24(u64 key) {
   const u64 p = (key & 0x00FFFFFFFFFFFFFFull) >> 30;
@@ -229,26 +240,31 @@ __global__ __launch_bounds__(1024) void topk_final_kernel(const u64 *__restrict_
   } else {
     // more ties on the 24-bit prefix than region 1 holds (near-constant or saturated score maps, where thousands of
     // scores are equal and only the index decides): continue the radix select inside this workgroup on key bits
-    // [29:18], [17:6], [5:0] -- one histogram pass over the segment per level -- until the candidates fit the buffer
+    // [29:18], [17:6], [5:0] -- one histogram pass over the segment per level -- until the candidates fit the buffer.
+    // The tie group is the set of keys with tk_prefix24(key) == thr24, as in the compaction.  The clamp prefix 0xFFFFFF
+    // stands for every 26-bit value of bits [55:30] from 0xFFFFFF up, so its group is first ordered on those bits
+    // (levels -3, -2, -1: bits [55:54], [53:42], [41:30]); after them `chain` is the group's exact threshold on bits
+    // [55:30] and `below` counts its members under it, which is the state every other prefix starts level 0 in.
     const int R = K - A;                           // >= 1 keys are still needed from the tie group
     const unsigned thr24 = thr[s];
     const u64 *seg = keys + (size_t)s * n;
     unsigned *hist3 = (unsigned *)(buf + TK_BUF);  // TK_BINS counters behind the sort buffer
     const u64 low56 = 0x00FFFFFFFFFFFFFFull;
-    u64 chain = (u64)thr24 << 30;                  // threshold prefix found so far (bits [55:sh_prev])
-    int sh_prev = 30;
+    const bool clamp = thr24 == 0xFFFFFFu;
+    u64 chain = clamp ? 0ull : (u64)thr24 << 30;   // threshold prefix found so far (bits [55:sh_prev])
+    int sh_prev = clamp ? 56 : 30;
     unsigned below = 0;                            // tie-group keys already known to be selected
     bool fits = false;
     int sh = 18;
-    for (int level = 0; level < 3 && !fits; ++level) {
-      sh = level == 0 ? 18 : (level == 1 ? 6 : 0);
+    for (int level = clamp ? -3 : 0; level < 3 && !fits; ++level) {
+      sh = max(18 - 12 * level, 0);                // 54, 42, 30 | 18, 6, 0
       const unsigned nbits = sh_prev - sh, bmask = (1u << nbits) - 1u;
       for (int e = t; e < TK_BINS; e += 1024) hist3[e] = 0;
       __syncthreads();
       for (long long i0 = 0; i0 < n; i0 += 1024) {  // whole waves enter: the ballots below need every lane
         const long long i = i0 + t;
         const u64 key = i < n ? seg[i] : ~0ull;
-        const bool in = key != ~0ull && ((key & low56) >> sh_prev) == (chain >> sh_prev);
+        const bool in = key != ~0ull && tk_prefix24(key) == thr24 && ((key & low56) >> sh_prev) == (chain >> sh_prev);
         const unsigned bin = (unsigned)(key >> sh) & bmask;
         const u64 m = __ballot(in);
         if (m == 0) continue;
@@ -268,18 +284,18 @@ __global__ __launch_bounds__(1024) void topk_final_kernel(const u64 *__restrict_
       chain |= (u64)T3 << sh;
       below += A3;
       sh_prev = sh;
-      fits = (unsigned)A + below + P3 <= (unsigned)TK_BUF;
+      fits = level >= 0 && (unsigned)A + below + P3 <= (unsigned)TK_BUF;
     }
     if (fits) {
       if (t == 0) s_cnt = A;
       for (int e = t; e < A; e += 1024) buf[e] = region0[(size_t)s * K + e];
       __syncthreads();
-      const u64 lo = ((u64)thr24 << 30) >> sh, hi = chain >> sh;
+      const u64 hi = chain >> sh;                  // the tie group's keys up to the threshold bin: below + P3 of them
       for (long long i0 = 0; i0 < n; i0 += 1024) {
         const long long i = i0 + t;
         const u64 key = i < n ? seg[i] : ~0ull;
         const u64 v = (key & low56) >> sh;
-        const bool in = key != ~0ull && v >= lo && v <= hi && tk_prefix24(key) == thr24;
+        const bool in = key != ~0ull && v <= hi && tk_prefix24(key) == thr24;
         const u64 m = __ballot(in);
         if (m == 0) continue;
         const int lane = threadIdx.x & 63, leader = __ffsll((long long)m) - 1;
@@ -299,7 +315,11 @@ __global__ __launch_bounds__(1024) void topk_final_kernel(const u64 *__restrict_
       if (t == 0) s_cnt = R;
       __syncthreads();
       for (long long base = 0; base < n; base += 1024) {
-        if (s_cnt + 1024 > TK_BUF) {               // uniform: s_cnt is read after a barrier
+        // every thread takes its copy of the fill count between two barriers: a wave that read s_cnt after another wave's
+        // append below would take the other side of the branch and leave the workgroup's barriers skewed
+        const int fill = s_cnt;
+        __syncthreads();
+        if (fill + 1024 > TK_BUF) {
           tk_bitonic(buf, TK_BUF);
           for (int e = R + t; e < TK_BUF; e += 1024) buf[e] = ~0ull;
           if (t == 0) s_cnt = R;
@@ -350,7 +370,7 @@ static void topk_layout(int S, int K, TopkWs &w) {
 }
 
 size_t topk_keys_workspace(int S, long long n, int K) {
-  if (S <= 0 || n <= 0 || K <= 0 || K > TK_TIE_CAP) return 0;
+  if (S <= 0 || n <= 0 || n > TK_MAX_N || K <= 0 || K > TK_TIE_CAP) return 0;
   TopkWs w;
   topk_layout(S, K, w);
   return w.total;
@@ -361,6 +381,7 @@ int topk_keys(const u64 *keys, int S, long long n, int K, u64 *out, int32_t *out
   DF3D_CHECK_ARG(keys && out && ws_, "topk_keys: null argument");
   DF3D_CHECK_ARG(S > 0 && S <= 65535 && n > 0 && K > 0 && K <= TK_TIE_CAP, "topk_keys: need 1..65535 segments, n > 0, 0 < K <= %d",
                  TK_TIE_CAP);
+  DF3D_CHECK_ARG(n <= TK_MAX_N, "topk_keys: n = %lld keys per segment, the 32-bit counters hold at most %lld", n, TK_MAX_N);
   TopkWs w;
   topk_layout(S, K, w);
   DF3D_CHECK_ARG(ws_bytes >= w.total, "topk_keys: workspace %zu < %zu bytes", ws_bytes, w.total);

@@ -2515,7 +2515,7 @@ def topk_keys(keys, k):
     cnt = torch.empty((S,), dtype=torch.int32, device=keys.device)
     nbytes = lib.df3d_topk_keys_workspace_bytes(S, n, int(k))
     if nbytes == 0:
-        raise _lib.Df3dError("df3d_topk_keys: unsupported sizes (1 <= k <= 4096)")
+        raise _lib.Df3dError("df3d_topk_keys: unsupported sizes (1 <= k <= 4096, 1 <= n < 2^31)")
     ws = torch.empty((int(nbytes),), dtype=torch.uint8, device=keys.device)
     lib.df3d_topk_keys(_ptr(keys), S, n, int(k), _ptr(out), _ptr(cnt), _ptr(ws), int(nbytes), _stream())
     return out, cnt

@@ -568,10 +568,15 @@ int df3d_dynamic_voxelize(const float *points, long long num_points, int num_fea
  * ties by ascending index).  Replaces the full sorts of the reference -- the per-(task, sample) score sort before
  * rotate_nms_pcdet (CP/det3d/models/bbox_heads/center_head.py:470-478, box_torch_ops.py:248-279) and the argsort of
  * all C*H*W scores (TF/mmdet3d/models/dense_heads/transfusion_head.py:866) -- by a two-level radix select
- * (histogram, histogram, compaction, one-workgroup sort); exact for any input.
+ * (histogram, histogram, compaction, one-workgroup sort).
  *   keys [segments, n] u64 (bits 63:56 equal within a segment; the all-ones key is "masked"), out [segments, k] u64
- *   (padded with all-ones keys when n < k), out_count [segments] i32 or NULL = keys of out below the all-ones key.
- *   1 <= k <= 4096.
+ *   (padded with all-ones keys when fewer than k keys are unmasked), out_count [segments] i32 or NULL = keys of out
+ *   below the all-ones key.  1 <= segments <= 65535, 1 <= n < 2^31, 1 <= k <= 4096; other sizes are refused
+ *   (DF3D_EINVAL, workspace size 0).
+ * Exact -- the first k keys of a full sort of each segment -- for any values of bits 55:0, duplicates included.  The
+ * two histogram levels order the 26-bit value of bits 55:30 clamped to 2^24 - 1; keys with bit 54 or 55 set all
+ * share the clamp bin, so they are selected exactly but cost more when more than 4096 of them tie for the last
+ * places: the final kernel then makes up to six passes over the segment instead of up to three.  The detection tails keep bits 55:54 zero.  The keys are not modified.
  */
 size_t df3d_topk_keys_workspace_bytes(int segments, long long n, int k);
 int df3d_topk_keys(const unsigned long long *keys, int segments, long long n, int k, unsigned long long *out,
