@@ -241,18 +241,6 @@ __device__ __forceinline__ void load_site(const LossArgs &a, long long i, Site &
   }
 }
 
-// sigmoid focal loss (alpha 0.25, gamma 2) of one logit against target tt in {0, 1}: value and derivative
-__device__ __forceinline__ void focal(double x, double tt, double &value, double &dx) {
-  const double p = 1.0 / (1.0 + exp(-x));
-  const double alpha_w = tt * 0.25 + (1.0 - tt) * 0.75;
-  const double pt = tt * (1.0 - p) + (1.0 - tt) * p;
-  double bce, dbce;
-  bce_with_logits(x, tt, bce, dbce);
-  value = alpha_w * pt * pt * bce;
-  const double dpt = (1.0 - 2.0 * tt) * p * (1.0 - p);
-  dx = alpha_w * (2.0 * pt * dpt * bce + pt * pt * dbce);
-}
-
 // code-weighted difference of code e (add_sin_difference on code 6) and its derivative with respect to the prediction
 __device__ __forceinline__ void code_diff(const LossArgs &a, const float *p, const Site &s, int e, double &d, double &dd) {
   if (e == 6) {

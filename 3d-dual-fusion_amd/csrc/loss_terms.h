@@ -1,5 +1,5 @@
-// Loss terms and the ordered reduction of the fused loss kernels: anchorloss.hip, roiloss.hip, and the
-// reduction in tfloss.hip.  A term is the fp64 value and derivative of one element (the compiler drops what a caller does not
+// Loss terms and the ordered reduction of the fused loss kernels: anchorloss.hip, roiloss.hip, pointhead.hip, and
+// the reduction in tfloss.hip.  A term is the fp64 value and derivative of one element (the compiler drops what a caller does not
 // use); the includer sets `#pragma clang fp contract(off)` in front of the include, as for bev_overlap.h.
 // Reduction: every workgroup of 256 threads writes its J fp64 sums at partials[block * J + j]; ONE workgroup then adds them,
 // thread t taking blocks t, t + 256, ... in turn, and block_sum256 adds the 256 accumulators of each j: a fixed order.
@@ -24,6 +24,18 @@ __device__ __forceinline__ void smooth_l1(double d, double beta, double &value, 
 __device__ __forceinline__ void bce_with_logits(double x, double target, double &value, double &slope) {
   value = fmax(x, 0.0) - x * target + log1p(exp(-fabs(x)));
   slope = 1.0 / (1.0 + exp(-x)) - target;
+}
+
+// sigmoid focal loss (alpha 0.25, gamma 2) of one logit against target tt in {0, 1}: value and derivative
+__device__ __forceinline__ void focal(double x, double tt, double &value, double &dx) {
+  const double p = 1.0 / (1.0 + exp(-x));
+  const double alpha_w = tt * 0.25 + (1.0 - tt) * 0.75;
+  const double pt = tt * (1.0 - p) + (1.0 - tt) * p;
+  double bce, dbce;
+  bce_with_logits(x, tt, bce, dbce);
+  value = alpha_w * pt * pt * bce;
+  const double dpt = (1.0 - 2.0 * tt) * p * (1.0 - p);
+  dx = alpha_w * (2.0 * pt * dpt * bce + pt * pt * dbce);
 }
 
 // max and sum of exp(q - max) of n logits: log-softmax of k is q[k] - (mx + log(sum)), softmax exp(q[k] - mx) / sum

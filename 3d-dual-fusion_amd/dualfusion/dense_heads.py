@@ -16,7 +16,10 @@ loss, smooth-L1 regression, direction cross entropy), chosen per call by DF3D_AN
             from the tables, the regression target encoded only at the positives, no device-to-host read;
   composed  the reference's formulation in torch under autograd: per-frame dense IoU matrices, one-hot targets and three
             dense loss maps.
-TRAIN-mode proposals are not here: forward_train returns no RoIs (the RoI head's targets and losses are in roi_heads.py)."""
+TRAIN-mode proposals are not made here: forward_train returns no RoIs (the RoI head's targets and losses are in roi_heads.py);
+`write_train_predictions` hands a RoI head the detached predictions of that pass, as the PVRCNN detector does.
+
+PointHeadSimple, the keypoint segmentation head of the PV-RCNN tree, is at the end of this file."""
 import os
 
 import numpy as np
@@ -507,6 +510,11 @@ class AnchorHeadSingle(nn.Module):
         if (H, W) != (self.tables.H, self.tables.W):
             raise ValueError("AnchorHeadSingle: the map is %d x %d, the anchors were built for %d x %d" % (H, W, self.tables.H, self.tables.W))
         cls_rows, box_rows, dir_rows = self.head_rows(x)
+        return self.write_predictions(data_dict, cls_rows, box_rows, dir_rows, B, H, W)
+
+    def write_predictions(self, data_dict, cls_rows, box_rows, dir_rows, B, H, W):
+        """What `forward` leaves for the RoI head, from the three column views of the head's row buffer: the rows and the
+        anchor tables (fused mode) or every anchor decoded (composed mode)."""
         if tail_fused():
             data_dict["dense_cls_rows"], data_dict["dense_box_rows"], data_dict["dense_dir_rows"] = cls_rows, box_rows, dir_rows
             data_dict["dense_anchor_tables"] = {
@@ -520,6 +528,186 @@ class AnchorHeadSingle(nn.Module):
         data_dict["batch_box_preds"] = batch_box_preds
         data_dict["cls_preds_normalized"] = False
         return data_dict
+
+    def write_train_predictions(self, data_dict):
+        """After `forward_train`: the first stage's predictions of that pass, DETACHED, under the keys `forward` writes, so
+        that a RoI head can make its TRAIN proposals from them (the reference's predict_boxes_when_training; its
+        generate_predicted_boxes runs on detached maps too: the RoIs carry no gradient into this head)."""
+        r = self.forward_ret_dict
+        if not r or "rows" not in r:
+            raise KeyError("AnchorHeadSingle.write_train_predictions follows forward_train")
+        rows = r["rows"].detach()
+        B, H, W = r["cls_preds"].shape[:3]
+        n_cls, n_box = self.conv_cls.out_channels, self.conv_box.out_channels
+        dir_rows = rows[:, n_cls + n_box:] if self.conv_dir_cls is not None else None
+        with torch.no_grad():
+            return self.write_predictions(data_dict, rows[:, :n_cls], rows[:, n_cls:n_cls + n_box], dir_rows, int(B), int(H), int(W))
+
+
+def point_head_fused():
+    """DF3D_POINT_HEAD_FUSED, read per call (default: fused)"""
+    return os.environ.get("DF3D_POINT_HEAD_FUSED", "1") != "0"
+
+
+def composed_point_targets(points, gt_boxes, extra_width, num_class):
+    """assign_stack_targets (point_head_template.py:49-129, ignore flag, no box or part labels) with points_in_boxes_gpu in
+    torch, vectorised over [P, G] with no per-frame loop: float32 rotation, double comparisons, first box wins.
+    -> labels [P] int64, box_idx [P] int64 (-1: in no box)."""
+    P, (B, G) = points.shape[0], gt_boxes.shape[:2]
+    labels = torch.zeros((P,), dtype=torch.int64, device=points.device)
+    if G == 0 or P == 0 or B == 0:
+        return labels, torch.full((P,), -1, dtype=torch.int64, device=points.device)
+    points, gt_boxes = points.float(), gt_boxes.float()
+    bf = points[:, 0]
+    frame = torch.clamp(bf, 0, B - 1).long()
+    valid = (bf >= 0) & (bf < B) & (frame.to(bf.dtype) == bf)
+    boxes = gt_boxes[frame]                                                    # [P, G, 8]
+    extra = ops.device_constant([float(v) for v in extra_width], torch.float32, points.device)
+    x, y, z = points[:, 1:2], points[:, 2:3], points[:, 3:4]
+    az = torch.abs(z - boxes[..., 2]).double()
+    sx, sy = x - boxes[..., 0], y - boxes[..., 1]
+    cosa, sina = torch.cos(-boxes[..., 6]), torch.sin(-boxes[..., 6])
+    ax = torch.abs(sx * cosa + sy * (-sina)).double()
+    ay = torch.abs(sx * sina + sy * cosa).double()
+    margin = float(np.float32(1e-5))
+
+    def inside(sizes):
+        half = sizes.double() / 2.0
+        return ~(az > half[..., 2]) & (ax < half[..., 0] + margin) & (ay < half[..., 1] + margin) & valid[:, None]
+    plain, ext = inside(boxes[..., 3:6]), inside(boxes[..., 3:6] + extra)
+    first = (torch.cumsum(plain.long(), dim=1) == 0).sum(dim=1)                # the first box that holds the point, G if none
+    fg = first < G
+    idx = torch.clamp(first, max=G - 1)
+    cls = torch.ones_like(labels) if num_class == 1 else boxes[torch.arange(P, device=points.device), idx, 7].long()
+    labels = torch.where(fg ^ ext.any(dim=1), torch.full_like(labels, -1), labels)      # the reference's order: ignore flag,
+    labels = torch.where(fg, cls, labels)                                              # then the class over every fg row
+    return labels, torch.where(fg, first, torch.full_like(first, -1))
+
+
+def composed_point_cls_loss(point_cls_preds, point_cls_labels, weight):
+    """get_cls_layer_loss (point_head_template.py:131-155) in torch under autograd: one-hot targets and a weights tensor.
+    -> (loss, pos_num) as 1-element tensors."""
+    num_class = point_cls_preds.shape[1]
+    positives = point_cls_labels > 0
+    cls_weights = ((point_cls_labels == 0) * 1.0 + 1.0 * positives).to(point_cls_preds.dtype)
+    pos_normalizer = positives.sum(dim=0).to(point_cls_preds.dtype)
+    cls_weights = cls_weights / torch.clamp(pos_normalizer, min=1.0)
+    one_hot = point_cls_preds.new_zeros(point_cls_labels.shape[0], num_class + 1)
+    one_hot.scatter_(-1, (point_cls_labels * (point_cls_labels >= 0).long()).unsqueeze(dim=-1), 1.0)
+    loss = sigmoid_focal_loss(point_cls_preds, one_hot[..., 1:], cls_weights).sum() * weight
+    return loss.view(1), pos_normalizer.view(1)
+
+
+@DENSE_HEADS.register_module
+class PointHeadSimple(nn.Module):
+    """VR/pcdet/models/dense_heads/point_head_simple.py:7-97 over point_head_template.py: the keypoint segmentation head of
+    PV-RCNN.  The reference's constructor, config keys (CLS_FC, CLASS_AGNOSTIC, USE_POINT_FEATURES_BEFORE_FUSION,
+    TARGET_CONFIG.GT_EXTRA_WIDTH, LOSS_CONFIG.LOSS_WEIGHTS.point_cls_weight) and parameter names (cls_layers.{0,1,3,4,..}).
+
+    `forward` writes batch_dict['point_cls_scores'] [P] (max over classes of the sigmoid) and, in training mode, assigns the
+    targets of batch_dict['gt_boxes'] to batch_dict['point_coords']; `get_loss` is the focal segmentation loss.  The FC
+    layers run on channels-last rows (F.linear + ops.batch_norm_rows).  Targets and loss are chosen per call by
+    DF3D_POINT_HEAD_FUSED (default 1):
+      fused     ops.point_head_targets + ops.point_cls_loss (csrc/pointhead.hip): one launch for all frames, no one-hot and
+                no weights tensor, nothing read back; CPU tensors are refused;
+      composed  the reference's formulation in torch under autograd, vectorised over [P, G] with no per-frame loop.
+    PointHeadBox, PointIntraPartOffsetHead and this fork's AuxPointHeadSimple are not provided."""
+
+    def __init__(self, num_class, input_channels, model_cfg, **kwargs):
+        super().__init__()
+        self.model_cfg = model_cfg
+        self.num_class = int(num_class)
+        fc_cfg = _get(model_cfg, "CLS_FC")
+        if fc_cfg is None:
+            raise KeyError("PointHeadSimple: the config has no CLS_FC")
+        self.cls_layers = self.make_fc_layers(list(fc_cfg), input_channels, self.num_class)
+        self.forward_ret_dict = None
+
+    @staticmethod
+    def make_fc_layers(fc_cfg, input_channels, output_channels):
+        """point_head_template.py:35-47"""
+        fc_layers, c_in = [], input_channels
+        for width in fc_cfg:
+            fc_layers.extend([nn.Linear(c_in, width, bias=False), nn.BatchNorm1d(width), nn.ReLU()])
+            c_in = width
+        fc_layers.append(nn.Linear(c_in, output_channels, bias=True))
+        return nn.Sequential(*fc_layers)
+
+    def _training_setup(self):
+        """extra width and loss weight, read on first use: an eval-only config needs neither key"""
+        if getattr(self, "point_cls_weight", None) is None:
+            target_cfg = _get(self.model_cfg, "TARGET_CONFIG")
+            extra = _get(target_cfg, "GT_EXTRA_WIDTH") if target_cfg is not None else None
+            if extra is None:
+                raise KeyError("PointHeadSimple: the targets need TARGET_CONFIG.GT_EXTRA_WIDTH")
+            if len(extra) != 3:
+                raise ValueError("PointHeadSimple: GT_EXTRA_WIDTH must have 3 entries (got %d)" % len(extra))
+            weights = _get(_get(self.model_cfg, "LOSS_CONFIG") or {}, "LOSS_WEIGHTS") or {}
+            w = _get(weights, "point_cls_weight")
+            if w is None:
+                raise KeyError("PointHeadSimple: the loss needs LOSS_CONFIG.LOSS_WEIGHTS.point_cls_weight")
+            self.gt_extra_width = [float(v) for v in extra]
+            self.point_cls_weight = float(w)
+
+    def assign_targets(self, input_dict):
+        """point_head_simple.py:20-53: point_coords [P, 4] (b, x, y, z), gt_boxes [B, G, 8] -> {'point_cls_labels' [P] int64}"""
+        self._training_setup()
+        point_coords, gt_boxes = input_dict["point_coords"], input_dict["gt_boxes"]
+        if gt_boxes.dim() != 3 or gt_boxes.shape[2] != 8 or point_coords.dim() != 2 or point_coords.shape[1] != 4:
+            raise ValueError("PointHeadSimple: point_coords must be [P, 4] and gt_boxes [B, G, 8] (got %s, %s)"
+                             % (tuple(point_coords.shape), tuple(gt_boxes.shape)))
+        if point_head_fused():
+            labels = ops.point_head_targets(point_coords.detach().to(torch.float32).contiguous(),
+                                            gt_boxes.detach().to(torch.float32).contiguous(), self.gt_extra_width, self.num_class)
+        else:
+            with torch.no_grad():
+                labels, _ = composed_point_targets(point_coords, gt_boxes, self.gt_extra_width, self.num_class)
+        return {"point_cls_labels": labels}
+
+    def cls_rows(self, point_features):
+        """cls_layers on channels-last rows [P, C] -> point_cls_preds [P, num_class]"""
+        x, layers = point_features, list(self.cls_layers)
+        for k in range(0, len(layers) - 1, 3):
+            x = ops.batch_norm_rows(layers[k + 1], F.linear(x, layers[k].weight), relu=True)
+        return F.linear(x, layers[-1].weight, layers[-1].bias)
+
+    def forward(self, batch_dict):
+        key = "point_features_before_fusion" if _get(self.model_cfg, "USE_POINT_FEATURES_BEFORE_FUSION", False) else "point_features"
+        point_features = batch_dict[key]
+        if point_head_fused() and not point_features.is_cuda:
+            raise ops._lib.Df3dError("PointHeadSimple: %s must live on the GPU (got %s); the fused mode has no CPU path "
+                                     "(DF3D_POINT_HEAD_FUSED=0 is the torch composition)" % (key, point_features.device))
+        point_cls_preds = self.cls_rows(point_features)
+        ret_dict = {"point_cls_preds": point_cls_preds}
+        batch_dict["point_cls_scores"] = torch.sigmoid(point_cls_preds).max(dim=-1)[0]
+        if self.training:
+            ret_dict["point_cls_labels"] = self.assign_targets(batch_dict)["point_cls_labels"]
+        self.forward_ret_dict = ret_dict
+        return batch_dict
+
+    def get_cls_layer_loss(self, tb_dict=None):
+        """point_head_template.py:131-155; the tb_dict values are detached device tensors (nothing is read back)"""
+        self._training_setup()
+        r = self.forward_ret_dict
+        if not r or "point_cls_labels" not in r:
+            raise KeyError("PointHeadSimple.get_loss follows a training-mode forward (no point_cls_labels)")
+        preds = r["point_cls_preds"].view(-1, self.num_class)
+        labels = r["point_cls_labels"].view(-1)
+        if point_head_fused():
+            loss, pos_num = ops.point_cls_loss(preds, labels, self.point_cls_weight)
+        else:
+            loss, pos_num = composed_point_cls_loss(preds, labels, self.point_cls_weight)
+        point_loss_cls = loss[0]
+        tb_dict = {} if tb_dict is None else tb_dict
+        tb_dict.update(point_loss_cls=point_loss_cls.detach(), point_pos_num=pos_num[0].detach())
+        return point_loss_cls, tb_dict
+
+    def get_loss(self, tb_dict=None):
+        """-> (point_loss, tb_dict) with point_loss_cls and point_pos_num"""
+        tb_dict = {} if tb_dict is None else tb_dict
+        point_loss_cls, tb_dict_1 = self.get_cls_layer_loss()
+        tb_dict.update(tb_dict_1)
+        return point_loss_cls, tb_dict
 
 
 @MAP_TO_BEV.register_module

@@ -10,6 +10,7 @@ names, argument order, caller-allocated outputs and error behaviour as the pybin
   gather_points_ext             TF/mmdet3d/ops/gather_points/src/gather_points.cpp:54-59
   iou3d_cuda                    TF/mmdet3d/ops/iou3d/src/iou3d.cpp (boxes_overlap_bev_gpu / boxes_iou_bev_gpu / nms_gpu / nms_normal_gpu)
   pointnet2_stack_cuda          VR/pcdet/ops/pointnet2/pointnet2_stack/src/pointnet2_api.cpp:14,19-20 (voxel query, stack grouping)
+  roiaware_pool3d_cuda          VR/pcdet/ops/roiaware_pool3d/src/roiaware_pool3d.cpp (points_in_boxes_gpu)
 
 `install()` puts them into `sys.modules` under the import paths the reference's Python wrappers use, so that
 `from . import sparse_conv_ext` (TF/mmdet3d/ops/spconv/ops.py:17), `from .voxel_layer import hard_voxelize`
@@ -22,7 +23,7 @@ import sys
 NAMES = ("sparse_conv_ext", "voxel_layer", "MultiScaleDeformableAttention", "furthest_point_sample_ext", "ball_query_ext",
          "group_points_ext", "gather_points_ext", "iou3d_cuda")
 # the shims of the pcdet tree (NAMES is the mmdet3d / Det3D set)
-PCDET_NAMES = ("pointnet2_stack_cuda",)
+PCDET_NAMES = ("pointnet2_stack_cuda", "roiaware_pool3d_cuda")
 
 # import paths of the reference's wrappers (module attribute of a package, or a top-level module)
 ALIASES = {
@@ -36,6 +37,7 @@ ALIASES = {
     "gather_points_ext": ("mmdet3d.ops.gather_points.gather_points_ext", "det3d.ops.gather_points.gather_points_ext"),
     "iou3d_cuda": ("mmdet3d.ops.iou3d.iou3d_cuda",),
     "pointnet2_stack_cuda": ("pcdet.ops.pointnet2.pointnet2_stack.pointnet2_stack_cuda",),
+    "roiaware_pool3d_cuda": ("pcdet.ops.roiaware_pool3d.roiaware_pool3d_cuda",),
 }
 
 

@@ -1711,6 +1711,124 @@ def rcnn_loss(rcnn_cls, rcnn_reg, targets, spec):
     return _RcnnLoss.apply(rcnn_cls, rcnn_reg, targets, spec)
 
 
+POINT_HEAD_MAX_GT = 1024           # DF3D_POINT_HEAD_MAX_GT (= ROI_MAX_GT): ground-truth rows per frame
+POINT_HEAD_GT_CHUNK = 128          # DF3D_POINT_HEAD_GT_CHUNK: rows staged in LDS at a time
+POINT_HEAD_MAX_POINTS = 1 << 24    # rows of one launch (pos_num is a float32 count)
+POINT_HEAD_MAX_CLASSES = 64
+
+
+def points_in_boxes(boxes, pts, out=None):
+    """points_in_boxes_gpu of the reference's roiaware_pool3d (csrc/pointhead.hip): boxes [B, N, 7], pts [B, npts, 3] fp32 ->
+    int32 [B, npts], the index of the FIRST box that holds the point, else -1 (z test strict, xy margin 1e-5).  out: the
+    caller's tensor, every element written."""
+    lib = _lib.load()
+    _chk(boxes, torch.float32, "boxes")
+    _chk(pts, torch.float32, "pts")
+    if boxes.dim() != 3 or boxes.shape[2] != 7 or pts.dim() != 3 or pts.shape[2] != 3 or boxes.shape[0] != pts.shape[0]:
+        raise ValueError("points_in_boxes: boxes must be [B, N, 7] and pts [B, npts, 3] (got %s, %s)"
+                         % (tuple(boxes.shape), tuple(pts.shape)))
+    B, N, npts = int(boxes.shape[0]), int(boxes.shape[1]), int(pts.shape[1])
+    if B > 65535:
+        raise NotImplementedError("points_in_boxes: %d frames exceed 65535" % B)
+    if out is None:
+        out = torch.empty((B, npts), dtype=torch.int32, device=pts.device)
+    else:
+        _chk(out, torch.int32, "box_idx_of_points")
+        if tuple(out.shape) != (B, npts):
+            raise ValueError("points_in_boxes: box_idx_of_points must be [B, npts] = [%d, %d]" % (B, npts))
+    lib.df3d_points_in_boxes(_ptr(boxes), _ptr(pts), B, N, npts, _ptr(out), _stream())
+    return out
+
+
+def _point_rows(points, what):
+    _chk(points, torch.float32, "points")
+    if points.dim() != 2 or points.shape[1] != 4:
+        raise ValueError("%s: points must be [P, 4] = (frame, x, y, z) (got %s)" % (what, tuple(points.shape)))
+    P = int(points.shape[0])
+    if P > POINT_HEAD_MAX_POINTS:
+        raise NotImplementedError("%s: %d points exceed %d" % (what, P, POINT_HEAD_MAX_POINTS))
+    return P
+
+
+def point_head_targets(points, gt_boxes, extra_width, num_class, want_box_idx=False):
+    """PointHeadTemplate.assign_stack_targets as PointHeadSimple calls it (ignore flag, no box or part labels) for all frames
+    in one launch, nothing read back (csrc/pointhead.hip).  points [P, 4] fp32 (frame, x, y, z) in any row order, gt_boxes
+    [B, G, 8] fp32 (zero-padded rows take part, as in the reference), extra_width the three GT_EXTRA_WIDTH values.
+    -> labels [P] int64: 1 (num_class 1) or the class of the first box that holds the point, -1 inside an enlarged box only,
+    0 elsewhere and for a row of no frame 0..B-1; with want_box_idx also that box's row, int32 [P], or -1."""
+    lib = _lib.load()
+    P = _point_rows(points, "point_head_targets")
+    B, G = _gt_boxes(gt_boxes)
+    if G > POINT_HEAD_MAX_GT:
+        raise NotImplementedError("point_head_targets: %d ground-truth rows per frame exceed %d" % (G, POINT_HEAD_MAX_GT))
+    extra = [float(v) for v in extra_width]
+    if len(extra) != 3:
+        raise ValueError("point_head_targets: GT_EXTRA_WIDTH must have 3 entries (got %d)" % len(extra))
+    if int(num_class) < 1:
+        raise ValueError("point_head_targets: num_class must be >= 1 (got %d)" % num_class)
+    labels = torch.empty((P,), dtype=torch.int64, device=points.device)
+    box_idx = torch.empty((P,), dtype=torch.int32, device=points.device) if want_box_idx else None
+    ex_p, keep = _lib.float_arr(extra)
+    lib.df3d_point_head_targets(_ptr(points), P, _ptr(gt_boxes), B, G, ex_p, int(num_class), _ptr(labels), _ptr(box_idx), _stream())
+    return (labels, box_idx) if want_box_idx else labels
+
+
+def _point_loss_args(preds, labels):
+    if not preds.is_cuda:
+        raise _lib.Df3dError("point_cls_preds must live on the GPU (got %s); the MI355X path has no CPU fallback" % preds.device)
+    if preds.dtype != torch.float32 or preds.dim() != 2 or (preds.shape[1] > 1 and preds.stride(1) != 1):
+        raise ValueError("point_cls_loss: point_cls_preds must be a CUDA fp32 [P, num_class] view with unit column stride")
+    P, C = int(preds.shape[0]), int(preds.shape[1])
+    if C < 1 or C > POINT_HEAD_MAX_CLASSES:
+        raise NotImplementedError("point_cls_loss: 1..%d classes (got %d)" % (POINT_HEAD_MAX_CLASSES, C))
+    if P > POINT_HEAD_MAX_POINTS:
+        raise NotImplementedError("point_cls_loss: %d points exceed %d" % (P, POINT_HEAD_MAX_POINTS))
+    _chk(labels, torch.int64, "point_cls_labels")
+    if labels.numel() != P:
+        raise ValueError("point_cls_loss: point_cls_labels must hold %d values, one per row of point_cls_preds (got %d)"
+                         % (P, labels.numel()))
+    return P, C
+
+
+class _PointClsLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, preds, labels, weight):
+        lib = _lib.load()
+        P, C = _point_loss_args(preds, labels)
+        dev = preds.device
+        loss = torch.empty((1,), dtype=torch.float32, device=dev)
+        pos_num = torch.empty((1,), dtype=torch.float32, device=dev)
+        dlogit = torch.empty((P, C), dtype=torch.float64, device=dev)
+        nbytes = int(lib.df3d_point_cls_loss_workspace_bytes(P))
+        ws = _workspace(nbytes, dev)
+        lib.df3d_point_cls_loss(_ptr(preds), int(preds.stride(0)) if P else C, _ptr(labels), P, C, float(weight), _ptr(loss),
+                                _ptr(pos_num), _ptr(dlogit), _ptr(ws), nbytes, _stream())
+        ctx.save_for_backward(dlogit, pos_num)
+        ctx.weight, ctx.rows = float(weight), (P, C)
+        ctx.mark_non_differentiable(pos_num)
+        return loss, pos_num
+
+    @staticmethod
+    def backward(ctx, grad_loss, _grad_pos):
+        lib = _lib.load()
+        dlogit, pos_num = ctx.saved_tensors
+        P, C = ctx.rows
+        upstream = grad_loss.to(torch.float32).contiguous()
+        grad = torch.empty((P, C), dtype=torch.float32, device=dlogit.device)
+        lib.df3d_point_cls_loss_grad(_ptr(dlogit), _ptr(pos_num), _ptr(upstream), P, C, ctx.weight,
+                                     _ptr(grad), C, _stream())
+        return grad, None, None
+
+
+def point_cls_loss(point_cls_preds, labels, weight=1.0):
+    """get_cls_layer_loss of the point heads, fused (csrc/pointhead.hip): sigmoid focal loss (alpha 0.25, gamma 2) of
+    point_cls_preds [P, num_class] fp32 against labels [P] int64 (-1 ignored, 0 background, c = class c), no one-hot and no
+    weights tensor.  -> (loss [1], pos_num [1]) fp32 on the device: loss = weight * sum / max(#(label > 0), 1).  Differentiable
+    with respect to point_cls_preds: backward is one launch that scales the derivatives stored by the forward pass with the
+    upstream gradient and the normaliser, both read on the device."""
+    return _PointClsLoss.apply(point_cls_preds, labels, weight)
+
+
 class _HeadTargets(ctypes.Structure):
     _c_name_ = "df3d_head_targets"
     _fields_ = [(n, ctypes.c_void_p) for n in ("hm", "ind", "mask", "cat", "box")]

@@ -13,9 +13,8 @@ Sources are read as the reference reads them: rows stacked frame after frame (as
 collate and the sparse convolutions of this package leave them.
 
 Not provided, refused by name: SAMPLE_METHOD SPC (sectorized proposal-centric sampling), FILTER_NEIGHBOR_WITH_ROI and the
-vector-pool aggregation.  PointHeadSimple, whose `forward(sconv, gt_boxes)` in this fork no longer fits the detector's
-module loop, and the PVRCNN detector class are out of scope: the caller puts `point_cls_scores` into batch_dict for
-PVRCNNHead."""
+vector-pool aggregation.  The keypoint scores PVRCNNHead reads (`point_cls_scores`) come from PointHeadSimple
+(dualfusion/dense_heads.py); the PVRCNN detector (dualfusion/vr_detector.py) strings the modules together."""
 import torch
 import torch.nn as nn
 import torch.nn.functional as F

@@ -609,8 +609,8 @@ class PVRCNNHead(RoIHeadTemplate):
     the keypoints of VoxelSetAbstraction (dualfusion/pfe.py) through one StackSAModuleMSG -- one fused kernel per scale in
     eval mode (dualfusion/pointnet2_stack.py) -- and the reference's Conv1d layers refine them.  The proposal layer, the
     decoding, `forward_train` and `get_loss` are RoIHeadTemplate's, shared with VoxelRCNNHead (and with its limits: the
-    9000-candidate TRAIN proposals stay refused).  `point_cls_scores` comes from the caller: PointHeadSimple and the PVRCNN
-    detector class are not provided."""
+    9000-candidate TRAIN proposals stay refused).  `point_cls_scores` is what PointHeadSimple (dualfusion/dense_heads.py) writes
+    in front of this head in the PVRCNN detector; a caller that runs the head alone supplies it."""
 
     def __init__(self, input_channels, model_cfg, num_class=1, **kwargs):
         super().__init__()
@@ -660,8 +660,8 @@ class PVRCNNHead(RoIHeadTemplate):
         """rois [B, num_rois, 7 + C], point_coords [P, 4] (b, x, y, z) stacked frame after frame, point_features [P, C],
         point_cls_scores [P] -> [B * num_rois, g^3, C_out]."""
         if "point_cls_scores" not in batch_dict:
-            raise KeyError("PVRCNNHead.roi_grid_pool needs batch_dict['point_cls_scores'] [P] (the keypoint scores of the "
-                           "point head, which is not provided: the caller supplies them)")
+            raise KeyError("PVRCNNHead.roi_grid_pool needs batch_dict['point_cls_scores'] [P] (the keypoint scores "
+                           "PointHeadSimple writes)")
         batch_size = batch_dict["batch_size"]
         rois = batch_dict["rois"]
         point_coords = batch_dict["point_coords"]

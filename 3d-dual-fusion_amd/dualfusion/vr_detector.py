@@ -2,6 +2,10 @@
 backbone_3d -> map_to_bev -> backbone_2d -> dense_head -> roi_head -> post_processing, on a batch dict that already holds
 voxels (as VoxelBackBone8xFusion takes it).  Recall records, training and the losses are not here.
 
+The PV-RCNN detector (VR/pcdet/models/detectors/pv_rcnn.py): backbone_3d -> map_to_bev -> pfe -> backbone_2d -> dense_head ->
+point_head -> roi_head, on a batch dict that also holds `points`; eval returns boxes through the same `post_processing`,
+training returns the sum of the three heads' losses (get_training_loss, pv_rcnn.py:57-62).
+
 `post_processing` is the class-agnostic branch of Detector3DTemplate.post_processing (detector3d_template.py:251-269).  In
 the fused mode (DF3D_VR_TAIL_FUSED, default 1) the RoI decode and the selection of ALL frames are one call with no host round
 trip (ops.roi_decode_select, csrc/proposals.hip); the per-frame counts are read back in ONE copy to cut the padded results
@@ -9,9 +13,9 @@ into the reference's list of dicts.  The composed mode is the reference's per-fr
 import torch
 import torch.nn as nn
 
-from . import backbones, ops  # noqa: F401 (backbones registers the 3-D backbones)
+from . import backbones, ops, pfe  # noqa: F401 (backbones and pfe register the 3-D backbones and VoxelSetAbstraction)
 from .dense_heads import _get, tail_fused
-from .registry import BACKBONES_2D, BACKBONES_3D, DENSE_HEADS, DETECTORS_PCDET, MAP_TO_BEV, ROI_HEADS
+from .registry import BACKBONES_2D, BACKBONES_3D, DENSE_HEADS, DETECTORS_PCDET, MAP_TO_BEV, PFE, ROI_HEADS
 from .roi_heads import VoxelRCNNHead, class_agnostic_nms
 
 
@@ -77,6 +81,15 @@ def post_processing(batch_dict, cfg):
     return pred_dicts
 
 
+def _build_module(model_cfg, registry, key, **kwargs):
+    """the module model_cfg[key].NAME names in `registry`, built from that node (pcdet's `__all__[cfg.NAME](model_cfg=cfg, ..)`)"""
+    cfg = _need(model_cfg, key)
+    cls = registry.get(_need(cfg, "NAME"))
+    if cls is None:
+        raise KeyError("%s is not in the %s registry" % (_get(cfg, "NAME"), registry.name))
+    return cls(model_cfg=cfg, **kwargs)
+
+
 @DETECTORS_PCDET.register_module
 class VoxelRCNN(nn.Module):
     """model_cfg: BACKBONE_3D, MAP_TO_BEV, BACKBONE_2D, DENSE_HEAD, ROI_HEAD (each with its NAME) and POST_PROCESSING."""
@@ -86,11 +99,7 @@ class VoxelRCNN(nn.Module):
         self.model_cfg, self.num_class, self.class_names = model_cfg, num_class, class_names
 
         def build(registry, key, **kwargs):
-            cfg = _need(model_cfg, key)
-            cls = registry.get(_need(cfg, "NAME"))
-            if cls is None:
-                raise KeyError("%s is not in the %s registry" % (_get(cfg, "NAME"), registry.name))
-            return cls(model_cfg=cfg, **kwargs)
+            return _build_module(model_cfg, registry, key, **kwargs)
 
         self.backbone_3d = build(BACKBONES_3D, "BACKBONE_3D", input_channels=input_channels, grid_size=grid_size,
                                  voxel_size=voxel_size, point_cloud_range=point_cloud_range)
@@ -114,3 +123,73 @@ class VoxelRCNN(nn.Module):
         for module in self.module_list:
             batch_dict = module(batch_dict)
         return post_processing(batch_dict, self.roi_head.post_process_cfg), {}
+
+
+@DETECTORS_PCDET.register_module
+class PVRCNN(nn.Module):
+    """VR/pcdet/models/detectors/pv_rcnn.py.  model_cfg: BACKBONE_3D, MAP_TO_BEV, PFE, BACKBONE_2D, DENSE_HEAD, POINT_HEAD,
+    ROI_HEAD (each with its NAME) and POST_PROCESSING; the channel hand-offs are detector3d_template.py:100-173.  The batch
+    dict holds voxel_features, voxel_coords, points [N, 1 + input_channels] (b, x, y, z, ..) and batch_size; training adds
+    gt_boxes [B, G, 8].
+
+    Eval: `forward` -> (pred_dicts, {}).  Training: `forward` -> ({'loss': loss}, tb_dict, {}) with loss = rpn + point + rcnn.
+    The first stage trains through AnchorHeadSingle.forward_train; the RoI head makes its TRAIN proposals from that pass's
+    DETACHED predictions (NMS_CONFIG.TRAIN.NMS_PRE_MAXSIZE inside the 4096-candidate cap).  Not provided, refused by name:
+    DENSE_HEAD_3D and the auxiliary losses of this fork's backbone (BACKBONE_3D.SEG_LOSS, AUX_PTS_LOSS, AUX_CNS_LOSS)."""
+
+    def __init__(self, model_cfg, num_class, class_names, grid_size, point_cloud_range, voxel_size, input_channels=4):
+        super().__init__()
+        self.model_cfg, self.num_class, self.class_names = model_cfg, num_class, class_names
+        if _get(model_cfg, "DENSE_HEAD_3D", None) is not None:
+            raise NotImplementedError("PVRCNN: DENSE_HEAD_3D is not provided")
+        for key in ("SEG_LOSS", "AUX_PTS_LOSS", "AUX_CNS_LOSS"):
+            if _get(_need(model_cfg, "BACKBONE_3D"), key, None):
+                raise NotImplementedError("PVRCNN: BACKBONE_3D.%s is not provided (the auxiliary heads of the backbone have no "
+                                          "counterpart here)" % key)
+
+        def build(registry, key, **kwargs):
+            return _build_module(model_cfg, registry, key, **kwargs)
+
+        def classes(key):
+            return 1 if _get(_need(model_cfg, key), "CLASS_AGNOSTIC", False) else num_class
+
+        self.backbone_3d = build(BACKBONES_3D, "BACKBONE_3D", input_channels=input_channels, grid_size=grid_size,
+                                 voxel_size=voxel_size, point_cloud_range=point_cloud_range)
+        self.map_to_bev_module = build(MAP_TO_BEV, "MAP_TO_BEV", grid_size=grid_size)
+        self.pfe = build(PFE, "PFE", voxel_size=voxel_size, point_cloud_range=point_cloud_range,
+                         num_bev_features=self.map_to_bev_module.num_bev_features, num_rawpoint_features=input_channels)
+        self.backbone_2d = build(BACKBONES_2D, "BACKBONE_2D", input_channels=self.map_to_bev_module.num_bev_features)
+        self.dense_head = build(DENSE_HEADS, "DENSE_HEAD", input_channels=self.backbone_2d.num_bev_features,
+                                num_class=classes("DENSE_HEAD"), class_names=class_names, grid_size=grid_size,
+                                point_cloud_range=point_cloud_range, predict_boxes_when_training=True)
+        before_fusion = _get(_need(model_cfg, "POINT_HEAD"), "USE_POINT_FEATURES_BEFORE_FUSION", False)
+        self.point_head = build(DENSE_HEADS, "POINT_HEAD", num_class=classes("POINT_HEAD"), predict_boxes_when_training=True,
+                                input_channels=self.pfe.num_point_features_before_fusion if before_fusion
+                                else self.pfe.num_point_features)
+        self.roi_head = build(ROI_HEADS, "ROI_HEAD", input_channels=self.pfe.num_point_features,
+                              backbone_channels=getattr(self.backbone_3d, "backbone_channels", None),
+                              point_cloud_range=point_cloud_range, voxel_size=voxel_size, num_class=classes("ROI_HEAD"))
+        self.roi_head.post_process_cfg = _need(model_cfg, "POST_PROCESSING")
+        self.module_list = [self.backbone_3d, self.map_to_bev_module, self.pfe, self.backbone_2d, self.dense_head,
+                            self.point_head, self.roi_head]
+
+    def get_training_loss(self):
+        """pv_rcnn.py:57-62 -> (loss, tb_dict, disp_dict); the tb_dict values are detached device tensors"""
+        loss_rpn, tb_dict = self.dense_head.get_loss()
+        loss_point, tb_dict = self.point_head.get_loss(tb_dict)
+        loss_rcnn, tb_dict = self.roi_head.get_loss(tb_dict)
+        return loss_rpn + loss_point + loss_rcnn, tb_dict, {}
+
+    def forward(self, batch_dict):
+        if not self.training:
+            for module in self.module_list:
+                batch_dict = module(batch_dict)
+            return post_processing(batch_dict, self.roi_head.post_process_cfg), {}
+        for module in self.module_list[:4]:
+            batch_dict = module(batch_dict)
+        batch_dict = self.dense_head.forward_train(batch_dict)
+        self.dense_head.write_train_predictions(batch_dict)
+        batch_dict = self.point_head(batch_dict)
+        self.roi_head.forward_train(batch_dict)
+        loss, tb_dict, disp_dict = self.get_training_loss()
+        return {"loss": loss}, tb_dict, disp_dict

@@ -1666,6 +1666,52 @@ int df3d_rcnn_loss_grad(const float *rcnn_cls, int ld_cls, const float *rcnn_reg
                         const float *rcnn_cls_labels, const df3d_rcnn_loss_cfg *cfg, const double *norms,
                         const float *grad_losses, float *grad_cls, int ld_gcls, float *grad_reg, int ld_greg, void *stream);
 
+/* ---------------------------------------------------------------------------------------------------------------------
+ * PV-RCNN keypoint segmentation head (csrc/pointhead.hip): points in boxes, the targets of
+ * PointHeadSimple and its focal loss, with no device-to-host copy.
+ *
+ * df3d_points_in_boxes is points_in_boxes_kernel over check_pt_in_box3d
+ * (VR/pcdet/ops/roiaware_pool3d/src/roiaware_pool3d_kernel.cu:313-336, :16-36).
+ *   boxes [B][N][7] f32 (x, y, z, dx, dy, dz, heading), pts [B][npts][3] f32 -> box_idx_of_points [B][npts] int32: the FIRST
+ *   box (lowest index) that holds the point, else -1; every element is written.  A point is outside when
+ *   fabsf(z - cz) > dz / 2 (strict: on the top or bottom face is inside); it is rotated by -heading in float32; inside means
+ *   |local_x| < dx / 2 + 1e-5 and |local_y| < dy / 2 + 1e-5, compared in double with the float constant 1e-5.  Rows are not
+ *   filtered: a zero row is a box of size 0.  B <= 65535.
+ *
+ * df3d_point_head_targets is PointHeadTemplate.assign_stack_targets with set_ignore_flag=True, use_ball_constraint=False and
+ * no box or part labels (VR/pcdet/models/dense_heads/point_head_template.py:49-129), the one call PointHeadSimple.assign_targets
+ * makes (point_head_simple.py:20-53): one launch for all frames.
+ *   points [P][4] f32 (frame, x, y, z) in ANY row order (stacked frame after frame is the fast case), gt_boxes [B][G][8] f32
+ *   (box, class), extra_width [3] HOST floats (GT_EXTRA_WIDTH).  Per point: fg = inside some box of its frame, idx the first
+ *   such box; ext = inside some box with sizes dx + ex, dy + ey, dz + ez (added in float32, box_utils.enlarge_box3d).
+ *   labels [P] int64: where fg: 1 if num_class == 1, otherwise (long) gt_boxes[b][idx][7]; else -1 where ext; else 0 (the
+ *   reference sets -1 where fg != ext and then writes the class over every fg row, so a fg row keeps its class even when a
+ *   negative extra width leaves it outside every enlarged box).
+ *   box_idx [P] int32 (may be null): idx or -1.  A row whose frame is not one of 0..B-1 gets 0 / -1.  Zero-padded rows of
+ *   gt_boxes take part as the reference lets them (an enlarged zero row is a box of the extra width at the origin).
+ *   G == 0: all zeros.  Limits: G <= DF3D_POINT_HEAD_MAX_GT (staged in LDS DF3D_POINT_HEAD_GT_CHUNK rows at a time), P <= 2^24.
+ *
+ * df3d_point_cls_loss / df3d_point_cls_loss_grad are get_cls_layer_loss (point_head_template.py:131-155) with
+ * SigmoidFocalClassificationLoss(alpha 0.25, gamma 2) (VR/pcdet/utils/loss_utils.py:9-72), without the one-hot and weights
+ * tensors.
+ *   preds [P][num_class] f32 rows (row stride ld in floats), labels [P] int64.  The term of class c of point i has target
+ *   (label == c + 1) and weight (label >= 0).  loss [1] f32 = weight * sum / max(#(label > 0), 1); pos_num [1] f32 =
+ *   #(label > 0); dlogit [P][num_class] f64 = the derivative of every term (0 where label < 0), not yet normalised.  fp64
+ *   partials per workgroup at fixed positions and an ordered final sum: two runs are bit-identical.
+ * df3d_point_cls_loss_grad writes grad [P][num_class] (own row stride) = dlogit * upstream[0] * weight / max(pos_num[0], 1),
+ *   upstream [1] and pos_num [1] f32 read from DEVICE memory. */
+#define DF3D_POINT_HEAD_MAX_GT 1024
+#define DF3D_POINT_HEAD_GT_CHUNK 128
+int df3d_points_in_boxes(const float *boxes, const float *pts, int batch, int num_boxes, int num_pts, int32_t *box_idx_of_points,
+                         void *stream);
+int df3d_point_head_targets(const float *points, long long num_points, const float *gt_boxes, int batch, int max_gt,
+                            const float *extra_width, int num_class, int64_t *labels, int32_t *box_idx, void *stream);
+size_t df3d_point_cls_loss_workspace_bytes(long long num_points);
+int df3d_point_cls_loss(const float *preds, int ld, const int64_t *labels, long long num_points, int num_class, float weight,
+                        float *loss, float *pos_num, double *dlogit, void *workspace, size_t workspace_bytes, void *stream);
+int df3d_point_cls_loss_grad(const double *dlogit, const float *pos_num, const float *upstream, long long num_points,
+                             int num_class, float weight, float *grad, int ld_grad, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
