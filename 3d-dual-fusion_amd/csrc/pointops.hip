@@ -298,6 +298,283 @@ __global__ __launch_bounds__(512) void fps_kernel_half(const float *__restrict__
 #undef FPS_DPP_STEP
 }
 
+// Stacked FPS (VR/pcdet/ops/pointnet2/pointnet2_stack/src/sampling_gpu.cu:187-349): segment k of `xyz` = rows
+// [S_k, S_k + N_k), its picks go to idx[T_k, T_k + M_k) as GLOBAL rows; S and T are the prefix sums of the two device count
+// arrays, taken here, so nothing is read back and the B segments of a launch run side by side, one workgroup each.
+// The counts live on the device, so the launcher cannot choose the per-thread capacity: the kernel does, with a
+// workgroup-uniform branch on N_k into the same <PT> variants as fps_kernel (one workgroup per CU is all a launch places, so
+// the register count of the largest variant costs nothing).  The block is always 1024 threads; the reference's block size
+// `bs` enters only through the tie rule (larger distance, lower k mod bs, lower k), so thread t < bs plays the reference's
+// thread t and the others idle.  mode DF3D_FPS_STACK: bs = 1024 whatever N_k is and the loop keeps picking past N_k, as the
+// reference's kernel does; DF3D_FPS_FRAMES: bs = fps_block(N_k), min(N_k, M_k) picks and a cyclic tail, which is what
+// VoxelSetAbstraction's per-frame calls of the batch kernel and its padding give.
+// One pick = the thread's scan, the wave's arg-max by DPP, ONE barrier (two result buffers), and every thread reducing the
+// 16 wave results itself.
+struct StackFpsShared {
+  float v[2][16];
+  int t[2][16], k[2][16];
+  long long pre[2][16];
+};
+
+template <bool REG, int PT, bool XYZ>
+__device__ __forceinline__ void stack_fps_segment(const float *__restrict__ p, const int n, const int picks, const int bs,
+                                                  float *__restrict__ tg, int32_t *__restrict__ o, const int base,
+                                                  StackFpsShared &sh) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const bool owner = tid < bs;
+  float temp[PT];
+  float px[XYZ ? PT : 1], py[XYZ ? PT : 1], pz[XYZ ? PT : 1];
+  if (REG) {
+#pragma unroll
+    for (int i = 0; i < PT; ++i) {
+      const int k = tid + i * bs;
+      const bool valid = owner && k < n;
+      // a slot without a row never wins: its running minimum starts (and stays) below every real distance
+      temp[i] = valid ? 1e10f : -1.f;
+      if (XYZ) {
+        const int kk = valid ? k : 0;
+        px[i] = p[kk * 3];
+        py[i] = p[kk * 3 + 1];
+        pz[i] = p[kk * 3 + 2];
+      }
+    }
+  } else {
+    for (long long k = tid; k < n; k += 1024) tg[k] = 1e10f;      // (bs = 1024: n > 32 * 1024; a thread reads its own rows only)
+  }
+#define SFPS_DPP_STEP(CTRL)                                                                           \
+  do {                                                                                                \
+    Best ot;                                                                                          \
+    ot.v = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, me.v), CTRL, 0xf, 0xf, false)); \
+    ot.tid = __builtin_amdgcn_update_dpp(0, me.tid, CTRL, 0xf, 0xf, false);                           \
+    ot.k = __builtin_amdgcn_update_dpp(0, me.k, CTRL, 0xf, 0xf, false);                               \
+    me = better(me, ot);                                                                              \
+  } while (0)
+  float x1 = p[0], y1 = p[1], z1 = p[2];
+  for (int j = 1; j < picks; ++j) {
+    Best me = {-1.f, tid, 0};
+    if (REG) {
+#pragma unroll
+      for (int i = 0; i < PT; ++i) {
+        const int k = tid + i * bs;
+        float x2, y2, z2;
+        if (XYZ) {
+          x2 = px[i], y2 = py[i], z2 = pz[i];
+        } else {
+          const int kk = (owner && k < n) ? k : 0;
+          x2 = p[kk * 3], y2 = p[kk * 3 + 1], z2 = p[kk * 3 + 2];
+        }
+        const float d2 = fminf(dist2_fma(x2 - x1, y2 - y1, z2 - z1), temp[i]);
+        temp[i] = d2;
+        if (d2 > me.v) {
+          me.v = d2;
+          me.k = k;
+        }
+      }
+    } else {
+      for (long long k = tid; k < n; k += 1024) {
+        const float x2 = p[k * 3], y2 = p[k * 3 + 1], z2 = p[k * 3 + 2];
+        const float d2 = fminf(dist2_fma(x2 - x1, y2 - y1, z2 - z1), tg[k]);
+        tg[k] = d2;
+        if (d2 > me.v) {
+          me.v = d2;
+          me.k = (int)k;
+        }
+      }
+    }
+    // thread ids are distinct, so `better` is a total order and any pairing gives the same winner
+    SFPS_DPP_STEP(0xB1);                             // quad_perm [1, 0, 3, 2]
+    SFPS_DPP_STEP(0x4E);                             // quad_perm [2, 3, 0, 1]
+    SFPS_DPP_STEP(0x141);                            // row_half_mirror
+    SFPS_DPP_STEP(0x140);                            // row_mirror: every lane of a row of 16 holds the row's best
+    Best wb = {__builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, me.v), 0)),
+               __builtin_amdgcn_readlane(me.tid, 0), __builtin_amdgcn_readlane(me.k, 0)};
+#pragma unroll
+    for (int r = 1; r < 4; ++r) {
+      Best ot = {__builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, me.v), r * 16)),
+                 __builtin_amdgcn_readlane(me.tid, r * 16), __builtin_amdgcn_readlane(me.k, r * 16)};
+      wb = better(wb, ot);
+    }
+    const int par = j & 1;                           // the next pick writes the other buffer
+    if (lane == 0) {
+      sh.v[par][wave] = wb.v;
+      sh.t[par][wave] = wb.tid;
+      sh.k[par][wave] = wb.k;
+    }
+    __syncthreads();
+    Best r = {sh.v[par][0], sh.t[par][0], sh.k[par][0]};
+#pragma unroll
+    for (int w = 1; w < 16; ++w) {
+      Best ot = {sh.v[par][w], sh.t[par][w], sh.k[par][w]};
+      r = better(r, ot);
+    }
+    const int old = r.k;                             // in [0, n): a segment that gets here has a row, and row slots beat -1
+    if (tid == 0) o[j] = old + base;
+    x1 = p[(size_t)old * 3];
+    y1 = p[(size_t)old * 3 + 1];
+    z1 = p[(size_t)old * 3 + 2];
+  }
+#undef SFPS_DPP_STEP
+}
+
+// 24 576 < n <= 32 768 rows (the shipped KITTI frames): 32 rows per thread with the COORDINATES in registers (96 VGPRs) and
+// the running minima in LDS, [8][1024] float4 = 128 KiB of the CU's 160 (a thread reads and writes its own entries only: no
+// barrier for them; consecutive lanes, 16 bytes each: conflict-free ds_read / ds_write_b128).  The register variant of that
+// size keeps the minima and re-reads the coordinates on every pick.  bs = 1024 here: n > 1024.
+constexpr int SFPS_LDS_MIN_BYTES = FPS_MAXPT * 1024 * 4;
+
+__device__ __forceinline__ void stack_fps_segment_lds(const float *__restrict__ p, const int n, const int picks,
+                                                      int32_t *__restrict__ o, const int base, StackFpsShared &sh,
+                                                      float *__restrict__ smin) {
+  typedef float f4 __attribute__((ext_vector_type(4)));
+  constexpr int NQ = FPS_MAXPT / 4;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  f4 *sm = (f4 *)smin + tid;
+  float px[FPS_MAXPT], py[FPS_MAXPT], pz[FPS_MAXPT];
+#pragma unroll
+  for (int q = 0; q < NQ; ++q) {
+    f4 t;
+#pragma unroll
+    for (int h = 0; h < 4; ++h) {
+      const int i = 4 * q + h, k = tid + i * 1024;
+      const bool valid = k < n;
+      const int kk = valid ? k : 0;
+      t[h] = valid ? 1e10f : -1.f;
+      px[i] = p[kk * 3];
+      py[i] = p[kk * 3 + 1];
+      pz[i] = p[kk * 3 + 2];
+    }
+    sm[q * 1024] = t;
+  }
+#define SFPS_DPP_STEP(CTRL)                                                                           \
+  do {                                                                                                \
+    Best ot;                                                                                          \
+    ot.v = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, me.v), CTRL, 0xf, 0xf, false)); \
+    ot.tid = __builtin_amdgcn_update_dpp(0, me.tid, CTRL, 0xf, 0xf, false);                           \
+    ot.k = __builtin_amdgcn_update_dpp(0, me.k, CTRL, 0xf, 0xf, false);                               \
+    me = better(me, ot);                                                                              \
+  } while (0)
+  float x1 = p[0], y1 = p[1], z1 = p[2];
+  for (int j = 1; j < picks; ++j) {
+    Best me = {-1.f, tid, 0};
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) {
+      f4 t = sm[q * 1024];
+#pragma unroll
+      for (int h = 0; h < 4; ++h) {
+        const int i = 4 * q + h;
+        const float d2 = fminf(dist2_fma(px[i] - x1, py[i] - y1, pz[i] - z1), t[h]);
+        t[h] = d2;
+        if (d2 > me.v) {
+          me.v = d2;
+          me.k = tid + i * 1024;
+        }
+      }
+      sm[q * 1024] = t;
+    }
+    SFPS_DPP_STEP(0xB1);
+    SFPS_DPP_STEP(0x4E);
+    SFPS_DPP_STEP(0x141);
+    SFPS_DPP_STEP(0x140);
+    Best wb = {__builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, me.v), 0)),
+               __builtin_amdgcn_readlane(me.tid, 0), __builtin_amdgcn_readlane(me.k, 0)};
+#pragma unroll
+    for (int r = 1; r < 4; ++r) {
+      Best ot = {__builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, me.v), r * 16)),
+                 __builtin_amdgcn_readlane(me.tid, r * 16), __builtin_amdgcn_readlane(me.k, r * 16)};
+      wb = better(wb, ot);
+    }
+    const int par = j & 1;
+    if (lane == 0) {
+      sh.v[par][wave] = wb.v;
+      sh.t[par][wave] = wb.tid;
+      sh.k[par][wave] = wb.k;
+    }
+    __syncthreads();
+    Best r = {sh.v[par][0], sh.t[par][0], sh.k[par][0]};
+#pragma unroll
+    for (int w = 1; w < 16; ++w) {
+      Best ot = {sh.v[par][w], sh.t[par][w], sh.k[par][w]};
+      r = better(r, ot);
+    }
+    const int old = r.k;
+    if (tid == 0) o[j] = old + base;
+    x1 = p[old * 3];
+    y1 = p[old * 3 + 1];
+    z1 = p[old * 3 + 2];
+  }
+#undef SFPS_DPP_STEP
+}
+
+// lds_min: the launch carries SFPS_LDS_MIN_BYTES of dynamic LDS and segments of 24 577 .. 32 768 rows keep their minima there
+__global__ __launch_bounds__(1024) void stack_fps_kernel(const float *__restrict__ xyz, const int32_t *__restrict__ xyz_cnt,
+                                                         const long long N, const int32_t *__restrict__ num_sampled,
+                                                         const long long M, const int mode, const int lds_min,
+                                                         float *__restrict__ temp, int32_t *__restrict__ idx) {
+  extern __shared__ __align__(16) float sfps_min[];
+  __shared__ StackFpsShared sh;
+  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  // S_b, T_b: the counts before this segment (b < B <= 1024: one per thread), a negative count as 0
+  long long s = 0, t = 0;
+  if (tid < b) {
+    s = xyz_cnt[tid] > 0 ? xyz_cnt[tid] : 0;
+    t = num_sampled[tid] > 0 ? num_sampled[tid] : 0;
+  }
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) {
+    s += __shfl_xor(s, off, 64);
+    t += __shfl_xor(t, off, 64);
+  }
+  if (lane == 0) {
+    sh.pre[0][wave] = s;
+    sh.pre[1][wave] = t;
+  }
+  __syncthreads();
+  s = t = 0;
+#pragma unroll
+  for (int w = 0; w < 16; ++w) {
+    s += sh.pre[0][w];
+    t += sh.pre[1][w];
+  }
+  // clipped to the rows and the slots there are: nothing is read past N or written past M
+  const long long S = s < N ? s : N, T = t < M ? t : M;
+  long long nn = xyz_cnt[b] > 0 ? xyz_cnt[b] : 0, mm = num_sampled[b] > 0 ? num_sampled[b] : 0;
+  nn = nn < N - S ? nn : N - S;
+  mm = mm < M - T ? mm : M - T;
+  const int n = __builtin_amdgcn_readfirstlane((int)nn), m = __builtin_amdgcn_readfirstlane((int)mm);
+  const int base = __builtin_amdgcn_readfirstlane((int)S);
+  if (m == 0) return;
+  int32_t *o = idx + T;
+  if (n == 0) {
+    for (int j = tid; j < m; j += 1024) o[j] = -1;
+    return;
+  }
+  const float *p = xyz + (size_t)S * 3;
+  int bs = 1024, picks = m;
+  if (mode == DF3D_FPS_FRAMES) {
+    bs = 1 << (31 - __builtin_clz(n));               // fps_block(): the largest power of two <= n, at most 1024
+    bs = bs < 1024 ? bs : 1024;
+    picks = n < m ? n : m;
+  }
+  if (tid == 0) o[0] = base;
+  const int ppt = (n + bs - 1) / bs;
+  if (ppt <= 8)
+    stack_fps_segment<true, 8, true>(p, n, picks, bs, nullptr, o, base, sh);
+  else if (ppt <= 16)
+    stack_fps_segment<true, 16, true>(p, n, picks, bs, nullptr, o, base, sh);
+  else if (ppt <= 24)
+    stack_fps_segment<true, 24, true>(p, n, picks, bs, nullptr, o, base, sh);
+  else if (ppt <= FPS_MAXPT && lds_min)
+    stack_fps_segment_lds(p, n, picks, o, base, sh, sfps_min);
+  else if (ppt <= FPS_MAXPT)
+    stack_fps_segment<true, FPS_MAXPT, false>(p, n, picks, bs, nullptr, o, base, sh);
+  else
+    stack_fps_segment<false, 1, false>(p, n, picks, bs, temp + S, o, base, sh);
+  if (picks < m) {                                   // pad_keypoint_indices: the picks again, in their order
+    __syncthreads();
+    for (int j = picks + tid; j < m; j += 1024) o[j] = o[j % picks];
+  }
+}
+
 // out[b,c,p,s] = feat[b,c,idx[b,p,s]]  (gather_points: nsample == 1)
 __global__ __launch_bounds__(256) void group_points_kernel(const float *__restrict__ feat,
                                                            const int32_t *__restrict__ idx, int C, int N, int np,
@@ -408,6 +685,32 @@ extern "C" int df3d_furthest_point_sample(const float *xyz, int B, int N, int m,
     hipLaunchKernelGGL((fps_kernel<true, FPS_MAXPT, false>), dim3(B), dim3(bs), 0, stream, xyz, N, m, temp, idx);
   else
     hipLaunchKernelGGL((fps_kernel<false, 1, false>), dim3(B), dim3(bs), 0, stream, xyz, N, m, temp, idx);
+  DF3D_LAUNCH_CHECK();
+  return DF3D_OK;
+}
+
+extern "C" int df3d_stack_furthest_point_sample(const float *xyz, const int32_t *xyz_batch_cnt, long long N,
+                                                const int32_t *num_sampled, int B, long long M, int mode, float *temp,
+                                                int32_t *idx, void *stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  DF3D_CHECK_ARG(xyz && xyz_batch_cnt && num_sampled && temp && idx, "stack_furthest_point_sample: null argument");
+  DF3D_CHECK_ARG(B >= 0, "stack_furthest_point_sample: B = %d is negative", B);
+  DF3D_CHECK_ARG(B <= 1024, "stack_furthest_point_sample: B = %d segments (at most 1024 a launch: one thread sums one count)", B);
+  DF3D_CHECK_ARG(mode == DF3D_FPS_STACK || mode == DF3D_FPS_FRAMES,
+                 "stack_furthest_point_sample: mode %d (DF3D_FPS_STACK = 0 or DF3D_FPS_FRAMES = 1)", mode);
+  DF3D_CHECK_ARG(N >= 0 && N < (1ll << 31), "stack_furthest_point_sample: N = %lld rows (indices are int32: below 2^31)", N);
+  DF3D_CHECK_ARG(M >= 0 && M < (1ll << 31), "stack_furthest_point_sample: M = %lld slots (below 2^31)", M);
+  if (B == 0 || M == 0) return DF3D_OK;
+  // DF3D_STACK_FPS_LDS=0 (read per call): 24 577 .. 32 768-row segments keep their minima in registers and re-read coordinates
+  const char *sw = getenv("DF3D_STACK_FPS_LDS");
+  const int lds_min = !(sw && sw[0] == '0' && sw[1] == 0);
+  static bool lds_attr = false;
+  if (lds_min && !lds_attr) {
+    DF3D_HIP(hipFuncSetAttribute((const void *)stack_fps_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, SFPS_LDS_MIN_BYTES));
+    lds_attr = true;
+  }
+  hipLaunchKernelGGL(stack_fps_kernel, dim3(B), dim3(1024), lds_min ? SFPS_LDS_MIN_BYTES : 0, stream, xyz, xyz_batch_cnt, N,
+                     num_sampled, M, mode, lds_min, temp, idx);
   DF3D_LAUNCH_CHECK();
   return DF3D_OK;
 }

@@ -1,7 +1,8 @@
 """`pointnet2_stack_cuda` (VR/pcdet/ops/pointnet2/pointnet2_stack/src/pointnet2_api.cpp:12-31): the entry points the voxel
 RoI pooling and the PV-RCNN point branch use -- voxel query, stack grouping with its gradient, and the stacked ball query --
-in the argument order of voxel_query.cpp:28-30, group_points.cpp:31-54 and ball_query.cpp, outputs allocated by the caller.
-The other entry points of that module (sampling, three_nn / interpolate, vector pool) are not provided."""
+in the argument order of voxel_query.cpp:28-30, group_points.cpp:31-54 and ball_query.cpp, outputs allocated by the caller;
+and the two samplers of sampling.cpp, `farthest_point_sampling_wrapper` and `stack_farthest_point_sampling_wrapper`.
+The other entry points of that module (three_nn / interpolate, vector pool) are not provided."""
 import torch
 
 from .. import _lib
@@ -90,4 +91,35 @@ def group_points_grad_wrapper(B, M, C, N, nsample, grad_out_tensor, idx_tensor, 
     from .. import ops
     ops.group_points_stack_backward(grad_out_tensor, idx_tensor, idx_batch_cnt_tensor, features_batch_cnt_tensor, int(N),
                                     out=grad_features_tensor)
+    return 1
+
+
+@runtime_errors
+def farthest_point_sampling_wrapper(B, N, npoint, xyz, temp, output):
+    """sampling.cpp:24-37: xyz float32 [B, N, 3] -> output int32 [B, npoint] (first pick = row 0).  `temp` [B, N] is taken
+    as holding 1e10, as the reference's callers fill it (it is initialised here); its contents afterwards are unspecified."""
+    for t, nm in ((xyz, "xyz"), (temp, "temp"), (output, "output")):
+        need_cuda_contiguous(t, nm)
+    _need_dtype(xyz, torch.float32, "xyz")
+    _need_dtype(temp, torch.float32, "temp")
+    _need_dtype(output, torch.int32, "output")
+    if tuple(xyz.shape) != (B, N, 3) or temp.numel() < B * N or output.numel() < B * npoint:
+        raise RuntimeError("farthest_point_sampling: xyz [B, N, 3], temp [B, N], output [B, npoint]")
+    _lib.load().df3d_furthest_point_sample(_ptr(xyz), int(B), int(N), int(npoint), _ptr(temp), _ptr(output), _stream())
+    return 1
+
+
+@runtime_errors
+def stack_farthest_point_sampling_wrapper(xyz, temp, xyz_batch_cnt, idx, num_sampled_points):
+    """sampling.cpp:40-60: xyz float32 [N1 + N2 .., 3], xyz_batch_cnt / num_sampled_points int32 [B] -> idx int32
+    [sum(num_sampled_points)] of global rows, every segment in one launch.  `temp` [N] as above.  The counts are not read:
+    a segment is clipped to the rows of xyz and the slots of idx."""
+    for t, nm in ((xyz, "xyz"), (temp, "temp"), (xyz_batch_cnt, "xyz_batch_cnt"), (idx, "idx"),
+                  (num_sampled_points, "num_sampled_points")):
+        need_cuda_contiguous(t, nm)
+    _need_dtype(temp, torch.float32, "temp")
+    if temp.numel() < xyz.shape[0] or idx.dim() != 1:
+        raise RuntimeError("stack_farthest_point_sampling: temp [N], idx [M]")
+    from .. import ops
+    ops.stack_furthest_point_sample(xyz, xyz_batch_cnt, num_sampled_points, total=idx.shape[0], mode="stack", out=idx)
     return 1

@@ -3258,6 +3258,51 @@ def furthest_point_sample(xyz, m):
     return idx
 
 
+FPS_MODES = {"stack": 0, "frames": 1}            # DF3D_FPS_STACK / DF3D_FPS_FRAMES (include/df3d_hip.h)
+
+
+def stack_furthest_point_sample(xyz, xyz_batch_cnt, num_sampled, total=None, mode="stack", out=None):
+    """Furthest point sampling of B segments in one launch (one workgroup per segment): xyz float32 [N, 3] holds the
+    segments one after another, xyz_batch_cnt int32 [B] on the device -> int32 [M] GLOBAL rows, segment k's picks at
+    [T_k, T_k + M_k).  mode "stack" is the reference's stack_farthest_point_sample (block of 1024 whatever the segment's
+    size; a segment asked for more picks than it has rows keeps picking); "frames" is B calls of furthest_point_sample with
+    the keypoint padding of VoxelSetAbstraction (min(N_k, M_k) picks, then the picks again in their order).  A segment
+    without rows gives -1 in its slots.
+
+    num_sampled: an int (every segment), a list, or a device int32 tensor [B].  For an int or a list M is known on the
+    host; for a tensor `total` gives M without a read, and with total=None the sum is read back ONCE (the one
+    device-to-host copy of this function; the reference does the same with `npoint.sum().item()`).  The counts themselves
+    are never read back."""
+    lib = _lib.load()
+    _chk(xyz, torch.float32, "xyz")
+    _chk(xyz_batch_cnt, torch.int32, "xyz_batch_cnt")
+    if xyz.dim() != 2 or xyz.shape[1] != 3 or xyz_batch_cnt.dim() != 1:
+        raise _lib.Df3dError("stack_furthest_point_sample: xyz [N, 3], xyz_batch_cnt [B]")
+    if mode not in FPS_MODES:
+        raise _lib.Df3dError("stack_furthest_point_sample: mode %r (one of %s)" % (mode, sorted(FPS_MODES)))
+    B, N = xyz_batch_cnt.shape[0], xyz.shape[0]
+    if isinstance(num_sampled, torch.Tensor):
+        _chk(num_sampled, torch.int32, "num_sampled")
+        M = int(num_sampled.sum().item()) if total is None else int(total)
+    else:
+        per = [int(v) for v in num_sampled] if isinstance(num_sampled, (list, tuple)) else [int(num_sampled)] * B
+        M = sum(max(v, 0) for v in per)
+        num_sampled = device_constant(per, torch.int32, xyz.device) if B else xyz_batch_cnt
+    if tuple(num_sampled.shape) != (B,):
+        raise _lib.Df3dError("stack_furthest_point_sample: num_sampled must have one entry per segment (%d)" % B)
+    idx = torch.empty((M,), dtype=torch.int32, device=xyz.device) if out is None else _chk(out, torch.int32, "idx")
+    if M < 0 or idx.numel() < M:
+        raise _lib.Df3dError("stack_furthest_point_sample: idx has %d slots for M = %d" % (idx.numel(), M))
+    if B == 0 or M == 0:
+        return idx
+    if N == 0:                                        # (no row to point at: every segment is empty)
+        xyz = xyz.new_zeros((1, 3))
+    temp = torch.empty((max(N, 1),), dtype=torch.float32, device=xyz.device)
+    lib.df3d_stack_furthest_point_sample(_ptr(xyz), _ptr(xyz_batch_cnt), N, _ptr(num_sampled), B, M, FPS_MODES[mode],
+                                         _ptr(temp), _ptr(idx), _stream())
+    return idx
+
+
 def ball_query(min_radius, max_radius, nsample, xyz, new_xyz):
     lib = _lib.load()
     _chk(xyz, torch.float32, "xyz")

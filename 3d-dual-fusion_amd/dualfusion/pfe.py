@@ -6,8 +6,10 @@ constructor signature, config keys, parameter names and batch_dict keys.
 Device path: the BEV sample is one launch for all frames (ops.bev_interpolate, NCHW read in place, ordered backward), every
 set-abstraction scale is one fused kernel in eval mode (dualfusion/pointnet2_stack.py), and the per-frame counts of every
 source are one device count per tensor (an integer index_add_: torch.bincount reads its maximum back), not the reference's
-per-frame `.sum()` loops.  `forward` makes ONE device-to-host copy: the frames' point counts that size the per-frame
-ops.furthest_point_sample calls (frames differ in point count, and there is no stacked FPS kernel here).
+per-frame `.sum()` loops.  The keypoints of all frames come from one launch of the stacked FPS kernel
+(ops.stack_furthest_point_sample, mode "frames": frames differ in point count, and the counts stay on the device), so
+`forward` makes NO device-to-host copy; DF3D_VSA_STACK_FPS=0 keeps the per-frame ops.furthest_point_sample calls, which read
+the frames' point counts back once.  `sector_fps` is the reference's function of that name on the same kernel.
 
 Sources are read as the reference reads them: rows stacked frame after frame (ascending batch index), which is how pcdet's
 collate and the sparse convolutions of this package leave them.
@@ -15,6 +17,9 @@ collate and the sparse convolutions of this package leave them.
 Not provided, refused by name: SAMPLE_METHOD SPC (sectorized proposal-centric sampling), FILTER_NEIGHBOR_WITH_ROI and the
 vector-pool aggregation.  The keypoint scores PVRCNNHead reads (`point_cls_scores`) come from PointHeadSimple
 (dualfusion/dense_heads.py); the PVRCNN detector (dualfusion/vr_detector.py) strings the modules together."""
+import math
+import os
+
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
@@ -36,6 +41,37 @@ def pad_keypoint_indices(non_empty, num_keypoints):
     """voxel_set_abstraction.py:258-261: a frame with fewer points than keypoints repeats its sampled order"""
     times = int(num_keypoints / non_empty.shape[0]) + 1
     return non_empty.repeat(times)[:num_keypoints]
+
+
+def stack_fps_enabled():
+    return os.environ.get("DF3D_VSA_STACK_FPS", "1") != "0"
+
+
+def sector_fps(points, num_sampled_points, num_sectors):
+    """voxel_set_abstraction.py:78-121, the second half of SPC keypoint sampling: points [N, 3] are split into
+    `num_sectors` sectors by azimuth, sector s with n_s points gives min(n_s, ceil(n_s / N * num_sampled_points)) picks, and
+    all sectors are sampled by ONE stacked launch -> sampled points [N_out, 3], sector after sector.
+
+    The sector of a point as the reference computes it (atan2 + pi, divide, floor, clamp to [0, num_sectors]; a point that
+    lands on `num_sectors` belongs to no sector there either), a stable sort by sector, the per-sector counts by index_add_
+    and the pick counts in float64, all on the device; empty sectors are segments without rows and without picks.  One
+    device-to-host read, of the output length (the reference makes one per sector).  If no sector has a point the
+    reference samples the whole cloud as one segment; so does this."""
+    sector_size = math.pi * 2 / num_sectors
+    point_angles = torch.atan2(points[:, 1], points[:, 0]) + math.pi
+    sector_idx = (point_angles / sector_size).floor().clamp(min=0, max=num_sectors).long()
+    order = torch.argsort(sector_idx, stable=True)
+    xyz = points[order].contiguous()
+    ones = torch.ones(points.shape[0], dtype=torch.int32, device=points.device)
+    cnt = torch.zeros(num_sectors + 1, dtype=torch.int32, device=points.device).index_add_(0, sector_idx, ones)[:num_sectors]
+    ratio = cnt.double() / points.shape[0]
+    num = torch.minimum(cnt, torch.ceil(ratio * num_sampled_points).int()).contiguous()
+    idx = ops.stack_furthest_point_sample(xyz, cnt.contiguous(), num, mode="stack")
+    if idx.shape[0] == 0:
+        xyz = points.contiguous()
+        idx = ops.stack_furthest_point_sample(xyz, ops.device_constant([points.shape[0]], torch.int32, points.device),
+                                              int(num_sampled_points), mode="stack")
+    return xyz[idx.long()]
 
 
 @PFE.register_module
@@ -99,7 +135,15 @@ class VoxelSetAbstraction(nn.Module):
                                    bev_stride)
 
     def get_sampled_points(self, batch_dict):
-        """-> keypoints [B * NUM_KEYPOINTS, 4] (b, x, y, z).  The one device-to-host copy of `forward` is here."""
+        """-> keypoints [B * NUM_KEYPOINTS, 4] (b, x, y, z).
+
+        Stacked path (the default; read per call): the frames' rows in frame order, their counts on the device, ONE
+        `frames`-mode launch of ops.stack_furthest_point_sample with NUM_KEYPOINTS picks for every frame, one gather.  No
+        device-to-host copy.  It therefore cannot raise on an empty frame: that frame's keypoint rows come out as NaN
+        (its indices are -1).
+
+        DF3D_VSA_STACK_FPS=0: one ops.furthest_point_sample call per frame, sized by the frames' point counts, which are
+        read back (the one device-to-host copy of `forward` on that path); an empty frame raises ValueError."""
         batch_size = batch_dict["batch_size"]
         if self.point_source == "raw_points":
             src_points = batch_dict["points"][:, 1:4]
@@ -111,8 +155,16 @@ class VoxelSetAbstraction(nn.Module):
         # compaction per frame
         order = torch.argsort(batch_indices, stable=True)
         src_points = src_points[order].contiguous()
-        counts = frame_counts(batch_indices, batch_size).tolist()
         K = self.num_keypoints
+        if stack_fps_enabled():
+            num = torch.full((batch_size,), K, dtype=torch.int32, device=src_points.device)
+            idx = ops.stack_furthest_point_sample(src_points, frame_counts(batch_indices, batch_size), num,
+                                                  total=batch_size * K, mode="frames")
+            keypoints = src_points[idx.clamp(min=0).long()]
+            keypoints = torch.where((idx < 0)[:, None], keypoints.new_full((), float("nan")), keypoints)
+            batch_idx = torch.arange(batch_size, device=keypoints.device).view(-1, 1).repeat(1, K).view(-1, 1)
+            return torch.cat((batch_idx.float(), keypoints), dim=1)
+        counts = frame_counts(batch_indices, batch_size).tolist()
         keypoints_list, start = [], 0
         for bs_idx in range(batch_size):
             n = counts[bs_idx]

@@ -185,7 +185,8 @@ class NeighborVoxelSAModuleMSG(nn.Module):
 # scale in eval mode without autograd (ball query, gather, both MLP layers, max; nothing of size M * C * nsample is stored)
 # and the reference's formulation on the query and grouping ops otherwise (the composed path: it trains, and it serves
 # avg_pool, MLPs of another depth and channel counts the kernel does not); `DF3D_STACK_SA_FUSED=0` keeps the composed path
-# everywhere.  Not provided: `VectorPoolAggregationModuleMSG` (refused by name), stacked FPS, three_nn / interpolate.
+# everywhere.  `stack_farthest_point_sample` is the reference's stacked FPS (one launch for all segments).  Not provided:
+# `VectorPoolAggregationModuleMSG` (refused by name), three_nn / interpolate.
 def ball_query_stack(radius, nsample, xyz, xyz_batch_cnt, new_xyz, new_xyz_batch_cnt):
     """`BallQuery.apply` of the reference: idx int32 [M, nsample] local to the frame with the rows of empty balls set to 0,
     and empty_ball_mask bool [M].  The counts stay on the device."""
@@ -217,6 +218,15 @@ class QueryAndGroup(nn.Module):
             assert self.use_xyz, "Cannot have not features and not use xyz as a feature!"
             new_features = grouped_xyz
         return new_features, idx
+
+
+def stack_farthest_point_sample(xyz, xyz_batch_cnt, npoint):
+    """`StackFarthestPointSampling.apply` of the reference (pointnet2_utils.py:187-221): xyz [N1 + N2 .., 3], xyz_batch_cnt
+    [B], npoint an int, a list or a tensor [B] -> int32 [sum(npoint)] of global rows, all segments in one launch.  Not
+    differentiable.  With a tensor `npoint` its sum is read back once, as the reference reads it."""
+    with torch.no_grad():
+        return ops.stack_furthest_point_sample(xyz.contiguous(), xyz_batch_cnt.int().contiguous(),
+                                               npoint.int().contiguous() if isinstance(npoint, torch.Tensor) else npoint)
 
 
 def frame_counts(batch_idx, batch_size):

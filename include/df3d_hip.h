@@ -727,6 +727,24 @@ int df3d_pe_gather_add(const float *feat, const int64_t *sel, const float *xyz, 
  * ---------------------------------------------------------------------------------- */
 int df3d_furthest_point_sample(const float *xyz, int B, int N, int m, float *temp, int32_t *idx,
                                void *stream);
+/* stack_farthest_point_sampling_wrapper (VR/pcdet/ops/pointnet2/pointnet2_stack/src/sampling_gpu.cu:187-349): B segments
+ *   in ONE launch, one workgroup each.  xyz [N,3] holds the segments one after another; xyz_batch_cnt and num_sampled are
+ *   DEVICE int32 [B] and are never read back: segment k reads rows [S_k, S_k + N_k) and writes idx[T_k, T_k + M_k) (int32 [M],
+ *   GLOBAL rows = local index + S_k, as the reference writes them), S and T the prefix sums of the two arrays, taken in the
+ *   kernel.  Pick 0 is the segment's first row; pick j maximises the running minimum (started at 1e10) of
+ *   fma(dz, dz, fma(dy, dy, dx * dx)) in float32.  Equal maxima: the lower (k mod bs), then the lower k, k the row within
+ *   the segment.  mode DF3D_FPS_STACK: the reference's stacked kernel (bs = 1024 whatever N_k is; with M_k > N_k the loop
+ *   keeps picking).  DF3D_FPS_FRAMES: B independent calls of df3d_furthest_point_sample (bs = the largest power of two
+ *   <= N_k, at most 1024; min(N_k, M_k) picks, the other slots repeat them cyclically, idx[j] = idx[j mod min(N_k, M_k)]).
+ *   M_k = 0 writes nothing; N_k = 0 fills its M_k slots with -1 and reads no row; a negative count is 0; N_k is clipped to
+ *   the rows xyz has and M_k to the slots idx has.  temp [N] f32 is scratch (initialised here), used only by segments of
+ *   more than 32 * 1024 rows.  Refused (DF3D_EINVAL): a null pointer, B < 0, B > 1024, an unknown mode, N or M >= 2^31.
+ *   B = 0 or M = 0: DF3D_OK without a launch. */
+#define DF3D_FPS_STACK 0
+#define DF3D_FPS_FRAMES 1
+int df3d_stack_furthest_point_sample(const float *xyz, const int32_t *xyz_batch_cnt, long long N,
+                                     const int32_t *num_sampled, int B, long long M, int mode,
+                                     float *temp, int32_t *idx, void *stream);
 int df3d_ball_query(const float *new_xyz, const float *xyz, int B, int N, int m,
                     float min_radius, float max_radius, int nsample, int32_t *idx, void *stream);
 int df3d_group_points(const float *features, const int32_t *idx, int B, int C, int N, int npoint,
