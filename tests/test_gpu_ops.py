@@ -1006,6 +1006,21 @@ def _canon(ids):
     return np.lexsort(np.asarray(ids).T[::-1])
 
 
+def _check_gradients_vs_dense(sd, net, leaves, got, names, layers):
+    """The gradients `got` of loss = net(*leaves) against float64 autograd through the dense network `net`, in the bound of
+    the arithmetic mode in force (spconv_dense_reference.excess: 1e-4 of max |ref|; "bf16": elementwise, against the same
+    network on absolute values).  layers: the products in a row between an operand and its gradient -- the loss is the
+    squared output, so its gradient rows carry the forward's rounding back through every layer."""
+    from dualfusion import ops
+    leaves = [torch.from_numpy(a).double().requires_grad_(True) for a in leaves]
+    want = torch.autograd.grad(net(*leaves), leaves)
+    mags = [l.detach().abs().requires_grad_(True) for l in leaves]
+    A = torch.autograd.grad(net(*mags), mags)
+    for g, ref, a, name in zip(got, want, A, names):
+        rel, frac = sd.excess(g, ref, a, ops.CONV_PRECISION, layers)
+        assert frac <= 1.0, (name, rel, frac)
+
+
 def test_sparse_maxpool_module_golden_and_oracle(golden, dev):
     """SparseMaxPool3d forward / backward (one launch each over the neighbour table) against the reference's compiled
     CPU outputs (tests/golden/pool.npz) and the oracle -- bit for bit, incl. the zero-initialised output and the
@@ -1075,7 +1090,15 @@ def test_sparse_inverse_conv_golden_and_autograd(golden, dev):
     # training path: gradients flow through both convolutions
     xg = spconv.SparseConvTensor(T(f, dev).requires_grad_(True), T(ind, dev), CONV_BWD_SHAPE, CONV_BWD_BATCH)
     up(down(xg)).features.square().sum().backward()
-    assert xg.features.grad.abs().sum() > 0 and up.weight.grad.abs().sum() > 0 and down.weight.grad.abs().sum() > 0
+    # ... and equal those of the same two layers as dense float64 convolutions (tests/spconv_dense_reference.py)
+    import spconv_dense_reference as sd
+
+    def net(x, wd, wu):
+        sites, sites_shape, h = sd.conv(x, ind, CONV_BWD_SHAPE, CONV_BWD_BATCH, wd, None, st, pd)
+        return sd.inverse(h, sites, sites_shape, CONV_BWD_BATCH, wu, None, ind, CONV_BWD_SHAPE, st, pd)[2].square().sum()
+
+    _check_gradients_vs_dense(sd, net, (f, w, wi), (xg.features.grad, down.weight.grad, up.weight.grad),
+                              ("d features", "d down.weight", "d up.weight"), layers=4)
 
 
 def test_dynamic_voxelize_golden_and_oracle(golden, dev):
@@ -1123,7 +1146,12 @@ def test_sparse_conv_transpose_golden(golden, dev):
     xf = T(f, dev).requires_grad_(True)
     out = m(spconv.SparseConvTensor(xf, T(ind, dev), CONV_BWD_SHAPE, CONV_BWD_BATCH))
     out.features.square().sum().backward()
-    assert torch.isfinite(xf.grad).all() and float(xf.grad.abs().sum()) > 0 and float(m.weight.grad.abs().sum()) > 0
+    import spconv_dense_reference as sd
+
+    def net(x, wt):
+        return sd.conv_transpose(x, ind, CONV_BWD_SHAPE, CONV_BWD_BATCH, wt, None, st, pd, op)[2].square().sum()
+
+    _check_gradients_vs_dense(sd, net, (f, w), (xf.grad, m.weight.grad), ("d features", "d weight"), layers=2)
 
 
 def test_sparse_conv2d_and_pool2d_vs_dense_torch(dev):
