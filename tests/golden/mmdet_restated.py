@@ -11,7 +11,14 @@ the reference module's outputs; nothing here is imported by the product package.
   mmdet/models/losses/gaussian_focal_loss.py  GaussianFocalLoss
   mmdet/core/bbox/match_costs/match_cost.py   FocalLossCost
   mmdet/core/bbox/assigners/assign_result.py  AssignResult (fields only)
-  mmdet/core/bbox/samplers/pseudo_sampler.py, sampling_result.py   PseudoSampler / SamplingResult"""
+  mmdet/core/bbox/samplers/pseudo_sampler.py, sampling_result.py   PseudoSampler / SamplingResult
+
+and, for make_golden_backbones.py (the reference's own SparseEncoder over its own spconv layer):
+
+  mmcv/utils/registry.py                  Registry: register_module() as a decorator, get()
+  mmcv/cnn/bricks/conv.py, norm.py        build_conv_layer / build_norm_layer (the 'BN1d' entry)
+  mmdet/models/backbones/resnet.py        BasicBlock: the constructor and the norm1 / norm2 properties (the forward is the
+                                          reference's own, TF/mmdet3d/ops/sparse_block.py)"""
 import torch
 
 
@@ -135,3 +142,81 @@ class PseudoSampler(object):
         neg_inds = torch.nonzero(assign_result.gt_inds == 0, as_tuple=False).squeeze(-1).unique()
         gt_flags = bboxes.new_zeros(bboxes.shape[0], dtype=torch.uint8)
         return SamplingResult(pos_inds, neg_inds, bboxes, gt_bboxes, assign_result, gt_flags)
+
+
+# ------------------------------------------------------------------------------------------- mmcv builders, mmdet BasicBlock
+class Registry(object):
+    def __init__(self, name):
+        self.name, self.module_dict = name, {}
+
+    def get(self, key):
+        return self.module_dict.get(key)
+
+    def register_module(self, name=None, force=False, module=None):
+        def _register(cls):
+            self.module_dict[name or cls.__name__] = cls
+            return cls
+        return _register if module is None else _register(module)
+
+
+CONV_LAYERS = Registry('conv layer')
+CONV_LAYERS.register_module('Conv2d', module=torch.nn.Conv2d)
+NORM_LAYERS = Registry('norm layer')
+NORM_LAYERS.register_module('BN1d', module=torch.nn.BatchNorm1d)     # abbreviation 'bn' (infer_abbr of a _BatchNorm)
+
+
+def build_conv_layer(cfg, *args, **kwargs):
+    cfg_ = dict(type='Conv2d') if cfg is None else cfg.copy()
+    layer_type = cfg_.pop('type')
+    conv_layer = CONV_LAYERS.get(layer_type)
+    if conv_layer is None:
+        raise KeyError('Unrecognized norm type %s' % layer_type)
+    return conv_layer(*args, **kwargs, **cfg_)
+
+
+def build_norm_layer(cfg, num_features, postfix=''):
+    cfg_ = cfg.copy()
+    layer_type = cfg_.pop('type')
+    norm_layer = NORM_LAYERS.get(layer_type)
+    if norm_layer is None:
+        raise KeyError('Unrecognized norm type %s' % layer_type)
+    name = 'bn' + str(postfix)
+    requires_grad = cfg_.pop('requires_grad', True)
+    cfg_.setdefault('eps', 1e-5)
+    layer = norm_layer(num_features, **cfg_)
+    for param in layer.parameters():
+        param.requires_grad = requires_grad
+    return name, layer
+
+
+class BasicBlock(torch.nn.Module):
+    expansion = 1
+
+    def __init__(self, inplanes, planes, stride=1, dilation=1, downsample=None, style='pytorch', with_cp=False,
+                 conv_cfg=None, norm_cfg=dict(type='BN'), dcn=None, plugins=None):
+        super(BasicBlock, self).__init__()
+        assert dcn is None and plugins is None
+        self.norm1_name, norm1 = build_norm_layer(norm_cfg, planes, postfix=1)
+        self.norm2_name, norm2 = build_norm_layer(norm_cfg, planes, postfix=2)
+        self.conv1 = build_conv_layer(conv_cfg, inplanes, planes, 3, stride=stride, padding=dilation, dilation=dilation,
+                                      bias=False)
+        self.add_module(self.norm1_name, norm1)
+        self.conv2 = build_conv_layer(conv_cfg, planes, planes, 3, padding=1, bias=False)
+        self.add_module(self.norm2_name, norm2)
+        self.relu = torch.nn.ReLU(inplace=True)
+        self.downsample = downsample
+        self.stride = stride
+        self.dilation = dilation
+        self.with_cp = with_cp
+
+    @property
+    def norm1(self):
+        return getattr(self, self.norm1_name)
+
+    @property
+    def norm2(self):
+        return getattr(self, self.norm2_name)
+
+
+class Bottleneck(torch.nn.Module):
+    """only named by an import of the reference's sparse_block.py; never built here"""
